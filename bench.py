@@ -12,13 +12,18 @@ BVH replicated) and, for N>1, the 16-byte hit records are gathered onto rank 0 o
 Rays, BVH and hit records are resident in HBM for the whole timed region. The BVH is
 built on the GPU by the product path (rtk_dev_scene_build) before the timed region.
 
-Prints ONE JSON line on rank 0 (contract in the task statement): whole-job Mrays/s, plus
+Prints ONE JSON line on rank 0: whole-job Mrays/s (`value`) and the wall time of one timed step (`ms_per_step`). A plain run
+does only what that figure needs: scene, BVH, rays, warm-up, the K timed steps. `--dump-outputs DIR` then writes what the last
+timed step returned (a fixed sample of the records, dump_outputs below). `--full` adds everything else:
   roofline:     algorithmic bytes of the traversal kernel per unit it actually fetches for (a 64-ray tile for
                 the packet kernel, a ray for the per-lane kernels) / its measured duration vs 8 TB/s, the
                 fabric traffic of the same launch from the committed rocprofv3 PMC summary, and the kernel's
                 real limiter (VALU issue / lane utilisation) from the same counters
   cpu_baseline: the CPU oracle (a port of rtk.c's trace path) timed on this host's cores,
-                with the parity of the timed GPU result against it (every id mismatch is listed).
+                with the parity of the timed GPU result against it (every id mismatch is listed),
+  config:       steady-state and device-resident build times, the same frame without the image hint and as an any-hit
+                batch, hit fraction; N > 1: the other two treatments of the records and the kernel time per rank,
+  other_workloads (default workload): compact config-3 / config-5 lines.
 
 Other BASELINE.json configs (parity-test cases, not the headline line):
   --workload incoherent   config 3: 2^24 random rays on the same scene
@@ -152,6 +157,40 @@ def honest_fractions(achieved_gbs, traffic, k_ms, lim):
 
 def f32_ulps(a, b):
     return int(abs(int(np.float32(a).view(np.int32)) - int(np.float32(b).view(np.int32))))
+
+
+DUMP_RAYS = 1 << 20         # 28 MB of .npy for a sample of the 2^24-ray frame (the whole output would be 256 MB of records)
+
+
+def dump_sample(n, seed=6):
+    """The rays --dump-outputs writes: all of them up to DUMP_RAYS, else one ray per block of `stride` consecutive rays at an
+    offset drawn by synth's counter-based generator (the same rays on every run and machine, spread over the whole frame)."""
+    from rtk_amd import synth
+    if n <= DUMP_RAYS:
+        return np.arange(n, dtype=np.int64)
+    stride = -(-n // DUMP_RAYS)
+    blocks = -(-n // stride)
+    sel = np.arange(blocks, dtype=np.int64) * stride + (synth.u01(seed, 0, blocks) * np.float32(stride)).astype(np.int64)
+    return sel[sel < n]
+
+
+def dump_outputs(path, d_out, n, shadow):
+    """--dump-outputs: what the last timed step handed its caller, for the rays of dump_sample(n), as DIR/<name>.npy --
+    closest hit: the 16-byte records' t, u, v (float32) and global primitive id (float64, exact; 4294967295 = RTK_PRIM_NONE,
+    a miss); any hit: the occluded flag (float32). ray_index (float64) names the sampled rays."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    sel = dump_sample(n)
+    idx = torch.from_numpy(sel).to(d_out.device)
+    arrays = {"ray_index": sel.astype(np.float64)}
+    if shadow:
+        arrays["occluded"] = d_out[idx].cpu().numpy().astype(np.float32)
+    else:
+        rec = d_out.view(-1, HIT_BYTES)[idx].cpu().numpy().reshape(-1).view(HIT_RECORD_NP)
+        arrays.update(t=rec["t"], u=rec["u"], v=rec["v"], prim=rec["prim"].astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    log("dump: %d of %d rays' outputs written to %s (%s)" % (len(sel), n, path, ", ".join(sorted(arrays))))
 
 
 def other_workload(kind, steps, warmup, frame=4096, with_parity=True):
@@ -326,6 +365,13 @@ def main():
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="no GPU: gloo + CPU tensors + a stand-in tracer that only fills buffers; exercises the "
                          "multi-rank step loop / gather / timing / JSON plumbing in the CPU tests. Prints no perf claim.")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline figure as well: steady-state and device-resident builds, roofline "
+                         "(counting runs, committed PMC summaries), the frame without the image hint and as an any-hit batch, CPU "
+                         "baseline with parity, N>1: the other gather modes, default workload: the config-3 / config-5 lines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last step returned (rank 0's batch; a fixed sample of 2^20 rays "
+                         "of a larger one) as DIR/<name>.npy")
     args = ap.parse_args()
     DRY = args.dry_run_cpu
     if args.workload in ("shadow", "incoherent") and not args.no_sort_rays:
@@ -438,7 +484,7 @@ def main():
     info = ds.info()
     build_ms_first_call = info["build_ms"]
     build_ms_device_mesh = None
-    if args.bvh == "device" and not DRY:
+    if args.bvh == "device" and not DRY and args.full:
         # the first build of a process also pays one-time costs (code-object load, first touch of the
         # host pages by the DMA engine); build again for the steady-state figure, and once more with the
         # mesh already resident in HBM (no PCIe upload inside the build)
@@ -511,44 +557,45 @@ def main():
             shard.gather_records_wait(pending[b])
             pending[b] = []
 
-    # ---- algorithmic bytes from the counting build (not timed) ----------------------------
-    _, ctr = ds.trace_any_counted(rays, opts) if shadow else ds.trace_counted(rays, opts)
+    # ---- algorithmic bytes from the counting build (not timed; --full) ---------------------
     packet_kernel = args.workload == "coherent" and not args.no_tiling and not args.no_packet and not DRY
     # SURVEY.md section 8d per unit the kernel actually fetches for: the packet kernel fetches a node / triangle ONCE
     # per 64-ray tile (scalar cache), the per-lane kernels once per ray.
     # the per-lane kernels read the 64-byte compressed nodes (DevNodeQ) unless RTK_AMD_QNODES=0, the packet kernel the 128-byte exact ones
     lane_node_bytes = NODE_BYTES if os.environ.get("RTK_AMD_QNODES", "1") == "0" else 64
-    per_ray_bytes = n * (RAY_BYTES + out_bytes) + ctr["nodes"] * (NODE_BYTES if packet_kernel else lane_node_bytes) + ctr["triangles"] * TRI_BYTES
-    pk_ctr = None
-    if packet_kernel:
-        # the counting form of the kernel that is TIMED: rtk_packet_count2 = rtk_packet_beam2.S assembled with -DRTK_COUNT (three scalar
-        # counters per pair of tiles), plus the counting build of the C++ packet kernel on the tiles it hands back
-        try:
-            _, pk_ctr = ds.trace_packet_counted(rays, opts)
-        except api.RtkError as e:
-            log("packet counters not available (%s): pricing the C++ packet kernel's steps" % e)
-    if packet_kernel and pk_ctr:
-        fetched_nodes = pk_ctr["node_steps"] + pk_ctr["handed_back_node_steps"]
-        fetched_tris = pk_ctr["triangles_fetched"] + pk_ctr["handed_back_triangle_steps"]
-        alg_bytes = n * (RAY_BYTES + out_bytes) + fetched_nodes * NODE_BYTES + fetched_tris * TRI_BYTES
-        unit = ("PAIR of adjacent 8x8-pixel tiles (128 rays, one wave): 32 B per ray in, 16 B per ray out, each node (128 B) priced once per node "
-                "step of the pair and each triangle record (48 B) once per triangle of a leaf the pair enters; steps counted by rtk_packet_count2, "
-                "the kernel that is timed assembled with -DRTK_COUNT (rtk_dev_trace_rays_packet_counted), plus the C++ packet kernel's own "
-                "counting build on the %d tiles handed back" % pk_ctr["tiles_handed_back"])
-    elif packet_kernel:
-        alg_bytes = n * (RAY_BYTES + out_bytes) + ctr["wave_node_steps"] * NODE_BYTES + ctr["wave_triangle_steps"] * TRI_BYTES
-        unit = ("tile of 64 rays: each node (128 B) and triangle (48 B) priced once per tile; visit and step counts are those of the counting "
-                "C++ kernel (per-lane slab tests, one tile per wave)")
-    else:
-        alg_bytes = per_ray_bytes
-        unit = "ray: each lane fetches its own nodes (%d B) and triangles (48 B)" % lane_node_bytes
-        if args.sort_rays:
-            # the re-ordering pre-pass is inside the timed region: keys (32 B ray read, one 8-B word written: cell key over the
-            # ray's number), two radix passes over the words (8 B histogram read + 8 B read + 8 B written each), and the
-            # 8-B word the traversal reads per ray instead of counting
-            alg_bytes += n * (32 + 8 + 3 * 24 + 8)
-            per_ray_bytes = alg_bytes
-            unit += "; plus the ray re-ordering pre-pass (120 B per ray: keys, three radix passes over 8-byte words, the word read back), timed with the traversal"
+    ctr = pk_ctr = None
+    if args.full:
+        _, ctr = ds.trace_any_counted(rays, opts) if shadow else ds.trace_counted(rays, opts)
+        per_ray_bytes = n * (RAY_BYTES + out_bytes) + ctr["nodes"] * (NODE_BYTES if packet_kernel else lane_node_bytes) + ctr["triangles"] * TRI_BYTES
+        if packet_kernel:
+            # the counting form of the kernel that is TIMED: rtk_packet_count2 = rtk_packet_beam2.S assembled with -DRTK_COUNT (three scalar
+            # counters per pair of tiles), plus the counting build of the C++ packet kernel on the tiles it hands back
+            try:
+                _, pk_ctr = ds.trace_packet_counted(rays, opts)
+            except api.RtkError as e:
+                log("packet counters not available (%s): pricing the C++ packet kernel's steps" % e)
+        if packet_kernel and pk_ctr:
+            fetched_nodes = pk_ctr["node_steps"] + pk_ctr["handed_back_node_steps"]
+            fetched_tris = pk_ctr["triangles_fetched"] + pk_ctr["handed_back_triangle_steps"]
+            alg_bytes = n * (RAY_BYTES + out_bytes) + fetched_nodes * NODE_BYTES + fetched_tris * TRI_BYTES
+            unit = ("PAIR of adjacent 8x8-pixel tiles (128 rays, one wave): 32 B per ray in, 16 B per ray out, each node (128 B) priced once per node "
+                    "step of the pair and each triangle record (48 B) once per triangle of a leaf the pair enters; steps counted by rtk_packet_count2, "
+                    "the kernel that is timed assembled with -DRTK_COUNT (rtk_dev_trace_rays_packet_counted), plus the C++ packet kernel's own "
+                    "counting build on the %d tiles handed back" % pk_ctr["tiles_handed_back"])
+        elif packet_kernel:
+            alg_bytes = n * (RAY_BYTES + out_bytes) + ctr["wave_node_steps"] * NODE_BYTES + ctr["wave_triangle_steps"] * TRI_BYTES
+            unit = ("tile of 64 rays: each node (128 B) and triangle (48 B) priced once per tile; visit and step counts are those of the counting "
+                    "C++ kernel (per-lane slab tests, one tile per wave)")
+        else:
+            alg_bytes = per_ray_bytes
+            unit = "ray: each lane fetches its own nodes (%d B) and triangles (48 B)" % lane_node_bytes
+            if args.sort_rays:
+                # the re-ordering pre-pass is inside the timed region: keys (32 B ray read, one 8-B word written: cell key over the
+                # ray's number), two radix passes over the words (8 B histogram read + 8 B read + 8 B written each), and the
+                # 8-B word the traversal reads per ray instead of counting
+                alg_bytes += n * (32 + 8 + 3 * 24 + 8)
+                per_ray_bytes = alg_bytes
+                unit += "; plus the ray re-ordering pre-pass (120 B per ray: keys, three radix passes over 8-byte words, the word read back), timed with the traversal"
     sync()
 
     for k in range(args.warmup):
@@ -583,12 +630,15 @@ def main():
         sync()
     elapsed = time.perf_counter() - t_start
     kernel_ms = [ev_region[0].elapsed_time(ev_region[1]) / max(1, args.steps)]
+    d_out = d_outs[(args.steps - 1) % len(d_outs)] if args.steps else d_outs[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_out, n, shadow)
 
     # ---- the same frame WITHOUT the image hint (opts = NULL, what a host that only knows rays and records passes): the library looks
     # at the batch (two small launches and a wait per call), finds the image and runs the same kernels; records must be the same bytes
     no_hint = None
     any_image = None
-    if packet_kernel and world == 1 and args.steps:
+    if packet_kernel and world == 1 and args.steps and args.full:
         ref_out = d_outs[(args.steps - 1) % len(d_outs)].clone()
         k2 = max(3, args.steps // 4)
         ds.trace_device(d_rays, n, d_outs[0], None)
@@ -632,6 +682,7 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if world > 1 and args.full:
         # the same K steps under the other two treatments of the records, so that one line shows all three: a GPU that
         # traces 16 Grays/s produces ~260 GB/s of records, one xGMI link direction carries ~77 GB/s, and a root takes in at
         # most its 7 links -- what `value` includes decides what bounds it
@@ -654,20 +705,19 @@ def main():
     # N > 1 diagnostics: if the scaling is off, WHY -- a slow rank (kernel time per rank: min / max over the ranks of each
     # rank's mean over the timed steps) or an exchange that is not hidden (step time with the exchange minus step time without)
     rank_kernel = None
-    if world > 1:
+    if world > 1 and args.full:
         mine = torch.tensor([float(np.mean(kernel_ms)) if kernel_ms else 0.0], dtype=torch.float64, device=dev)
         every = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(every, mine)
         per_rank = [float(t.item()) for t in every]
         rank_kernel = {"per_rank": [round(x, 4) for x in per_rank], "min": round(min(per_rank), 4), "max": round(max(per_rank), 4),
                        "what": "mean over the timed steps of the traversal's time on each rank's launch stream (events around the launch), ms"}
-    d_out = d_outs[(args.steps - 1) % len(d_outs)] if args.steps else d_outs[0]
 
-    # ---- the result that was timed ---------------------------------------------------------
-    if shadow:
+    # ---- the result that was timed (--full: its hit fraction; the CPU baseline's parity) ---
+    if args.full and shadow:
         occ = d_out.cpu().numpy().astype(bool)
         hit_frac = float(occ.mean())
-    else:
+    elif args.full:
         rec = d_out.cpu().numpy().view(HIT_RECORD_DTYPE)
         hit_frac = float((rec["prim"] != 0xFFFFFFFF).mean())
 
@@ -676,22 +726,8 @@ def main():
             dist.destroy_process_group()
         return
 
-    # fabric traffic and limiter of the same launch from the committed rocprofv3 PMC summary (separate passes; see
-    # scripts/profile_workload.sh + scripts/summarize_profile.py). Dropped when the kernels changed since.
-    pj, traffic_src, fresh = (None, None, False) if DRY else load_pmc_summary(args.workload)
-    traffic = float(pj["hbm_traffic_bytes_per_launch"]) if (pj and fresh and args.bvh == "device") else None
-    limiter = limiter_from_pmc(pj) if (pj and fresh) else {}
-
     total_rays = n * world * args.steps
     mrays = total_rays / elapsed / 1e6
-    k_ms = float(np.mean(kernel_ms))
-    achieved = alg_bytes / (k_ms * 1e-3) / 1e9
-    h_frac, h_note, h_fbt, h_real = honest_fractions(achieved, traffic, k_ms, limiter)
-    lane_asm = os.environ.get("RTK_AMD_LANE_ASM", "1") != "0" and lane_node_bytes == 64 and not args.static
-    beam = os.environ.get("RTK_AMD_PACKET_BEAM", "2")
-    kernel_name = ({"0": "rtk_packet_hot", "1": "rtk_packet_beam"}.get(beam, "rtk_packet_beam2") + " (hand-written gfx950 assembly) + rtk_trace_packet_kernel<false> on the tiles it hands back" if packet_kernel else
-                   ("rtk_lane_hot_%s (hand-written gfx950 assembly) + " % ("any" if shadow else "closest") if lane_asm else "") +
-                   "rtk_trace_kernel<%d, false, false, %s>%s" % (1 if shadow else 0, "true" if lane_node_bytes == 64 else "false", " on the rays it hands back" if lane_asm else ""))
     out = {
         "metric": metric,
         "value": round(mrays, 2),
@@ -707,76 +743,92 @@ def main():
         "data": "synthetic" if not DRY else "none: --dry-run-cpu plumbing check, not a measurement",
         "config": {"workload": workload, "rays_per_gpu_per_step": n, "bvh": bvh_kind, "bvh_nodes": info["num_nodes"],
                    "bvh_build_s": round(t_build, 3), "bvh_build_ms_first_call": round(build_ms_first_call, 2),
-                   "bvh_build_ms_in_library": round(info["build_ms"], 2),
-                   "bvh_build_mtris_s": round(cfg["num_tris"] / max(info["build_ms"], 1e-9) / 1e3, 1) if info["build_ms"] else None,
-                   "bvh_build_ms_device_resident_mesh": round(build_ms_device_mesh, 2) if build_ms_device_mesh else None,
-                   "bvh_build_mtris_s_device_resident_mesh": round(cfg["num_tris"] / build_ms_device_mesh / 1e3, 1) if build_ms_device_mesh else None,
-                   "hit_fraction": round(hit_frac, 4),
                    "gather": {"striped": "every rank receives its stripe of every shard's records over RCCL (batched point-to-point, each link carries 1/N of a shard per step), overlapped with the next step's trace",
                               "root": "all records onto rank 0 over RCCL (batched point-to-point), overlapped with the next step's trace; bound by the root's incoming links",
                               "none": None}[mode],
-                   "value_without_gather_mrays_s": round(n * world * args.steps / elapsed_no_gather / 1e6, 2) if elapsed_no_gather else None,
-                   "value_root_gather_mrays_s": round(n * world * args.steps / other_modes["root"] / 1e6, 2) if "root" in other_modes else None,
-                   "value_striped_gather_mrays_s": round(n * world * args.steps / other_modes["striped"] / 1e6, 2) if "striped" in other_modes else None,
-                   "per_rank_kernel_ms": rank_kernel,
-                   "exposed_exchange_ms_per_step": ({how: round(((elapsed if how == mode else other_modes[how]) - elapsed_no_gather) / args.steps * 1e3, 4)
-                                                     for how in ("striped", "root") if (how == mode or how in other_modes)}
-                                                    if (world > 1 and elapsed_no_gather) else None),
-                   "without_image_hint": no_hint,
-                   "any_hit_on_the_same_image": any_image,
                    "launch": "static" if args.static else "persistent",
                    "ray_order": "RTK_TRACE_SORT_RAYS: re-ordered by origin cell inside every timed step" if args.sort_rays else "as given",
-                   "parallelism": "ray-batch shards x%d, BVH replicated" % world},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": h_frac, "traffic": traffic, "frac_by_traffic": h_fbt, "frac_note": h_note, "real_bound": h_real,
-                     "traffic_unit": ("bytes per launch of the traversal kernel crossing the L2 -> fabric boundary, Infinity-Cache (MALL) hits "
-                                      "INCLUDED: (2*FETCH_SIZE + WRITE_SIZE)*1024 from rocprofv3 PMC passes, %s; the scene is %.0f MB (the MALL "
-                                      "holds 256 MiB), so this is %s" % (traffic_src, info.get("total_device_bytes", 0) / 1e6,
-                                      "not pure HBM traffic" if info.get("total_device_bytes", 0) < 256 * 2 ** 20 else "mostly HBM traffic")) if traffic else
-                                     ("none: %s was measured on other kernel code (kernel_code_sha16 differs)" % traffic_src if pj else None),
-                     "unit_of_work": unit,
-                     "algorithmic_bytes_per_launch": int(alg_bytes),
-                     "kernel": kernel_name if not args.sort_rays else kernel_name + " preceded by the re-ordering pre-pass (rtk_ray_entry_keys_kernel, "
-                               "3 x k_sort_hist/k_scan_block/k_sort_scatter): kernel_ms is their sum per step",
-                     "kernel_ms": round(k_ms, 4),
-                     "limiter": dict(limiter, fabric_tb_s=round(traffic / pj["kernel_trace"]["average_ns"] / 1e3, 2) if traffic else None,
-                                     note=("VALU pipes busy `valu_busy` of the traversal kernel's time at `valu_lane_utilisation` "
-                                           "(SQ_ACTIVE_INST_VALU*4 / (1024 SIMDs * time * %.1f GHz), SQ_THREAD_CYCLES_VALU / (64 * SQ_ACTIVE_INST_VALU)); "
-                                           "`salu_issue` = SQ_INSTS_SALU / (256 CUs * time * clock): scalar instructions per cycle of a CU's one scalar unit; "
-                                           "`fabric_tb_s` = traffic / kernel time against ~6.3 TB/s achievable HBM and ~8.6 TB/s MALL gather rate; "
-                                           "counters from %s" % (CLOCK_GHZ, traffic_src))) if limiter else None,
-                     "visits_per_ray": {"nodes": round(ctr["nodes"] / n, 2), "leaves": round(ctr["leaves"] / n, 2),
-                                        "triangles": round(ctr["triangles"] / n, 2)},
-                     "wave_steps_per_64_rays": {"nodes": round(ctr["wave_node_steps"] * 64.0 / n, 1),
-                                                "triangles": round(ctr["wave_triangle_steps"] * 64.0 / n, 1),
-                                                "of": "rtk_trace_packet_kernel<true> (C++, one tile per wave, per-lane slab tests)" if packet_kernel else "the counting build of the per-lane kernel"},
-                     "timed_kernel_steps": ({"per_pair_of_tiles": {"node_steps": round(pk_ctr["node_steps"] / max(1, pk_ctr["pairs"]), 2),
-                                                                  "triangles_fetched": round(pk_ctr["triangles_fetched"] / max(1, pk_ctr["pairs"]), 2),
-                                                                  "triangle_group_tests": round(pk_ctr["triangle_group_tests"] / max(1, pk_ctr["pairs"]), 2)},
-                                             "pairs": pk_ctr["pairs"], "tiles_handed_back": pk_ctr["tiles_handed_back"],
-                                             "handed_back_node_steps": pk_ctr["handed_back_node_steps"], "handed_back_triangle_steps": pk_ctr["handed_back_triangle_steps"],
-                                             "counted_by": "rtk_packet_count2 (rtk_packet_beam2.S -DRTK_COUNT)"} if pk_ctr else None),
-                     "per_ray_model": {"bytes_per_ray": round(per_ray_bytes / n, 1), "gb_s": round(per_ray_bytes / (k_ms * 1e-3) / 1e9, 1),
-                                       "note": "every lane's visit priced at full size; caches absorb these for coherent rays, so this is "
-                                               "cache bandwidth demand, not a fraction of the HBM roofline"},
-                     "kernel_mrays_s": round(n / (k_ms * 1e-3) / 1e6, 1)},
+                   "parallelism": "ray-batch shards x%d, BVH replicated" % world}
     }
-    if args.bvh == "device" and build_ms_device_mesh:
-        # SURVEY.md section 8d, build formula with this build's sizes: 36 B positions in, the sort item out (< 2^24 triangles:
-        # one 8-B word = 40-bit code over the index, 5 passes; else a 12-B (key, index) pair, 8 passes), P passes x item read +
-        # written, 2 x 32 B binary node (refit write, collapse read), 128 B x wide nodes per triangle + 48 B triangle record out
-        # (key width from n: ceil(log2 n) + 8 bits in whole 8-bit passes, 3 ... 5 of them for the 8-byte words; rtk_build.hip)
-        lg = int(np.ceil(np.log2(max(2, cfg["num_tris"]))))
-        passes, item = (min(5, max(3, (lg + 8 + 7) // 8)), 8) if cfg["num_tris"] < (1 << 24) else (8, 12)
-        bpt = 36 + item + passes * 2 * item + 64 + 128.0 * info["num_nodes"] / cfg["num_tris"] + 48
-        gbs = cfg["num_tris"] * bpt / (build_ms_device_mesh * 1e-3) / 1e9
-        out["build"] = {"triangles": cfg["num_tris"], "ms": round(build_ms_device_mesh, 3), "what": "rtk_dev_scene_build, mesh resident in HBM, "
-                        "wall time inside the library (all kernels, no PCIe)", "sort_passes": passes,
-                        "algorithmic_bytes_per_triangle": round(bpt, 1), "achieved_gb_s": round(gbs, 1),
-                        "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 4), "mtris_s": round(cfg["num_tris"] / build_ms_device_mesh / 1e3, 1)}
+    if args.full:
+        # fabric traffic and limiter of the same launch from the committed rocprofv3 PMC summary (separate passes; see
+        # scripts/profile_workload.sh + scripts/summarize_profile.py). Dropped when the kernels changed since.
+        pj, traffic_src, fresh = (None, None, False) if DRY else load_pmc_summary(args.workload)
+        traffic = float(pj["hbm_traffic_bytes_per_launch"]) if (pj and fresh and args.bvh == "device") else None
+        limiter = limiter_from_pmc(pj) if (pj and fresh) else {}
+
+        k_ms = float(np.mean(kernel_ms))
+        achieved = alg_bytes / (k_ms * 1e-3) / 1e9
+        h_frac, h_note, h_fbt, h_real = honest_fractions(achieved, traffic, k_ms, limiter)
+        lane_asm = os.environ.get("RTK_AMD_LANE_ASM", "1") != "0" and lane_node_bytes == 64 and not args.static
+        beam = os.environ.get("RTK_AMD_PACKET_BEAM", "2")
+        kernel_name = ({"0": "rtk_packet_hot", "1": "rtk_packet_beam"}.get(beam, "rtk_packet_beam2") + " (hand-written gfx950 assembly) + rtk_trace_packet_kernel<false> on the tiles it hands back" if packet_kernel else
+                       ("rtk_lane_hot_%s (hand-written gfx950 assembly) + " % ("any" if shadow else "closest") if lane_asm else "") +
+                       "rtk_trace_kernel<%d, false, false, %s>%s" % (1 if shadow else 0, "true" if lane_node_bytes == 64 else "false", " on the rays it hands back" if lane_asm else ""))
+        out["config"].update({
+            "bvh_build_ms_in_library": round(info["build_ms"], 2),
+            "bvh_build_mtris_s": round(cfg["num_tris"] / max(info["build_ms"], 1e-9) / 1e3, 1) if info["build_ms"] else None,
+            "bvh_build_ms_device_resident_mesh": round(build_ms_device_mesh, 2) if build_ms_device_mesh else None,
+            "bvh_build_mtris_s_device_resident_mesh": round(cfg["num_tris"] / build_ms_device_mesh / 1e3, 1) if build_ms_device_mesh else None,
+            "hit_fraction": round(hit_frac, 4),
+            "value_without_gather_mrays_s": round(n * world * args.steps / elapsed_no_gather / 1e6, 2) if elapsed_no_gather else None,
+            "value_root_gather_mrays_s": round(n * world * args.steps / other_modes["root"] / 1e6, 2) if "root" in other_modes else None,
+            "value_striped_gather_mrays_s": round(n * world * args.steps / other_modes["striped"] / 1e6, 2) if "striped" in other_modes else None,
+            "per_rank_kernel_ms": rank_kernel,
+            "exposed_exchange_ms_per_step": ({how: round(((elapsed if how == mode else other_modes[how]) - elapsed_no_gather) / args.steps * 1e3, 4)
+                                              for how in ("striped", "root") if (how == mode or how in other_modes)}
+                                             if (world > 1 and elapsed_no_gather) else None),
+            "without_image_hint": no_hint,
+            "any_hit_on_the_same_image": any_image})
+        out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": h_frac, "traffic": traffic, "frac_by_traffic": h_fbt, "frac_note": h_note, "real_bound": h_real,
+                           "traffic_unit": ("bytes per launch of the traversal kernel crossing the L2 -> fabric boundary, Infinity-Cache (MALL) hits "
+                                            "INCLUDED: (2*FETCH_SIZE + WRITE_SIZE)*1024 from rocprofv3 PMC passes, %s; the scene is %.0f MB (the MALL "
+                                            "holds 256 MiB), so this is %s" % (traffic_src, info.get("total_device_bytes", 0) / 1e6,
+                                            "not pure HBM traffic" if info.get("total_device_bytes", 0) < 256 * 2 ** 20 else "mostly HBM traffic")) if traffic else
+                                           ("none: %s was measured on other kernel code (kernel_code_sha16 differs)" % traffic_src if pj else None),
+                           "unit_of_work": unit,
+                           "algorithmic_bytes_per_launch": int(alg_bytes),
+                           "kernel": kernel_name if not args.sort_rays else kernel_name + " preceded by the re-ordering pre-pass (rtk_ray_entry_keys_kernel, "
+                                     "3 x k_sort_hist/k_scan_block/k_sort_scatter): kernel_ms is their sum per step",
+                           "kernel_ms": round(k_ms, 4),
+                           "limiter": dict(limiter, fabric_tb_s=round(traffic / pj["kernel_trace"]["average_ns"] / 1e3, 2) if traffic else None,
+                                           note=("VALU pipes busy `valu_busy` of the traversal kernel's time at `valu_lane_utilisation` "
+                                                 "(SQ_ACTIVE_INST_VALU*4 / (1024 SIMDs * time * %.1f GHz), SQ_THREAD_CYCLES_VALU / (64 * SQ_ACTIVE_INST_VALU)); "
+                                                 "`salu_issue` = SQ_INSTS_SALU / (256 CUs * time * clock): scalar instructions per cycle of a CU's one scalar unit; "
+                                                 "`fabric_tb_s` = traffic / kernel time against ~6.3 TB/s achievable HBM and ~8.6 TB/s MALL gather rate; "
+                                                 "counters from %s" % (CLOCK_GHZ, traffic_src))) if limiter else None,
+                           "visits_per_ray": {"nodes": round(ctr["nodes"] / n, 2), "leaves": round(ctr["leaves"] / n, 2),
+                                              "triangles": round(ctr["triangles"] / n, 2)},
+                           "wave_steps_per_64_rays": {"nodes": round(ctr["wave_node_steps"] * 64.0 / n, 1),
+                                                      "triangles": round(ctr["wave_triangle_steps"] * 64.0 / n, 1),
+                                                      "of": "rtk_trace_packet_kernel<true> (C++, one tile per wave, per-lane slab tests)" if packet_kernel else "the counting build of the per-lane kernel"},
+                           "timed_kernel_steps": ({"per_pair_of_tiles": {"node_steps": round(pk_ctr["node_steps"] / max(1, pk_ctr["pairs"]), 2),
+                                                                        "triangles_fetched": round(pk_ctr["triangles_fetched"] / max(1, pk_ctr["pairs"]), 2),
+                                                                        "triangle_group_tests": round(pk_ctr["triangle_group_tests"] / max(1, pk_ctr["pairs"]), 2)},
+                                                   "pairs": pk_ctr["pairs"], "tiles_handed_back": pk_ctr["tiles_handed_back"],
+                                                   "handed_back_node_steps": pk_ctr["handed_back_node_steps"], "handed_back_triangle_steps": pk_ctr["handed_back_triangle_steps"],
+                                                   "counted_by": "rtk_packet_count2 (rtk_packet_beam2.S -DRTK_COUNT)"} if pk_ctr else None),
+                           "per_ray_model": {"bytes_per_ray": round(per_ray_bytes / n, 1), "gb_s": round(per_ray_bytes / (k_ms * 1e-3) / 1e9, 1),
+                                             "note": "every lane's visit priced at full size; caches absorb these for coherent rays, so this is "
+                                                     "cache bandwidth demand, not a fraction of the HBM roofline"},
+                           "kernel_mrays_s": round(n / (k_ms * 1e-3) / 1e6, 1)}
+        if args.bvh == "device" and build_ms_device_mesh:
+            # SURVEY.md section 8d, build formula with this build's sizes: 36 B positions in, the sort item out (< 2^24 triangles:
+            # one 8-B word = 40-bit code over the index, 5 passes; else a 12-B (key, index) pair, 8 passes), P passes x item read +
+            # written, 2 x 32 B binary node (refit write, collapse read), 128 B x wide nodes per triangle + 48 B triangle record out
+            # (key width from n: ceil(log2 n) + 8 bits in whole 8-bit passes, 3 ... 5 of them for the 8-byte words; rtk_build.hip)
+            lg = int(np.ceil(np.log2(max(2, cfg["num_tris"]))))
+            passes, item = (min(5, max(3, (lg + 8 + 7) // 8)), 8) if cfg["num_tris"] < (1 << 24) else (8, 12)
+            bpt = 36 + item + passes * 2 * item + 64 + 128.0 * info["num_nodes"] / cfg["num_tris"] + 48
+            gbs = cfg["num_tris"] * bpt / (build_ms_device_mesh * 1e-3) / 1e9
+            out["build"] = {"triangles": cfg["num_tris"], "ms": round(build_ms_device_mesh, 3), "what": "rtk_dev_scene_build, mesh resident in HBM, "
+                            "wall time inside the library (all kernels, no PCIe)", "sort_passes": passes,
+                            "algorithmic_bytes_per_triangle": round(bpt, 1), "achieved_gb_s": round(gbs, 1),
+                            "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 4), "mtris_s": round(cfg["num_tris"] / build_ms_device_mesh / 1e3, 1)}
 
     # ---- CPU baseline: the oracle (a port of rtk.c's trace path) on this host's cores -----
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # idle OpenMP workers sleep instead of spinning: the pool grows to every core for the all-cores figure, and on a box
         # whose cgroup grants fewer CPUs than it shows, spinning workers would eat the quota of the timed ones
         os.environ.setdefault("OMP_WAIT_POLICY", "PASSIVE")
@@ -893,7 +945,7 @@ def main():
         for b_ in (blob_s, probe_out, rays_s, out_s):
             b_.free()
         out["cpu_baseline"] = base
-    if world == 1 and args.workload == "coherent" and args.bvh == "device" and not args.no_other_workloads and not DRY and W == 4096:
+    if args.full and world == 1 and args.workload == "coherent" and args.bvh == "device" and not args.no_other_workloads and not DRY and W == 4096:
         # BASELINE.json configs 3 and 5 in the same run, so that their numbers are observed by whoever runs the default
         # command: compact lines, a few steps each, no CPU leg
         ds.free()

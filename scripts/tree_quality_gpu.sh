@@ -4,7 +4,7 @@
 export RTK_AMD_CPU_SAH_SPLIT_COST=0.5 RTK_AMD_CPU_LEAF_MIN=1
 for wl in coherent incoherent shadow; do
   for bvh in device cpu-sah oracle-blob; do      # oracle-blob: the CPU oracle's SAH tree as it is (leaves of ~3 triangles)
-    timeout -k 10 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --workload $wl --bvh $bvh 2>/dev/null | python3 -c "
+    timeout -k 10 900 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --workload $wl --bvh $bvh 2>/dev/null | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$wl', '$bvh', d['value'], 'Mrays/s', 'nodes', d['config']['bvh_nodes'], 'visits', r['visits_per_ray'], 'wave steps', r['wave_steps_per_64_rays'])"

@@ -182,7 +182,7 @@ def test_bench_multi_rank_plumbing_dry_run():
     import subprocess
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run-cpu", "--frame", "64"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run-cpu", "--frame", "64", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -221,3 +221,32 @@ def test_bench_refuses_a_world_size_other_than_gpus():
                         "--frame", "64"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run prints the headline line without the --full blocks, times exactly --steps steps, and --dump-outputs writes what
+    the last timed step returned: float32 / float64 arrays, at most 64 MB, the same sample of rays with the same values every run."""
+    import json
+    import subprocess
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / ("dump%d" % run))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--dry-run-cpu",
+                            "--frame", "2048", "--dump-outputs", d], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 4 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and "metric" in line
+        assert not {"roofline", "build", "cpu_baseline", "other_workloads"} & set(line)
+        names = sorted(os.listdir(d))
+        assert names == ["prim.npy", "ray_index.npy", "t.npy", "u.npy", "v.npy"]
+        arrays = {nm: np.load(os.path.join(d, nm)) for nm in names}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert len({a.shape for a in arrays.values()}) == 1
+        assert sum(os.path.getsize(os.path.join(d, nm)) for nm in names) <= 64 << 20
+        dumps.append(arrays)
+    idx = dumps[0]["ray_index.npy"]
+    assert len(idx) == 1 << 20 and (np.diff(idx) > 0).all() and idx[-1] < 2048 * 2048
+    assert all(np.array_equal(dumps[0][nm], dumps[1][nm]) for nm in dumps[0])
