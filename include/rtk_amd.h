@@ -126,6 +126,27 @@ long long rtk_dev_scene_primitive_order(const rtk_dev_scene *ds, uint32_t *out, 
 size_t rtk_dev_scene_export_size(const rtk_dev_scene *ds);
 rtk_scene *rtk_dev_scene_export(const rtk_dev_scene *ds, void *buffer, size_t size);
 
+/* New positions for the SAME triangles, in place: desc must describe the meshes the scene was made from -- the same
+ * num_meshes, the same num_triangles per mesh. Only mesh.position (data, stride, type; host or device memory, F32 or
+ * F64, as rtk_dev_scene_build accepts) is read; the triangles keep the vertex indices the scene recorded when it was
+ * built or uploaded (rtk_vertex.index), so mesh.index / index_cb are ignored. Afterwards the scene is what a build would
+ * have produced for this topology: every child box is the exact union of what is below it (also for an uploaded blob,
+ * whose boxes need not be), compressed nodes, child order words and constants are remade. Slots, primitive ids
+ * (rtk_dev_scene_primitive_order), node numbers, max_depth, stack_entries and every handle to the scene stay.
+ *   - A refit WRITES the scene. "A scene is never modified by a launch" stays true for traces; the caller must not have
+ *     a trace of this scene in flight on another stream or thread while a refit runs. Work queued earlier on `stream`
+ *     is ordered before it by the stream.
+ *   - Synchronous: the call returns after the refit has completed on `stream`; the scene may then be traced from any
+ *     stream. The first refit of a scene also makes its schedule (and, for a device-built scene, its side arrays).
+ *   - RTK_AMD_ERR_BAD_ARG: a NULL argument, a mesh count or a per-mesh triangle count that differs from the scene's, an
+ *     unknown position type, a mesh without positions. RTK_AMD_ERR_UNSUPPORTED: a mesh with position_cb set (callbacks
+ *     are out of scope for a refit). These are decided before anything is launched: the scene is untouched.
+ *   - The tree's QUALITY is the topology's: after a large deformation the scene traces correctly, but slower than a
+ *     rebuild of the new positions would. Nothing detects that; the host decides when to rebuild.
+ * rtk_dev_scene_last_refit_ms: wall time inside the last successful refit of the scene (0 if there was none). */
+int rtk_dev_scene_refit(rtk_dev_scene *ds, const rtk_scene_desc *desc, void *stream);
+double rtk_dev_scene_last_refit_ms(const rtk_dev_scene *ds);
+
 /* Structural check of a device scene, run on the device (the loader/validator the reference lacks,
  * SURVEY.md section 5; blob-level checks happen in rtk_dev_scene_upload). Every child box must contain
  * what is below it, every triangle slot must sit in exactly one leaf, every node but the root must be
@@ -251,6 +272,7 @@ int rtk_mgpu_num_devices(const rtk_mgpu *m);
 const rtk_dev_scene *rtk_mgpu_scene(const rtk_mgpu *m, int index);
 int rtk_mgpu_build(rtk_mgpu *m, const rtk_scene_desc *desc);      /* rtk_dev_scene_build on every GPU */
 int rtk_mgpu_upload(rtk_mgpu *m, const rtk_scene *scene);         /* rtk_dev_scene_upload on every GPU */
+int rtk_mgpu_refit(rtk_mgpu *m, const rtk_scene_desc *desc);      /* rtk_dev_scene_refit on every GPU of the context (handles stay valid) */
 /* host rays in, host records out (records[i] belongs to rays[i]) */
 int rtk_mgpu_trace_rays(rtk_mgpu *m, const rtk_ray *rays, size_t n, rtk_hit_record *records, const rtk_trace_opts *opts);
 /* device-resident shards: d_rays[r] / d_records[r] (counts[r] elements) live on GPU r of the context; if d_gathered

@@ -93,7 +93,8 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_trace_rays_filter", "rtk_amd_shard_range", "rtk_mgpu_create", "rtk_mgpu_destroy", "rtk_mgpu_num_devices",
                      "rtk_mgpu_scene", "rtk_mgpu_build", "rtk_mgpu_upload", "rtk_mgpu_trace_rays", "rtk_mgpu_trace_rays_device",
                      "rtk_amd_set_builder", "rtk_amd_get_builder", "rtk_amd_set_per_ray",
-                     "rtk_mgpu_trace_rays_device_striped", "rtk_mgpu_striped_segment"]
+                     "rtk_mgpu_trace_rays_device_striped", "rtk_mgpu_striped_segment",
+                     "rtk_dev_scene_refit", "rtk_dev_scene_last_refit_ms", "rtk_mgpu_refit"]
 
 _lib = None
 
@@ -158,6 +159,12 @@ def lib():
     L.rtk_mgpu_scene.argtypes = [C.c_void_p, C.c_int]
     L.rtk_mgpu_build.argtypes = [C.c_void_p, C.POINTER(SceneDesc)]
     L.rtk_mgpu_upload.argtypes = [C.c_void_p, C.c_void_p]
+    L.rtk_mgpu_refit.restype = C.c_int
+    L.rtk_mgpu_refit.argtypes = [C.c_void_p, C.POINTER(SceneDesc)]
+    L.rtk_dev_scene_refit.restype = C.c_int
+    L.rtk_dev_scene_refit.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.c_void_p]
+    L.rtk_dev_scene_last_refit_ms.restype = C.c_double
+    L.rtk_dev_scene_last_refit_ms.argtypes = [C.c_void_p]
     L.rtk_mgpu_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(TraceOpts)]
     L.rtk_mgpu_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(TraceOpts)]
     L.rtk_mgpu_trace_rays_device_striped.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TraceOpts)]
@@ -262,6 +269,16 @@ class DeviceScene:
         _torch()
         ms = meshes if isinstance(meshes, MeshSet) else MeshSet(meshes)
         return cls(lib().rtk_dev_scene_build(C.byref(ms.desc)), ms)
+
+    def refit(self, meshes):
+        """New vertex positions for the same triangles, in place (rtk_dev_scene_refit): meshes as for build(); only the
+        positions are read. Synchronous; the scene must not be traced from another stream or thread meanwhile."""
+        _torch()
+        ms = meshes if isinstance(meshes, MeshSet) else MeshSet(meshes)
+        _check(lib().rtk_dev_scene_refit(self.handle, C.byref(ms.desc), _stream_ptr()), "rtk_dev_scene_refit")
+
+    def last_refit_ms(self):
+        return float(lib().rtk_dev_scene_last_refit_ms(self.handle))
 
     def free(self):
         if self.handle:

@@ -1690,14 +1690,6 @@ void decode_mesh_on_host(const rtk_mesh *m, float *pos9, uint32_t *vidx3)
 	}
 }
 
-// Caller memory that is already device memory (hipMalloc) is read in place by the ingest kernel.
-bool is_device_ptr(const void *p)
-{
-	hipPointerAttribute_t attr;
-	if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-	return attr.type == hipMemoryTypeDevice;
-}
-
 // Host memory -> device. A plain hipMemcpy (the runtime's own pinned staging) measured faster on the
 // GPU box than a hand-rolled double-buffered copy (19 vs 25 ms per 10M-triangle build, steady state).
 // (on the build's stream: a plain hipMemcpy from pageable memory is ordered with the NULL stream only, and may return before its
@@ -1824,7 +1816,8 @@ namespace {
 // All temporaries of a build come out of ONE device allocation per device that is kept between builds
 // (grown on demand, released by rtk_amd_release_workspace): the 25 hipMalloc/hipFree pairs of the first
 // version cost more than the kernels of a 1M-triangle build. Builds on one device are serialised by the
-// mutex; the workspace is only ever touched in stream order on the null stream.
+// mutex, and so is a pass that borrows the workspace (WorkspaceLoan); whoever holds the mutex touches the memory in
+// stream order on a stream of its own (ws.stream for a build) and has waited for that stream before letting go.
 struct Workspace {
 	std::mutex mutex;
 	char *base = nullptr;
@@ -1848,8 +1841,6 @@ struct Arena {
 		return off <= cap ? p : nullptr;
 	}
 };
-
-size_t padded(size_t bytes) { return ((bytes ? bytes : 1) + 255u) & ~(size_t)255u; }
 
 // How one mesh reaches the ingest kernel.
 struct MeshPlan {
@@ -1894,6 +1885,48 @@ extern "C" void rtk_amd_release_workspace(void)
 		w.base = nullptr;
 		w.cap = 0;
 	}
+}
+
+// Caller memory that is already device memory (hipMalloc) is read in place (the ingest kernel, a refit's gather).
+bool rtk_is_device_ptr(const void *p)
+{
+	hipPointerAttribute_t attr;
+	if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+	return attr.type == hipMemoryTypeDevice;
+}
+
+// WorkspaceLoan (rtk_dev.h): the workspace of a device, grown to `bytes` if need be, under its mutex
+bool WorkspaceLoan::take(int dev, size_t bytes)
+{
+	if (device >= 0) { rtk_set_error("workspace: already borrowed"); return false; }
+	if (dev < 0 || dev >= RTK_MAX_DEVICES) { rtk_set_error("workspace: device %d out of range", dev); return false; }
+	Workspace &w = g_workspace[dev];
+	w.mutex.lock();
+	if (w.cap < bytes || !w.base) {
+		if (w.base) (void)hipFree(w.base);
+		w.base = nullptr;
+		w.cap = 0;
+		const size_t want = bytes ? bytes : 256;
+		if (hipMalloc(&w.base, want) != hipSuccess) {
+			(void)hipGetLastError();
+			w.base = nullptr;
+			w.mutex.unlock();
+			rtk_set_error("workspace: out of device memory (%zu bytes)", want);
+			return false;
+		}
+		w.cap = want;
+	}
+	device = dev;
+	base = w.base;
+	return true;
+}
+
+void WorkspaceLoan::release()
+{
+	if (device < 0) return;
+	g_workspace[device].mutex.unlock();
+	device = -1;
+	base = nullptr;
 }
 
 // force_bits: 0 = key width from the number of triangles; else the width of the Morton code in the packed sort words.
@@ -1944,7 +1977,7 @@ static rtk_dev_scene *build_impl(const rtk_scene_desc *desc, uint32_t force_bits
 		pl.f64 = m->position.type == RTK_TYPE_F64;
 		pl.pstride = m->position.stride ? m->position.stride : (pl.f64 ? 24 : 12);
 		pl.pos_src = (const char *)m->position.data;
-		pl.pos_on_device = is_device_ptr(m->position.data);
+		pl.pos_on_device = rtk_is_device_ptr(m->position.data);
 		uint64_t max_vertex = 3ull * nt - 1;
 		if (m->index.data) {
 			const bool u16 = m->index.type == RTK_TYPE_U16;
@@ -1953,7 +1986,7 @@ static rtk_dev_scene *build_impl(const rtk_scene_desc *desc, uint32_t force_bits
 			pl.idx_kind = u16 ? 1 : 2;
 			pl.istride = m->index.stride ? m->index.stride : (u16 ? 6 : 12);
 			pl.idx_src = (const char *)m->index.data;
-			pl.idx_on_device = is_device_ptr(m->index.data);
+			pl.idx_on_device = rtk_is_device_ptr(m->index.data);
 			if (pl.idx_on_device && !pl.pos_on_device) { rtk_set_error("rtk_dev_scene_build: mesh %zu has device indices but host positions", mi); return nullptr; }
 			if (!pl.idx_on_device) {
 				if (!pl.pos_on_device) {
@@ -1971,7 +2004,7 @@ static rtk_dev_scene *build_impl(const rtk_scene_desc *desc, uint32_t force_bits
 			}
 		}
 		if (!pl.pos_on_device) pl.pbytes = (size_t)max_vertex * pl.pstride + (pl.f64 ? 24 : 12);
-		upload_bytes += padded(pl.pbytes) + padded(pl.ibytes);
+		upload_bytes += rtk_padded(pl.pbytes) + rtk_padded(pl.ibytes);
 	}
 
 	if (n < 2) {
@@ -1996,14 +2029,14 @@ static rtk_dev_scene *build_impl(const rtk_scene_desc *desc, uint32_t force_bits
 	const size_t sort_words = rtk_sort_scratch_words(n);
 	const size_t collapse_blocks = ((size_t)n + COLLAPSE_BLOCK - 1) / COLLAPSE_BLOCK;
 	size_t need = upload_bytes + 64 * 256;
-	need += padded((size_t)n * sizeof(InTri)) + padded((size_t)n * 12) + padded((desc->num_meshes + 1) * sizeof(MeshSrc));   // staged triangles, doubled centroids, where each mesh is gathered from
-	need += 2 * padded((size_t)n * 8) + 2 * padded((size_t)n * 4);                  // keys a/b, vals a/b
-	need += padded(sort_words * 4) + padded(64) + padded(mesh_base.size() * 8);     // sort scratch, bounds, mesh_base
-	need += 2 * padded((size_t)n * 8) + padded((size_t)n * 12) + padded((size_t)n * 16) + padded((size_t)n * 4) + padded(16);   // lr, range, climbers, halves, arrive, root
-	need += padded((size_t)n * sizeof(BinNode));                                    // bin
-	need += padded((size_t)n * 16) + 2 * padded((size_t)n * 4) + padded(collapse_blocks * 4) + padded(sizeof(LevelState) * COLLAPSE_RING);   // collapse: dec, info, jobs, block sums, ring
-	need += padded((size_t)n * sizeof(DevNode));                                    // nodes (worst case; unused in tile mode)
-	need += 4 * padded(((size_t)n / REFIT_TILE + 4) * 4) + padded(16) + padded((size_t)n * 4);   // tile counts, tile bases, climbers and roots per tile, depth word, areas
+	need += rtk_padded((size_t)n * sizeof(InTri)) + rtk_padded((size_t)n * 12) + rtk_padded((desc->num_meshes + 1) * sizeof(MeshSrc));   // staged triangles, doubled centroids, where each mesh is gathered from
+	need += 2 * rtk_padded((size_t)n * 8) + 2 * rtk_padded((size_t)n * 4);                  // keys a/b, vals a/b
+	need += rtk_padded(sort_words * 4) + rtk_padded(64) + rtk_padded(mesh_base.size() * 8);     // sort scratch, bounds, mesh_base
+	need += 2 * rtk_padded((size_t)n * 8) + rtk_padded((size_t)n * 12) + rtk_padded((size_t)n * 16) + rtk_padded((size_t)n * 4) + rtk_padded(16);   // lr, range, climbers, halves, arrive, root
+	need += rtk_padded((size_t)n * sizeof(BinNode));                                    // bin
+	need += rtk_padded((size_t)n * 16) + 2 * rtk_padded((size_t)n * 4) + rtk_padded(collapse_blocks * 4) + rtk_padded(sizeof(LevelState) * COLLAPSE_RING);   // collapse: dec, info, jobs, block sums, ring
+	need += rtk_padded((size_t)n * sizeof(DevNode));                                    // nodes (worst case; unused in tile mode)
+	need += 4 * rtk_padded(((size_t)n / REFIT_TILE + 4) * 4) + rtk_padded(16) + rtk_padded((size_t)n * 4);   // tile counts, tile bases, climbers and roots per tile, depth word, areas
 	Workspace &ws = g_workspace[device];
 	std::lock_guard<std::mutex> ws_lock(ws.mutex);
 	if (ws.cap < need) {
@@ -2181,7 +2214,7 @@ static rtk_dev_scene *build_impl(const rtk_scene_desc *desc, uint32_t force_bits
 		return (char *)p;
 	};
 	// the triangle records; the mesh table (a few words the scene keeps: rtk_scene_side_arrays reads it)
-	const size_t o_mb = padded((size_t)n * sizeof(DevTri)), tri_block = o_mb + padded(mb.size() * 8);
+	const size_t o_mb = rtk_padded((size_t)n * sizeof(DevTri)), tri_block = o_mb + rtk_padded(mb.size() * 8);
 	char *tri_mem = dev_alloc(tri_block);
 	if (!tri_mem) return fail("out of device memory");
 	DevTri *d_tris = (DevTri *)tri_mem;
@@ -2237,7 +2270,7 @@ static rtk_dev_scene *build_impl(const rtk_scene_desc *desc, uint32_t force_bits
 	const uint32_t top_cap = getenv("RTK_AMD_TOP_CAP") ? std::min<uint32_t>(n / 2u, (uint32_t)atoi(getenv("RTK_AMD_TOP_CAP"))) : n / 2u;
 	uint4 *d_top_refs = reinterpret_cast<uint4 *>(d_nodes_tmp + top_cap);
 	uint32_t *d_top_level = reinterpret_cast<uint32_t *>(d_top_refs + top_cap);
-	unsigned long long *d_root_info = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(d_nodes_tmp) + padded((size_t)top_cap * (sizeof(DevNode) + 16u + 4u)));
+	unsigned long long *d_root_info = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(d_nodes_tmp) + rtk_padded((size_t)top_cap * (sizeof(DevNode) + 16u + 4u)));
 	int *d_root_list = reinterpret_cast<int *>(d_root_info + n);
 	static_assert(sizeof(DevNode) == 128, "the carving above: n / 2 * 148 + 8 n + 4 n + padding <= 128 n");
 	uint32_t *d_tile_nroots = ar.take<uint32_t>(num_tiles + 1u);
@@ -2478,7 +2511,7 @@ int rtk_scene_side_arrays(const rtk_dev_scene *ds_c, hipStream_t stream)
 	std::lock_guard<std::mutex> lock(ds->side_mutex);
 	if (ds->side_ready) return RTK_AMD_OK;
 	const size_t n = ds->view.num_tris, np = ds->view.num_prims;
-	const size_t o_pslot = padded(3 * n * 4), o_smesh = o_pslot + padded(np * 4), o_stri = o_smesh + padded(n * 4), total = o_stri + padded(n * 4);
+	const size_t o_pslot = rtk_padded(3 * n * 4), o_smesh = o_pslot + rtk_padded(np * 4), o_stri = o_smesh + rtk_padded(n * 4), total = o_stri + rtk_padded(n * 4);
 	void *mem = nullptr;
 	RTK_HIP_CHECK(hipMalloc(&mem, total), RTK_AMD_ERR_OOM);
 	char *base = (char *)mem;

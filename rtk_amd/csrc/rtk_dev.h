@@ -118,6 +118,19 @@ struct LaunchScratch {
 	size_t leftover_capacity = 0;               // tiles
 };
 
+// What a refit needs besides the scene (rtk_refit.hip): the node numbers grouped by HEIGHT (0: every child is a leaf or
+// empty; else 1 + the largest height among the inner children), so that one launch per height finds its children's boxes
+// written by an earlier launch. The device arrays are owned through rtk_dev_scene::allocs.
+struct RefitSchedule {
+	bool ready = false;
+	uint32_t *d_order = nullptr;               // [num_nodes] node numbers, by height, by number inside a height
+	uint32_t *d_level_start = nullptr;         // [heights + 1] where each height begins in d_order
+	std::vector<uint32_t> level_start;         // the same on the host
+	void *d_meshes = nullptr;                  // [num_meshes] where each mesh's positions are read from (filled per refit)
+	bool max_vertex_ready = false;
+	std::vector<uint32_t> max_vertex;          // [num_meshes] largest vertex index the mesh's triangles use (made when a mesh first arrives in host memory)
+};
+
 struct rtk_dev_scene {
 	int device = 0;
 	DevSceneView view = {};
@@ -145,6 +158,12 @@ struct rtk_dev_scene {
 	bool side_ready = true;                    // (uploads arrive with the arrays)
 	const uint32_t *d_vidx_in = nullptr;       // [3 * prim + k] original vertex indices in input order; NULL: every mesh has implicit indices
 	const unsigned long long *d_mesh_base = nullptr;   // num_meshes + 1, on the device
+	// Refits (rtk_refit.hip). The schedule is made by the first one and kept, like the side arrays; none of it is in the view
+	// the traversals copy.
+	const DevNodeQ *qnodes_mem = nullptr;      // the compressed array, also while view.qnodes is NULL (a misfit): the next refit fills it again
+	std::mutex refit_mutex;                    // one refit of a scene at a time; covers the schedule
+	RefitSchedule refit;
+	double refit_ms = 0.0;                     // wall time inside the last rtk_dev_scene_refit
 };
 // makes the side arrays if they are not there yet (synchronises `stream` the one time it has to work)
 int rtk_scene_side_arrays(const rtk_dev_scene *ds, hipStream_t stream);
@@ -183,6 +202,24 @@ int rtk_quantize_nodes(rtk_dev_scene *ds, hipStream_t stream, const DevNode *src
 	uint32_t only_first = 0xffffffffu, bool keep_consts = false, bool readback = true);   // (bound_hint: 0 = none; the floor of 1 is applied inside; readback: enqueue the copy of the constants to the host -- the device build brings them home with its other results)
 int rtk_scene_consts(rtk_dev_scene *ds, hipStream_t stream);
 void rtk_quantize_finish(rtk_dev_scene *ds);   // after that stream has been synchronised
+
+// -- the build workspace lent to another pass, helpers shared with the build (rtk_build.hip) --
+// The workspace of a device, at least `bytes` large, lent to a pass that is not a build (rtk_refit.hip: the temporaries of the
+// schedule, host-resident positions staged as a build stages them). Builds on the device wait while it is out; whatever the
+// borrower enqueued on the memory must have completed before release() (the destructor).
+struct WorkspaceLoan {
+	int device = -1;
+	char *base = nullptr;
+	WorkspaceLoan() = default;
+	WorkspaceLoan(const WorkspaceLoan &) = delete;
+	WorkspaceLoan &operator=(const WorkspaceLoan &) = delete;
+	~WorkspaceLoan() { release(); }
+	bool take(int device, size_t bytes);       // false: nothing is held (out of device memory; rtk_set_error says so)
+	void release();
+};
+bool rtk_is_device_ptr(const void *p);         // hipMalloc'ed memory?
+static inline size_t rtk_padded(size_t bytes) { return ((bytes ? bytes : 1) + 255u) & ~(size_t)255u; }   // sizes inside one allocation: 256-byte steps
+void rtk_export_forget(const rtk_dev_scene *ds);   // the scene's cached export plan, if any (rtk_build.hip)
 
 // -- radix sort shared with the builder (rtk_build.hip) --
 size_t rtk_sort_scratch_words(uint32_t n);

@@ -71,5 +71,6 @@ void rtk_quantize_finish(rtk_dev_scene *ds)
 {
 	ds->bound_abs = ds->consts_readback.bound_abs;
 	ds->bound_raw = ds->consts_readback.bound_raw;
+	if (ds->view.qnodes) ds->qnodes_mem = ds->view.qnodes;   // (a refit fills the array again and decides anew)
 	if (ds->consts_readback.qnode_misfits != 0u) ds->view.qnodes = nullptr;
 }
