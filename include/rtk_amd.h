@@ -147,6 +147,31 @@ rtk_scene *rtk_dev_scene_export(const rtk_dev_scene *ds, void *buffer, size_t si
 int rtk_dev_scene_refit(rtk_dev_scene *ds, const rtk_scene_desc *desc, void *stream);
 double rtk_dev_scene_last_refit_ms(const rtk_dev_scene *ds);
 
+/* The same for SOME meshes, at a cost that follows what moved. desc describes the scene as for rtk_dev_scene_refit (same
+ * num_meshes, same num_triangles per mesh: both checked for every mesh), but only the meshes listed in mesh_ids are READ:
+ * a mesh that is not listed may have position.data == NULL, a callback, anything; its triangles keep the positions they
+ * have. Listed meshes obey the rules above (F32 / F64 / REAL / DEFAULT, stride, host or device memory; position_cb ->
+ * RTK_AMD_ERR_UNSUPPORTED; no positions -> RTK_AMD_ERR_BAD_ARG). mesh_ids is host memory; an id may repeat (counted
+ * once); a listed mesh may have zero triangles.
+ *   - The result is BIT-IDENTICAL to the full refit: every node word, triangle record, compressed node, order word and
+ *     constant, and the choice between exact and compressed nodes, are what rtk_dev_scene_refit would have left, had it
+ *     been given the listed meshes' new positions and, for every other mesh, the positions the scene holds now.
+ *     Everything said above holds word for word: slots, ids, node numbers, depth and handles stay; the scene is WRITTEN,
+ *     so no trace of it may be in flight; synchronous; work queued earlier on `stream` is ordered before it.
+ *   - Work: the listed meshes' triangles, and the nodes above their leaves (boxes, compressed node, order words). The
+ *     first such call of a scene makes its tables (12 B per node, 8 B per triangle, counted in total_device_bytes). Two
+ *     cases run the full box and finish passes instead, with the same result: the listed meshes hold more than a
+ *     quarter of the scene's triangles (the full passes are cheaper then), or the scene is an uploaded blob that has not
+ *     had a refit yet (its boxes need not be exact unions, and the ones left alone would stay loose).
+ *   - num_ids == 0, or no triangle in the listed meshes: success, no bit changes, nothing is launched.
+ *   - RTK_AMD_ERR_BAD_ARG also for an id >= num_meshes and for mesh_ids == NULL with num_ids != 0. As above every
+ *     refusal is decided before anything is launched and leaves the scene alone.
+ * rtk_dev_scene_last_refit_nodes: how many nodes the last successful refit of the scene (either call) remade the boxes
+ * of: num_nodes after a full refit, 0 if there was none or it had nothing to do. rtk_dev_scene_last_refit_ms covers both
+ * calls (0 after a call that had nothing to do). */
+int rtk_dev_scene_refit_meshes(rtk_dev_scene *ds, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids, void *stream);
+uint64_t rtk_dev_scene_last_refit_nodes(const rtk_dev_scene *ds);
+
 /* Structural check of a device scene, run on the device (the loader/validator the reference lacks,
  * SURVEY.md section 5; blob-level checks happen in rtk_dev_scene_upload). Every child box must contain
  * what is below it, every triangle slot must sit in exactly one leaf, every node but the root must be
@@ -273,6 +298,7 @@ const rtk_dev_scene *rtk_mgpu_scene(const rtk_mgpu *m, int index);
 int rtk_mgpu_build(rtk_mgpu *m, const rtk_scene_desc *desc);      /* rtk_dev_scene_build on every GPU */
 int rtk_mgpu_upload(rtk_mgpu *m, const rtk_scene *scene);         /* rtk_dev_scene_upload on every GPU */
 int rtk_mgpu_refit(rtk_mgpu *m, const rtk_scene_desc *desc);      /* rtk_dev_scene_refit on every GPU of the context (handles stay valid) */
+int rtk_mgpu_refit_meshes(rtk_mgpu *m, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids);   /* rtk_dev_scene_refit_meshes on every GPU */
 /* host rays in, host records out (records[i] belongs to rays[i]) */
 int rtk_mgpu_trace_rays(rtk_mgpu *m, const rtk_ray *rays, size_t n, rtk_hit_record *records, const rtk_trace_opts *opts);
 /* device-resident shards: d_rays[r] / d_records[r] (counts[r] elements) live on GPU r of the context; if d_gathered

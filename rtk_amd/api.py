@@ -94,7 +94,8 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_mgpu_scene", "rtk_mgpu_build", "rtk_mgpu_upload", "rtk_mgpu_trace_rays", "rtk_mgpu_trace_rays_device",
                      "rtk_amd_set_builder", "rtk_amd_get_builder", "rtk_amd_set_per_ray",
                      "rtk_mgpu_trace_rays_device_striped", "rtk_mgpu_striped_segment",
-                     "rtk_dev_scene_refit", "rtk_dev_scene_last_refit_ms", "rtk_mgpu_refit"]
+                     "rtk_dev_scene_refit", "rtk_dev_scene_last_refit_ms", "rtk_mgpu_refit",
+                     "rtk_dev_scene_refit_meshes", "rtk_dev_scene_last_refit_nodes", "rtk_mgpu_refit_meshes"]
 
 _lib = None
 
@@ -165,6 +166,12 @@ def lib():
     L.rtk_dev_scene_refit.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.c_void_p]
     L.rtk_dev_scene_last_refit_ms.restype = C.c_double
     L.rtk_dev_scene_last_refit_ms.argtypes = [C.c_void_p]
+    L.rtk_dev_scene_refit_meshes.restype = C.c_int
+    L.rtk_dev_scene_refit_meshes.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_size_t, C.c_void_p]
+    L.rtk_dev_scene_last_refit_nodes.restype = C.c_uint64
+    L.rtk_dev_scene_last_refit_nodes.argtypes = [C.c_void_p]
+    L.rtk_mgpu_refit_meshes.restype = C.c_int
+    L.rtk_mgpu_refit_meshes.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_size_t]
     L.rtk_mgpu_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(TraceOpts)]
     L.rtk_mgpu_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(TraceOpts)]
     L.rtk_mgpu_trace_rays_device_striped.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TraceOpts)]
@@ -244,6 +251,19 @@ def make_opts(image=None, static=False, refill_min=0, blocks_per_cu=0, node_exit
     return o
 
 
+def mesh_set_of_some(meshes, mesh_base):
+    """A MeshSet in which the entries of `meshes` that are None describe their mesh by its triangle count alone
+    (mesh_base: the scene's prefix sums) and have no positions: what rtk_dev_scene_refit_meshes takes for meshes it is
+    not asked to move."""
+    empty = np.zeros((0, 3), np.float32)
+    ms = MeshSet([m if m is not None else dict(positions=empty) for m in meshes])
+    for i, m in enumerate(meshes):
+        if m is None and i + 1 < len(mesh_base):
+            ms._arr[i].num_triangles = int(mesh_base[i + 1] - mesh_base[i])
+            ms._arr[i].position.data = None
+    return ms
+
+
 class DeviceScene:
     """A device-resident scene (rtk_dev_scene*)."""
 
@@ -270,15 +290,27 @@ class DeviceScene:
         ms = meshes if isinstance(meshes, MeshSet) else MeshSet(meshes)
         return cls(lib().rtk_dev_scene_build(C.byref(ms.desc)), ms)
 
-    def refit(self, meshes):
+    def refit(self, meshes, only=None):
         """New vertex positions for the same triangles, in place (rtk_dev_scene_refit): meshes as for build(); only the
-        positions are read. Synchronous; the scene must not be traced from another stream or thread meanwhile."""
+        positions are read. Synchronous; the scene must not be traced from another stream or thread meanwhile.
+        only: a list of mesh indices (rtk_dev_scene_refit_meshes) -- just those meshes are read and moved, at a cost that
+        follows them; the entries of `meshes` that are not listed may be None."""
         _torch()
-        ms = meshes if isinstance(meshes, MeshSet) else MeshSet(meshes)
-        _check(lib().rtk_dev_scene_refit(self.handle, C.byref(ms.desc), _stream_ptr()), "rtk_dev_scene_refit")
+        if only is None:
+            ms = meshes if isinstance(meshes, MeshSet) else MeshSet(meshes)
+            _check(lib().rtk_dev_scene_refit(self.handle, C.byref(ms.desc), _stream_ptr()), "rtk_dev_scene_refit")
+            return
+        ms = meshes if isinstance(meshes, MeshSet) else mesh_set_of_some(meshes, self.mesh_base())
+        ids = np.ascontiguousarray(only, np.uint32).reshape(-1)
+        _check(lib().rtk_dev_scene_refit_meshes(self.handle, C.byref(ms.desc), ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids.size else None,
+                                                ids.size, _stream_ptr()), "rtk_dev_scene_refit_meshes")
 
     def last_refit_ms(self):
         return float(lib().rtk_dev_scene_last_refit_ms(self.handle))
+
+    def last_refit_nodes(self):
+        """Nodes whose boxes the last successful refit remade (rtk_dev_scene_last_refit_nodes)."""
+        return int(lib().rtk_dev_scene_last_refit_nodes(self.handle))
 
     def free(self):
         if self.handle:

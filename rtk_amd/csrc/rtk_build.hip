@@ -2493,11 +2493,12 @@ extern "C" rtk_dev_scene *rtk_dev_scene_build(const rtk_scene_desc *desc)
 {
 	bool narrow = false;
 	rtk_dev_scene *ds = build_impl(desc, 0u, &narrow);
+	if (ds) ds->boxes_exact = true;            // (every box the union of what is below it: what a refit of some meshes relies on)
 	if (!ds || !narrow || (getenv("RTK_AMD_KEY_REBUILD") && atoi(getenv("RTK_AMD_KEY_REBUILD")) == 0)) return ds;
 	const double first_ms = ds->build_ms;
 	rtk_dev_scene_free(ds);
 	ds = build_impl(desc, 40u, &narrow);
-	if (ds) ds->build_ms += first_ms;
+	if (ds) { ds->build_ms += first_ms; ds->boxes_exact = true; }
 	return ds;
 }
 

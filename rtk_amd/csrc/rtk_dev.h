@@ -131,6 +131,23 @@ struct RefitSchedule {
 	std::vector<uint32_t> max_vertex;          // [num_meshes] largest vertex index the mesh's triangles use (made when a mesh first arrives in host memory)
 };
 
+// What a refit of SOME meshes needs on top of the schedule (rtk_dev_scene_refit_meshes): who is above a node, which node holds
+// a slot's leaf, every mesh's slots, and the memory of the per-call dirty set. Made by the first such call of a scene, owned
+// through rtk_dev_scene::allocs; 12 B per node and 8 B per triangle.
+#define RTK_DIRTY_BLOCK 1024u                  // entries of d_order one workgroup of the compaction counts and scatters
+struct RefitPartial {
+	bool ready = false;
+	uint32_t *d_parent = nullptr;              // [num_nodes] the node whose child word names this one (RTK_REF_NONE: the root)
+	uint32_t *d_slot_node = nullptr;           // [num_tris] the node whose child word is the leaf that holds the slot
+	uint32_t *d_mesh_slots = nullptr;          // [num_tris] slot numbers grouped by mesh, ascending inside one; mesh m's begin at mesh_base[m]
+	uint32_t *d_dirty = nullptr;               // [num_nodes] == epoch: boxes of this node are remade by the running call
+	uint32_t *d_list = nullptr;                // [num_nodes] the dirty nodes in the order of d_order
+	uint32_t *d_block = nullptr;               // [blocks + 1] dirty entries per RTK_DIRTY_BLOCK entries of d_order, then their running sums; [blocks] = all
+	uint32_t *d_list_start = nullptr;          // [heights + 1] where each height begins in d_list
+	void *d_ranges = nullptr;                  // [num_meshes + 1] runs of listed meshes in d_mesh_slots (filled per call)
+	uint32_t epoch = 0;                        // of the last call (0: none yet; d_dirty starts cleared)
+};
+
 struct rtk_dev_scene {
 	int device = 0;
 	DevSceneView view = {};
@@ -163,7 +180,11 @@ struct rtk_dev_scene {
 	const DevNodeQ *qnodes_mem = nullptr;      // the compressed array, also while view.qnodes is NULL (a misfit): the next refit fills it again
 	std::mutex refit_mutex;                    // one refit of a scene at a time; covers the schedule
 	RefitSchedule refit;
-	double refit_ms = 0.0;                     // wall time inside the last rtk_dev_scene_refit
+	double refit_ms = 0.0;                     // wall time inside the last rtk_dev_scene_refit / rtk_dev_scene_refit_meshes
+	RefitPartial partial;
+	bool boxes_exact = false;                  // every box is known to be the exact union of what is below it (a device build, a full refit; not an upload)
+	uint64_t refit_nodes = 0;                  // nodes whose boxes the last successful refit remade
+	uint32_t partial_readback = 0;             // the dirty count of a partial refit, brought home with the constants
 };
 // makes the side arrays if they are not there yet (synchronises `stream` the one time it has to work)
 int rtk_scene_side_arrays(const rtk_dev_scene *ds, hipStream_t stream);
@@ -201,6 +222,10 @@ rtk_dev_scene *rtk_dev_scene_from_host_bvh(const HostBvh &h);
 int rtk_quantize_nodes(rtk_dev_scene *ds, hipStream_t stream, const DevNode *src = nullptr, DevNodeQ *dst = nullptr, float bound_hint = 0.0f,
 	uint32_t only_first = 0xffffffffu, bool keep_consts = false, bool readback = true);   // (bound_hint: 0 = none; the floor of 1 is applied inside; readback: enqueue the copy of the constants to the host -- the device build brings them home with its other results)
 int rtk_scene_consts(rtk_dev_scene *ds, hipStream_t stream);
+// The same finish for the nodes list[0 .. *d_count) only (a refit of some meshes): compressed node and order words of each, the
+// constants' bounds if the root is among them, misfits among them counted. The constants block is cleared first; the copy of
+// the constants to the host is enqueued. The compressed array is ds->qnodes_mem.
+int rtk_quantize_node_list(rtk_dev_scene *ds, hipStream_t stream, const uint32_t *list, const uint32_t *d_count);
 void rtk_quantize_finish(rtk_dev_scene *ds);   // after that stream has been synchronised
 
 // -- the build workspace lent to another pass, helpers shared with the build (rtk_build.hip) --

@@ -179,6 +179,18 @@ extern "C" int rtk_mgpu_refit(rtk_mgpu *m, const rtk_scene_desc *desc)
 	});
 }
 
+// the same for some meshes (rtk_dev_scene_refit_meshes)
+extern "C" int rtk_mgpu_refit_meshes(rtk_mgpu *m, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids)
+{
+	if (!m || !desc) { rtk_set_error("rtk_mgpu_refit_meshes: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
+	if (!mesh_ids && num_ids) { rtk_set_error("rtk_mgpu_refit_meshes: NULL mesh_ids with %zu ids", num_ids); return RTK_AMD_ERR_BAD_ARG; }
+	for (const DeviceSlot &s : m->slots) if (!s.scene) { rtk_set_error("rtk_mgpu_refit_meshes: the context holds no scene"); return RTK_AMD_ERR_BAD_ARG; }
+	return for_each_slot_in_parallel(m, [&](size_t j) -> int {
+		DeviceSlot &s = m->slots[j];
+		return rtk_dev_scene_refit_meshes(s.scene, desc, mesh_ids, num_ids, s.trace_stream);
+	});
+}
+
 // Where stripe `stripe` of shard `shard` lies: records [*first, *first + *count) of the buffer of GPU `stripe` (stripes of a
 // shard follow rtk_amd_shard_range(counts[shard], stripe, R); a GPU's buffer holds its stripe of shard 0, then of shard 1, ...).
 extern "C" void rtk_mgpu_striped_segment(const size_t *counts, int num_shards, int shard, int stripe, size_t *first, size_t *count)

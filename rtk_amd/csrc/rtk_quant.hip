@@ -29,6 +29,30 @@ __global__ void k_quantize(DevNode *nodes, uint32_t n, DevNodeQ *out, DevNode *c
 	if (misfit) atomicAdd(&consts->qnode_misfits, 1u);
 }
 
+// The list form (a refit of some meshes): the nodes list[0 .. *count) only, grid-stride (the count is on the device). What is
+// stored for a node is what k_quantize stores for it: both depend on the node's own child boxes and child words alone.
+__global__ void __launch_bounds__(256) k_quantize_list(DevNode *nodes, uint32_t n, const uint32_t *list, const uint32_t *count, DevNodeQ *out, DevSceneConsts *consts)
+{
+	uint32_t total = *count;
+	if (total > n) total = n;
+	for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+		const uint32_t i = list[e];
+		if (i >= n) continue;
+		DevNode nd = nodes[i];
+		child_order(nd, nd.order);
+		*reinterpret_cast<uint4 *>(nodes[i].order) = make_uint4(nd.order[0], nd.order[1], nd.order[2], nd.order[3]);
+		if (i == 0u) {
+			const float b = root_bound(nd, 0.0f);
+			consts->bound_raw = b;
+			consts->bound_abs = fmaxf(b, 1.0f);
+		}
+		DevNodeQ q;
+		const bool misfit = !quantize_node(nd, q);
+		out[i] = q;
+		if (misfit) atomicAdd(&consts->qnode_misfits, 1u);
+	}
+}
+
 } // namespace
 
 // The scene's constants word block, allocated on first use and cleared on `stream`.
@@ -62,6 +86,23 @@ int rtk_quantize_nodes(rtk_dev_scene *ds, hipStream_t stream, const DevNode *src
 	ds->view.qnodes = (const DevNodeQ *)p;
 	// the misfit count comes back with the caller's own synchronisation of `stream` (rtk_quantize_finish)
 	if (readback) RTK_HIP_CHECK(hipMemcpyAsync(&ds->consts_readback, consts, sizeof(DevSceneConsts), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
+	return RTK_AMD_OK;
+}
+
+int rtk_quantize_node_list(rtk_dev_scene *ds, hipStream_t stream, const uint32_t *list, const uint32_t *d_count)
+{
+	const uint32_t n = ds->view.num_nodes;
+	if (!ds->qnodes_mem || !ds->view.consts) { rtk_set_error("rtk_quantize_node_list: the scene has no compressed nodes"); return RTK_AMD_ERR_BAD_SCENE; }
+	const int rc = rtk_scene_consts(ds, stream);
+	if (rc != RTK_AMD_OK) return rc;
+	DevSceneConsts *consts = const_cast<DevSceneConsts *>(ds->view.consts);
+	unsigned blocks = (n + 255u) / 256u;
+	if (blocks > 2048u) blocks = 2048u;
+	if (n) hipLaunchKernelGGL(k_quantize_list, dim3(blocks), dim3(256), 0, stream, const_cast<DevNode *>(ds->view.nodes), n, list, d_count,
+		const_cast<DevNodeQ *>(ds->qnodes_mem), consts);
+	RTK_HIP_CHECK(hipGetLastError(), RTK_AMD_ERR_HIP);
+	ds->view.qnodes = ds->qnodes_mem;
+	RTK_HIP_CHECK(hipMemcpyAsync(&ds->consts_readback, consts, sizeof(DevSceneConsts), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
 	return RTK_AMD_OK;
 }
 

@@ -12,11 +12,17 @@
 //                   agent-scope release and acquire per hand-off);
 //   k_quantize      (rtk_quant.hip) the 64-byte compressed nodes, the child order words and the scene constants.
 // The heights and the node numbers grouped by them (RefitSchedule) are made by the first refit of a scene and kept.
+// rtk_dev_scene_refit_meshes does the same for SOME meshes, with work in proportion to them: only their slots are regathered
+// (k_refit_tris_listed, through per-mesh slot lists), every node above one of their leaves is marked dirty by climbing
+// parent[] with plain idempotent stores, the schedule's node list is compacted by that flag with its order kept
+// (k_dirty_count / k_dirty_scan / k_dirty_scatter), and boxes, compressed nodes and order words are remade for the dirty nodes
+// alone, height by height as above. The result is bit for bit the full refit's; DESIGN.md 3.4a has the reasoning.
 // A box is made by the validator's rule (rtk_validate.hip: fminf / fmaxf over the vertices of a leaf, over the non-empty
 // slots of an inner child), so after a refit every box is the exact union of what is below it.
 #include "rtk_dev.h"
 
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <chrono>
@@ -99,14 +105,8 @@ __global__ void k_refit_max_vertex(const uint32_t *vertex_index, const uint32_t 
 // MODE 0: every mesh has float positions, 1: every mesh doubles, 2: per mesh (RefitMesh::f64, a flag the host derived from
 // validated type codes). Doubles are converted as k_ingest converts them.
 template <int MODE>
-__global__ void __launch_bounds__(256) k_refit_tris(DevTri *tris, uint32_t n, const uint32_t *vertex_index, const uint32_t *slot_mesh,
-	const RefitMesh *meshes, uint32_t num_meshes)
+__device__ __forceinline__ void refit_tri(DevTri *tris, uint32_t s, const uint32_t *vertex_index, const RefitMesh &ms)
 {
-	const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-	if (s >= n) return;
-	const uint32_t mesh = slot_mesh[s];
-	if (mesh >= num_meshes) return;
-	const RefitMesh ms = meshes[mesh];
 	const uint32_t vi[3] = { vertex_index[3 * (size_t)s], vertex_index[3 * (size_t)s + 1], vertex_index[3 * (size_t)s + 2] };
 	float p[3][3];
 	const bool f64 = MODE == 1 || (MODE == 2 && ms.f64 != 0u);
@@ -127,6 +127,179 @@ __global__ void __launch_bounds__(256) k_refit_tris(DevTri *tris, uint32_t n, co
 	r1.x = p[1][0]; r1.y = p[1][1]; r1.z = p[1][2];
 	r2.x = p[2][0]; r2.y = p[2][1]; r2.z = p[2][2];
 	rec[0] = r0; rec[1] = r1; rec[2] = r2;
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) k_refit_tris(DevTri *tris, uint32_t n, const uint32_t *vertex_index, const uint32_t *slot_mesh,
+	const RefitMesh *meshes, uint32_t num_meshes)
+{
+	const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+	if (s >= n) return;
+	const uint32_t mesh = slot_mesh[s];
+	if (mesh >= num_meshes) return;
+	const RefitMesh ms = meshes[mesh];
+	refit_tri<MODE>(tris, s, vertex_index, ms);
+}
+
+// A run of listed meshes that are neighbours in mesh_slots: its entries from entry_begin on belong to the threads from
+// thread_begin on (the last run is followed by one that begins at the thread count).
+struct RefitRange { uint32_t entry_begin, thread_begin; };
+
+// The slots of the listed meshes only, one thread each (RefitMesh::pos of a mesh that is not listed is NULL), and the dirty
+// set: every node from the slot's leaf up to the root gets dirty[node] = epoch. Plain stores of one and the same value by
+// every writer; whoever finds a node marked stops, because the one who marked it goes on to the parent (by induction the
+// parent of every marked node is marked when the launch ends). A stale read -- another CU's store not seen yet -- only means
+// climbing further. Nothing is handed from one workgroup to another inside the launch: the flags are read by LATER launches.
+// MARK false: the triangles only (the full box passes follow, which ask nobody what is dirty).
+template <int MODE, bool MARK>
+__global__ void __launch_bounds__(256) k_refit_tris_listed(DevTri *tris, uint32_t n, const uint32_t *vertex_index, const uint32_t *slot_mesh,
+	const RefitMesh *meshes, uint32_t num_meshes, const uint32_t *mesh_slots, const uint32_t *slot_node, const RefitRange *ranges, uint32_t num_ranges,
+	uint32_t total, const uint32_t *parent, uint32_t *dirty, uint32_t num_nodes, uint32_t epoch)
+{
+	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+	uint32_t node = RTK_REF_NONE;
+	if (t < total) {
+		uint32_t lo = 0, hi = num_ranges;                      // the last run that begins at or before this thread
+		while (hi - lo > 1u) {
+			const uint32_t mid = (lo + hi) >> 1;
+			if (ranges[mid].thread_begin <= t) lo = mid; else hi = mid;
+		}
+		const uint32_t e = ranges[lo].entry_begin + (t - ranges[lo].thread_begin);
+		const uint32_t s = e < n ? mesh_slots[e] : RTK_REF_NONE;
+		const uint32_t mesh = s < n ? slot_mesh[s] : RTK_REF_NONE;
+		if (mesh < num_meshes) {
+			const RefitMesh ms = meshes[mesh];
+			if (ms.pos) {
+				refit_tri<MODE>(tris, s, vertex_index, ms);
+				if (MARK) node = slot_node[s];
+			}
+		}
+	}
+	if (!MARK) return;
+	// neighbouring slots mostly share their leaf: one lane of each run of equal nodes climbs
+	const uint32_t before = __shfl_up(node, 1);
+	if ((threadIdx.x & 63u) != 0u && before == node) node = RTK_REF_NONE;
+	while (node < num_nodes) {
+		if (dirty[node] == epoch) break;
+		dirty[node] = epoch;
+		node = parent[node];
+	}
+}
+
+// ---------------------------------------------------------------------------------- tables of the per-mesh refit (once per scene)
+
+// four lanes per node, one per child slot: the parent of an inner child, the holder of every slot of a leaf child
+__global__ void k_refit_parents(const DevNode *nodes, uint32_t n, const DevTri *tris, uint32_t num_tris, uint32_t *parent, uint32_t *slot_node)
+{
+	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t i = t >> 2;
+	if (i >= n) return;
+	const uint32_t ref = nodes[i].child[t & 3u];
+	if (ref == RTK_REF_NONE) return;
+	if (ref & RTK_REF_LEAF) {
+		const uint32_t first = ref & 0x7fffffffu;                // (the slots refit_child reads for this child)
+		uint32_t cnt = first < num_tris ? tris[first].spare : 0u;
+		if (cnt > 63u) cnt = 63u;
+		if (cnt > num_tris - first) cnt = num_tris - first;
+		for (uint32_t k = 0; k < cnt; k++) slot_node[first + k] = i;
+	} else if (ref < n) parent[ref] = i;
+}
+
+__global__ void k_refit_mesh_keys(const uint32_t *slot_mesh, uint32_t n, unsigned long long *keys)
+{
+	const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+	if (s < n) keys[s] = ((unsigned long long)slot_mesh[s] << 32) | s;
+}
+
+__global__ void k_refit_mesh_slots(const unsigned long long *keys, uint32_t n, uint32_t *mesh_slots)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) mesh_slots[i] = (uint32_t)keys[i];
+}
+
+// ---------------------------------------------------------------------------------- dirty nodes by height
+
+// entries e0 .. e0 + 3 of the schedule: bit k = node order[e0 + k] is dirty
+__device__ __forceinline__ uint32_t dirty_mask4(const uint32_t *order, uint32_t n, const uint32_t *dirty, uint32_t epoch, uint32_t e0, uint32_t node[4])
+{
+	uint32_t mask = 0;
+	if (e0 + 3u < n) {
+		const uint4 o = *reinterpret_cast<const uint4 *>(order + e0);    // (e0 is a multiple of four)
+		node[0] = o.x; node[1] = o.y; node[2] = o.z; node[3] = o.w;
+	} else {
+#pragma unroll
+		for (int k = 0; k < 4; k++) node[k] = e0 + k < n ? order[e0 + k] : RTK_REF_NONE;
+	}
+#pragma unroll
+	for (int k = 0; k < 4; k++) if (node[k] < n && dirty[node[k]] == epoch) mask |= 1u << k;
+	return mask;
+}
+
+// exclusive running sum of v over the 256 threads of a workgroup; *all = the sum over all of them
+__device__ __forceinline__ uint32_t block_scan_256(uint32_t v, uint32_t *all)
+{
+	__shared__ uint32_t wave_sum[4];
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	uint32_t incl = v;
+	for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o); if (lane >= (uint32_t)o) incl += t; }
+	if (lane == 63u) wave_sum[wave] = incl;
+	__syncthreads();
+	uint32_t base = 0, sum = 0;
+	for (uint32_t w = 0; w < 4u; w++) { if (w < wave) base += wave_sum[w]; sum += wave_sum[w]; }
+	*all = sum;
+	return base + incl - v;
+}
+
+// RTK_DIRTY_BLOCK entries of the schedule per workgroup: how many of them are dirty
+__global__ void __launch_bounds__(256) k_dirty_count(const uint32_t *order, uint32_t n, const uint32_t *dirty, uint32_t epoch, uint32_t *block)
+{
+	uint32_t node[4], all;
+	const uint32_t mask = dirty_mask4(order, n, dirty, epoch, blockIdx.x * RTK_DIRTY_BLOCK + threadIdx.x * 4u, node);
+	(void)block_scan_256(__popc(mask), &all);
+	if (threadIdx.x == 0u) block[blockIdx.x] = all;
+}
+
+// One workgroup: the counts become their exclusive running sums (block[nb] = the number of dirty nodes), then one wave per
+// height finds where that height begins in the compacted list: the dirty entries before level_start[h].
+__global__ void __launch_bounds__(1024) k_dirty_scan(uint32_t *block, uint32_t nb, const uint32_t *order, uint32_t n, const uint32_t *dirty, uint32_t epoch,
+	const uint32_t *level_start, uint32_t heights, uint32_t *list_start)
+{
+	__shared__ uint32_t wave_sum[16];
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	uint32_t carry = 0;
+	for (uint32_t b0 = 0; b0 < nb; b0 += 1024u) {
+		const uint32_t i = b0 + threadIdx.x;
+		const uint32_t v = i < nb ? block[i] : 0u;
+		uint32_t incl = v;
+		for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o); if (lane >= (uint32_t)o) incl += t; }
+		if (lane == 63u) wave_sum[wave] = incl;
+		__syncthreads();
+		uint32_t base = 0, sum = 0;
+		for (uint32_t w = 0; w < 16u; w++) { if (w < wave) base += wave_sum[w]; sum += wave_sum[w]; }
+		if (i < nb) block[i] = carry + base + incl - v;
+		carry += sum;
+		__syncthreads();
+	}
+	if (threadIdx.x == 0u) block[nb] = carry;
+	__syncthreads();                                           // (one workgroup: its own stores are what it reads below)
+	for (uint32_t h = wave; h <= heights; h += 16u) {
+		const uint32_t p = level_start[h] < n ? level_start[h] : n;
+		const uint32_t b = p / RTK_DIRTY_BLOCK;                  // (p == n on a block boundary: b == nb, the total)
+		uint32_t c = 0;
+		for (uint32_t e = b * RTK_DIRTY_BLOCK + lane; e < p; e += 64u) { const uint32_t node = order[e]; c += (node < n && dirty[node] == epoch) ? 1u : 0u; }
+		for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+		if (lane == 0u) list_start[h] = block[b] + c;
+	}
+}
+
+// the dirty nodes of the workgroup's entries, in the schedule's order, to where the running sums say
+__global__ void __launch_bounds__(256) k_dirty_scatter(const uint32_t *order, uint32_t n, const uint32_t *dirty, uint32_t epoch, const uint32_t *block, uint32_t *list)
+{
+	uint32_t node[4], all;
+	const uint32_t mask = dirty_mask4(order, n, dirty, epoch, blockIdx.x * RTK_DIRTY_BLOCK + threadIdx.x * 4u, node);
+	uint32_t at = block[blockIdx.x] + block_scan_256(__popc(mask), &all);
+#pragma unroll
+	for (int k = 0; k < 4; k++) if ((mask >> k & 1u) && at < n) list[at++] = node[k];
 }
 
 // ---------------------------------------------------------------------------------- boxes
@@ -196,6 +369,20 @@ __global__ void __launch_bounds__(256) k_refit_level(DevNode *nodes, const DevTr
 	if (e >= end) return;
 	const uint32_t node = order[e];
 	if (node < num_nodes) refit_child(nodes, tris, num_nodes, num_tris, node, t & 3u);
+}
+
+// one height of the dirty nodes: entries [list_start[h], list_start[h + 1]) of `list`, four lanes per node, grid-stride (the
+// host does not know how many there are)
+__global__ void __launch_bounds__(256) k_refit_level_list(DevNode *nodes, const DevTri *tris, uint32_t num_nodes, uint32_t num_tris,
+	const uint32_t *list, const uint32_t *list_start, uint32_t h)
+{
+	const uint32_t begin = list_start[h];
+	uint32_t end = list_start[h + 1u];
+	if (end > num_nodes) end = num_nodes;
+	for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; begin < end && (t >> 2) < end - begin; t += gridDim.x * blockDim.x) {
+		const uint32_t node = list[begin + (t >> 2)];
+		if (node < num_nodes) refit_child(nodes, tris, num_nodes, num_tris, node, t & 3u);
+	}
 }
 
 // heights [h0, h1) in one workgroup: what a height stores is read by the next one behind a barrier (workgroup scope is all
@@ -338,8 +525,80 @@ int make_max_vertex(rtk_dev_scene *ds, hipStream_t stream)
 	return RTK_AMD_OK;
 }
 
-// everything behind the argument checks; the scene's device is current
-int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t stream, WorkspaceLoan &loan)
+// temporaries of the per-mesh tables: two key arrays over the slots and the sort's scratch
+struct TablesTmp { size_t o_kb, o_sort, bytes; };
+TablesTmp tables_tmp(uint32_t num_tris)
+{
+	TablesTmp t;
+	t.o_kb = rtk_padded((size_t)num_tris * 8);
+	t.o_sort = t.o_kb + rtk_padded((size_t)num_tris * 8);
+	t.bytes = t.o_sort + rtk_padded(rtk_sort_scratch_words(num_tris) * 4);
+	return t;
+}
+
+// parent[], the node of every slot's leaf, the slots grouped by mesh, and the memory of the dirty set: once per scene, after
+// the schedule. tmp: tables_tmp(num_tris).bytes of device memory (the borrowed workspace).
+int make_partial_tables(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
+{
+	RefitPartial &rp = ds->partial;
+	if (rp.ready) return RTK_AMD_OK;
+	const DevSceneView &v = ds->view;
+	const uint32_t n = v.num_nodes, nt = v.num_tris;
+	const size_t num_meshes = ds->mesh_base.size() - 1;
+	const uint32_t nb = (n + RTK_DIRTY_BLOCK - 1u) / RTK_DIRTY_BLOCK;
+	const size_t heights = ds->refit.level_start.size() - 1;
+	const size_t o_slot_node = rtk_padded((size_t)n * 4), o_mesh_slots = o_slot_node + rtk_padded((size_t)nt * 4), o_dirty = o_mesh_slots + rtk_padded((size_t)nt * 4),
+		o_list = o_dirty + rtk_padded((size_t)n * 4), o_block = o_list + rtk_padded((size_t)n * 4), o_list_start = o_block + rtk_padded(((size_t)nb + 1) * 4),
+		o_ranges = o_list_start + rtk_padded((heights + 1) * 4), total = o_ranges + rtk_padded((num_meshes + 1) * sizeof(RefitRange));
+	void *mem = nullptr;
+	if (hipMalloc(&mem, total) != hipSuccess) { (void)hipGetLastError(); rtk_set_error("rtk_dev_scene_refit_meshes: out of device memory"); return RTK_AMD_ERR_OOM; }
+	char *base = (char *)mem;
+	uint32_t *d_parent = (uint32_t *)base, *d_slot_node = (uint32_t *)(base + o_slot_node), *d_mesh_slots = (uint32_t *)(base + o_mesh_slots);
+	const TablesTmp T = tables_tmp(nt);
+	unsigned long long *keys_a = (unsigned long long *)tmp, *keys_b = (unsigned long long *)(tmp + T.o_kb);
+	// (RTK_REF_NONE everywhere first: the root has no parent, and a slot no leaf names stays without a node)
+	bool ok = hipMemsetAsync(base, 0xff, o_mesh_slots, stream) == hipSuccess && hipMemsetAsync(base + o_dirty, 0, o_list - o_dirty, stream) == hipSuccess;
+	if (ok) {
+		hipLaunchKernelGGL(k_refit_parents, dim3((unsigned)(((size_t)n * 4 + 255) / 256)), dim3(256), 0, stream, v.nodes, n, v.tris, nt, d_parent, d_slot_node);
+		const unsigned blocks = (nt + 255u) / 256u;
+		hipLaunchKernelGGL(k_refit_mesh_keys, dim3(blocks), dim3(256), 0, stream, v.slot_mesh, nt, keys_a);
+		// mesh numbers are below num_meshes: that many bits of the upper word; stable, so the slots of a mesh stay ascending
+		uint32_t bits = 0;
+		while (bits < 32u && (1ull << bits) < (unsigned long long)num_meshes) bits++;
+		const unsigned long long *sorted = keys_a;
+		if (bits) sorted = rtk_sort_words_async(keys_a, keys_b, nt, 32u, 32u + bits, (uint32_t *)(tmp + T.o_sort), stream) ? keys_b : keys_a;
+		hipLaunchKernelGGL(k_refit_mesh_slots, dim3(blocks), dim3(256), 0, stream, sorted, nt, d_mesh_slots);
+		ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+	}
+	if (!ok) {
+		rtk_set_error("rtk_dev_scene_refit_meshes: tables: %s", hipGetErrorString(hipGetLastError()));
+		(void)hipFree(mem);
+		return RTK_AMD_ERR_HIP;
+	}
+	ds->allocs.push_back(mem);
+	ds->total_bytes += (size_t)n * 12 + (size_t)nt * 8 + ((size_t)nb + 1) * 4 + (heights + 1) * 4 + (num_meshes + 1) * sizeof(RefitRange);
+	rp.d_parent = d_parent; rp.d_slot_node = d_slot_node; rp.d_mesh_slots = d_mesh_slots;
+	rp.d_dirty = (uint32_t *)(base + o_dirty); rp.d_list = (uint32_t *)(base + o_list); rp.d_block = (uint32_t *)(base + o_block);
+	rp.d_list_start = (uint32_t *)(base + o_list_start); rp.d_ranges = base + o_ranges;
+	rp.epoch = 0;
+	rp.ready = true;
+	return RTK_AMD_OK;
+}
+
+// Above this share of the scene's triangles in the listed meshes the dirty-set passes lose against the full box and finish
+// passes, which then run instead (the triangles are still regathered for the listed meshes only). Where the two measured
+// curves meet, rounded down to a power of two: profiles/refit_meshes_timing.log. RTK_AMD_REFIT_MESHES_SHARE overrides it
+// (0: always the full passes, 1: never), for A/B; read at every call, so one process can measure both.
+#define REFIT_MESHES_MAX_SHARE 0.25
+double partial_max_share()
+{
+	const char *e = getenv("RTK_AMD_REFIT_MESHES_SHARE");
+	return e ? atof(e) : REFIT_MESHES_MAX_SHARE;
+}
+
+// everything behind the argument checks; the scene's device is current. listed: NULL = every mesh (rtk_dev_scene_refit), else
+// one flag per mesh (rtk_dev_scene_refit_meshes), with listed_tris triangles (not zero) in the flagged ones.
+int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t stream, WorkspaceLoan &loan, const uint8_t *listed, uint64_t listed_tris)
 {
 	int rc = rtk_scene_side_arrays(ds, stream);
 	if (rc != RTK_AMD_OK) return rc;
@@ -355,7 +614,7 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 	bool any_device = false, any_f32 = false, any_f64 = false;
 	for (size_t mi = 0; mi < num_meshes; mi++) {
 		const rtk_mesh *m = &desc->meshes[mi];
-		if (m->num_triangles == 0) continue;
+		if (m->num_triangles == 0 || (listed && !listed[mi])) continue;
 		RefitMesh &t = table[mi];
 		t.f64 = m->position.type == RTK_TYPE_F64 ? 1u : 0u;
 		t.stride = m->position.stride ? m->position.stride : (t.f64 ? 24 : 12);
@@ -368,12 +627,18 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 		upload_bytes += rtk_padded(upload[mi]);
 	}
 	// the workspace: first the temporaries of the schedule (the first refit of a scene; over when make_schedule returns), then
-	// the staged positions
+	// those of the per-mesh tables (the first refit of some meshes), then the staged positions
 	const size_t schedule_bytes = rs.ready ? 0 : schedule_tmp(ds->view.num_nodes).bytes;
-	const size_t borrow = schedule_bytes > upload_bytes ? schedule_bytes : upload_bytes;
+	const size_t tables_bytes = listed && !ds->partial.ready ? tables_tmp(v.num_tris).bytes : 0;
+	size_t borrow = schedule_bytes > upload_bytes ? schedule_bytes : upload_bytes;
+	if (tables_bytes > borrow) borrow = tables_bytes;
 	if (borrow && !loan.take(ds->device, borrow)) return RTK_AMD_ERR_OOM;
 	rc = make_schedule(ds, stream, loan.base);
 	if (rc != RTK_AMD_OK) return rc;
+	if (listed) {
+		rc = make_partial_tables(ds, stream, loan.base);
+		if (rc != RTK_AMD_OK) return rc;
+	}
 	if (upload_bytes) {
 		char *base = loan.base;
 		size_t off = 0;
@@ -388,46 +653,175 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 	if (any_device && stream != nullptr) REFIT_CHECK(hipStreamSynchronize(nullptr));
 	if (num_meshes) REFIT_CHECK(hipMemcpyAsync(rs.d_meshes, table.data(), num_meshes * sizeof(RefitMesh), hipMemcpyHostToDevice, stream));
 
+	// Until this call has succeeded nobody may take the boxes it leaves alone for exact unions.
+	const bool were_exact = ds->boxes_exact;
+	ds->boxes_exact = false;
+	// the dirty set pays while the listed meshes are a small part of the scene and the other boxes can be trusted
+	const bool dirty_set = listed && were_exact && (double)listed_tris <= partial_max_share() * (double)v.num_tris;
+
 	// ---- triangles
 	DevTri *tris = const_cast<DevTri *>(v.tris);
 	DevNode *nodes = const_cast<DevNode *>(v.nodes);
-	if (v.num_tris) {
+	const RefitMesh *dm = (const RefitMesh *)rs.d_meshes;
+	if (listed) {
+		RefitPartial &rp = ds->partial;
+		// runs of listed meshes that are neighbours in mesh_slots, one thread per slot
+		std::vector<RefitRange> ranges;
+		uint64_t threads = 0, run_end = 0;
+		for (size_t mi = 0; mi < num_meshes; mi++) {
+			if (!listed[mi] || ds->mesh_base[mi + 1] == ds->mesh_base[mi]) continue;
+			if (ranges.empty() || run_end != ds->mesh_base[mi]) ranges.push_back(RefitRange{ (uint32_t)ds->mesh_base[mi], (uint32_t)threads });
+			threads += ds->mesh_base[mi + 1] - ds->mesh_base[mi];
+			run_end = ds->mesh_base[mi + 1];
+		}
+		REFIT_CHECK(hipMemcpyAsync(rp.d_ranges, ranges.data(), ranges.size() * sizeof(RefitRange), hipMemcpyHostToDevice, stream));
+		if (++rp.epoch == 0u) {                                  // (every 2^32 calls the flags start over)
+			REFIT_CHECK(hipMemsetAsync(rp.d_dirty, 0, (size_t)v.num_nodes * 4, stream));
+			rp.epoch = 1u;
+		}
+		const uint32_t total = (uint32_t)threads;
+		const dim3 grid((total + 255u) / 256u), block(256);
+		const RefitRange *dr = (const RefitRange *)rp.d_ranges;
+#define LISTED_ARGS tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, (uint32_t)num_meshes, rp.d_mesh_slots, rp.d_slot_node, dr, (uint32_t)ranges.size(), total, rp.d_parent, rp.d_dirty, v.num_nodes, rp.epoch
+		const int mode = any_f64 && any_f32 ? 2 : any_f64 ? 1 : 0;
+		if (dirty_set) {
+			if (mode == 2) hipLaunchKernelGGL((k_refit_tris_listed<2, true>), grid, block, 0, stream, LISTED_ARGS);
+			else if (mode == 1) hipLaunchKernelGGL((k_refit_tris_listed<1, true>), grid, block, 0, stream, LISTED_ARGS);
+			else hipLaunchKernelGGL((k_refit_tris_listed<0, true>), grid, block, 0, stream, LISTED_ARGS);
+		} else {
+			if (mode == 2) hipLaunchKernelGGL((k_refit_tris_listed<2, false>), grid, block, 0, stream, LISTED_ARGS);
+			else if (mode == 1) hipLaunchKernelGGL((k_refit_tris_listed<1, false>), grid, block, 0, stream, LISTED_ARGS);
+			else hipLaunchKernelGGL((k_refit_tris_listed<0, false>), grid, block, 0, stream, LISTED_ARGS);
+		}
+#undef LISTED_ARGS
+		REFIT_CHECK(hipGetLastError());
+	} else if (v.num_tris) {
 		const dim3 grid((v.num_tris + 255u) / 256u), block(256);
-		const RefitMesh *dm = (const RefitMesh *)rs.d_meshes;
 		if (any_f64 && any_f32) hipLaunchKernelGGL((k_refit_tris<2>), grid, block, 0, stream, tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, (uint32_t)num_meshes);
 		else if (any_f64) hipLaunchKernelGGL((k_refit_tris<1>), grid, block, 0, stream, tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, (uint32_t)num_meshes);
 		else hipLaunchKernelGGL((k_refit_tris<0>), grid, block, 0, stream, tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, (uint32_t)num_meshes);
 		REFIT_CHECK(hipGetLastError());
 	}
 
-	// ---- boxes, height by height; runs of small heights share one launch of one workgroup
 	const uint32_t heights = (uint32_t)rs.level_start.size() - 1u;
-	for (uint32_t h = 0; h < heights;) {
-		const uint32_t begin = rs.level_start[h], end = rs.level_start[h + 1];
-		if (end - begin > REFIT_SMALL_LEVEL) {
-			const unsigned blocks = (unsigned)(((size_t)(end - begin) * 4 + 255) / 256);
-			hipLaunchKernelGGL(k_refit_level, dim3(blocks), dim3(256), 0, stream, nodes, tris, v.num_nodes, v.num_tris, rs.d_order, begin, end);
-			h++;
-		} else {
-			uint32_t h1 = h + 1;
-			while (h1 < heights && rs.level_start[h1 + 1] - rs.level_start[h1] <= REFIT_SMALL_LEVEL) h1++;
-			hipLaunchKernelGGL(k_refit_small, dim3(1), dim3(REFIT_SMALL_THREADS), 0, stream, nodes, tris, v.num_nodes, v.num_tris, rs.d_order, rs.d_level_start, h, h1);
-			h = h1;
+	bool full_finish = true;
+	if (dirty_set) {
+		// ---- the dirty nodes in the schedule's order, and where each height begins among them (all of it stays on the device)
+		RefitPartial &rp = ds->partial;
+		const uint32_t n = v.num_nodes, nb = (n + RTK_DIRTY_BLOCK - 1u) / RTK_DIRTY_BLOCK;
+		hipLaunchKernelGGL(k_dirty_count, dim3(nb), dim3(256), 0, stream, rs.d_order, n, rp.d_dirty, rp.epoch, rp.d_block);
+		hipLaunchKernelGGL(k_dirty_scan, dim3(1), dim3(1024), 0, stream, rp.d_block, nb, rs.d_order, n, rp.d_dirty, rp.epoch, rs.d_level_start, heights, rp.d_list_start);
+		hipLaunchKernelGGL(k_dirty_scatter, dim3(nb), dim3(256), 0, stream, rs.d_order, n, rp.d_dirty, rp.epoch, rp.d_block, rp.d_list);
+		// ---- their boxes, height by height. Which heights get a launch of their own is the full schedule's decision (the host
+		// does not know the dirty counts): a height that is small there is small here.
+		for (uint32_t h = 0; h < heights;) {
+			const uint32_t begin = rs.level_start[h], end = rs.level_start[h + 1];
+			if (end - begin > REFIT_SMALL_LEVEL) {
+				size_t blocks = ((size_t)(end - begin) * 4 + 255) / 256;
+				if (blocks > 2048) blocks = 2048;
+				hipLaunchKernelGGL(k_refit_level_list, dim3((unsigned)blocks), dim3(256), 0, stream, nodes, tris, v.num_nodes, v.num_tris, rp.d_list, rp.d_list_start, h);
+				h++;
+			} else {
+				uint32_t h1 = h + 1;
+				while (h1 < heights && rs.level_start[h1 + 1] - rs.level_start[h1] <= REFIT_SMALL_LEVEL) h1++;
+				hipLaunchKernelGGL(k_refit_small, dim3(1), dim3(REFIT_SMALL_THREADS), 0, stream, nodes, tris, v.num_nodes, v.num_tris, rp.d_list, rp.d_list_start, h, h1);
+				h = h1;
+			}
 		}
+		REFIT_CHECK(hipGetLastError());
+		REFIT_CHECK(hipMemcpyAsync(&ds->partial_readback, rp.d_block + nb, 4, hipMemcpyDeviceToHost, stream));
+		// ---- compressed nodes and order words of the dirty nodes, the constants from the root (dirty whenever anything moved).
+		// The misfit count is one over ALL nodes: the list form is the whole answer only if the others have none (the scene is on
+		// its compressed nodes now) and none of the dirty ones has one either; else the full pass below.
+		if (v.qnodes && ds->qnodes_mem) {
+			rc = rtk_quantize_node_list(ds, stream, rp.d_list, rp.d_block + nb);
+			if (rc != RTK_AMD_OK) return rc;
+			REFIT_CHECK(hipStreamSynchronize(stream));
+			full_finish = ds->consts_readback.qnode_misfits != 0u;
+		}
+	} else {
+		// ---- boxes, height by height; runs of small heights share one launch of one workgroup
+		for (uint32_t h = 0; h < heights;) {
+			const uint32_t begin = rs.level_start[h], end = rs.level_start[h + 1];
+			if (end - begin > REFIT_SMALL_LEVEL) {
+				const unsigned blocks = (unsigned)(((size_t)(end - begin) * 4 + 255) / 256);
+				hipLaunchKernelGGL(k_refit_level, dim3(blocks), dim3(256), 0, stream, nodes, tris, v.num_nodes, v.num_tris, rs.d_order, begin, end);
+				h++;
+			} else {
+				uint32_t h1 = h + 1;
+				while (h1 < heights && rs.level_start[h1 + 1] - rs.level_start[h1] <= REFIT_SMALL_LEVEL) h1++;
+				hipLaunchKernelGGL(k_refit_small, dim3(1), dim3(REFIT_SMALL_THREADS), 0, stream, nodes, tris, v.num_nodes, v.num_tris, rs.d_order, rs.d_level_start, h, h1);
+				h = h1;
+			}
+		}
+		REFIT_CHECK(hipGetLastError());
 	}
-	REFIT_CHECK(hipGetLastError());
 
-	// ---- compressed nodes, order words, constants (the block is cleared first: the misfit count starts at zero); every box
-	// lies inside the root's now, so no bound is passed in
-	rc = rtk_quantize_nodes(ds, stream, nullptr, const_cast<DevNodeQ *>(ds->qnodes_mem), 0.0f, 0xffffffffu, false, true);
-	if (rc != RTK_AMD_OK) return rc;
-	REFIT_CHECK(hipStreamSynchronize(stream));
+	if (full_finish) {
+		// ---- compressed nodes, order words, constants (the block is cleared first: the misfit count starts at zero); every box
+		// lies inside the root's now, so no bound is passed in
+		rc = rtk_quantize_nodes(ds, stream, nullptr, const_cast<DevNodeQ *>(ds->qnodes_mem), 0.0f, 0xffffffffu, false, true);
+		if (rc != RTK_AMD_OK) return rc;
+		REFIT_CHECK(hipStreamSynchronize(stream));
+	}
 	{
 		// (the trace path reads these host fields under the same mutex when it enqueues a launch)
 		std::lock_guard<std::mutex> lock(ds->scratch_mutex);
 		rtk_quantize_finish(ds);
 	}
 	rtk_export_forget(ds);
+	ds->boxes_exact = true;
+	ds->refit_nodes = dirty_set ? ds->partial_readback : v.num_nodes;
+	return RTK_AMD_OK;
+}
+
+// what both entry points do once nothing can be refused any more
+int refit_locked(rtk_dev_scene *ds, const rtk_scene_desc *desc, void *stream, const uint8_t *listed, uint64_t listed_tris)
+{
+	const auto t_begin = std::chrono::steady_clock::now();
+	std::lock_guard<std::mutex> lock(ds->refit_mutex);
+	int before = 0;
+	RTK_HIP_CHECK(hipGetDevice(&before), RTK_AMD_ERR_NO_DEVICE);
+	if (before != ds->device) RTK_HIP_CHECK(hipSetDevice(ds->device), RTK_AMD_ERR_NO_DEVICE);
+	WorkspaceLoan loan;
+	const int rc = refit_on_device(ds, desc, (hipStream_t)stream, loan, listed, listed_tris);
+	// (a failure may leave work enqueued that reads this call's tables or the workspace: it has to be over first)
+	if (rc != RTK_AMD_OK) (void)hipStreamSynchronize((hipStream_t)stream);
+	loan.release();
+	if (before != ds->device) (void)hipSetDevice(before);
+	if (rc == RTK_AMD_OK) ds->refit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	return rc;
+}
+
+// the rules for the positions of a mesh that is read
+int check_mesh_positions(const char *who, const rtk_mesh *m, size_t mi)
+{
+	if (m->position_cb) { rtk_set_error("%s: mesh %zu: position callbacks are not supported by a refit", who, mi); return RTK_AMD_ERR_UNSUPPORTED; }
+	if (m->num_triangles == 0) return RTK_AMD_OK;
+	if (m->position.type != RTK_TYPE_DEFAULT && m->position.type != RTK_TYPE_REAL && m->position.type != RTK_TYPE_F32 && m->position.type != RTK_TYPE_F64) {
+		rtk_set_error("%s: mesh %zu: bad position type %d", who, mi, (int)m->position.type);
+		return RTK_AMD_ERR_BAD_ARG;
+	}
+	if (!m->position.data) { rtk_set_error("%s: mesh %zu has no positions", who, mi); return RTK_AMD_ERR_BAD_ARG; }
+	return RTK_AMD_OK;
+}
+
+// the description against the scene it claims to describe
+int check_desc(const char *who, const rtk_dev_scene *ds, const rtk_scene_desc *desc)
+{
+	if (!desc->meshes && desc->num_meshes) { rtk_set_error("%s: NULL meshes", who); return RTK_AMD_ERR_BAD_ARG; }
+	const size_t scene_meshes = ds->mesh_base.empty() ? 0 : ds->mesh_base.size() - 1;
+	if (desc->num_meshes != scene_meshes) {
+		rtk_set_error("%s: %zu meshes, the scene was made from %zu", who, (size_t)desc->num_meshes, scene_meshes);
+		return RTK_AMD_ERR_BAD_ARG;
+	}
+	for (size_t mi = 0; mi < desc->num_meshes; mi++) {
+		const uint64_t have = ds->mesh_base[mi + 1] - ds->mesh_base[mi];
+		if ((uint64_t)desc->meshes[mi].num_triangles != have) {
+			rtk_set_error("%s: mesh %zu has %zu triangles, the scene's has %llu", who, mi, (size_t)desc->meshes[mi].num_triangles, (unsigned long long)have);
+			return RTK_AMD_ERR_BAD_ARG;
+		}
+	}
 	return RTK_AMD_OK;
 }
 
@@ -437,46 +831,53 @@ extern "C" int rtk_dev_scene_refit(rtk_dev_scene *ds, const rtk_scene_desc *desc
 {
 	// ---- everything that can be refused is refused here, before HIP is touched
 	if (!ds || !desc) { rtk_set_error("rtk_dev_scene_refit: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
-	if (!desc->meshes && desc->num_meshes) { rtk_set_error("rtk_dev_scene_refit: NULL meshes"); return RTK_AMD_ERR_BAD_ARG; }
-	const size_t scene_meshes = ds->mesh_base.empty() ? 0 : ds->mesh_base.size() - 1;
-	if (desc->num_meshes != scene_meshes) {
-		rtk_set_error("rtk_dev_scene_refit: %zu meshes, the scene was made from %zu", (size_t)desc->num_meshes, scene_meshes);
-		return RTK_AMD_ERR_BAD_ARG;
-	}
+	int rc = check_desc("rtk_dev_scene_refit", ds, desc);
+	if (rc != RTK_AMD_OK) return rc;
 	for (size_t mi = 0; mi < desc->num_meshes; mi++) {
-		const uint64_t have = ds->mesh_base[mi + 1] - ds->mesh_base[mi];
-		if ((uint64_t)desc->meshes[mi].num_triangles != have) {
-			rtk_set_error("rtk_dev_scene_refit: mesh %zu has %zu triangles, the scene's has %llu", mi, (size_t)desc->meshes[mi].num_triangles, (unsigned long long)have);
-			return RTK_AMD_ERR_BAD_ARG;
-		}
+		rc = check_mesh_positions("rtk_dev_scene_refit", &desc->meshes[mi], mi);
+		if (rc != RTK_AMD_OK) return rc;
 	}
-	for (size_t mi = 0; mi < desc->num_meshes; mi++) {
-		const rtk_mesh *m = &desc->meshes[mi];
-		if (m->position_cb) { rtk_set_error("rtk_dev_scene_refit: mesh %zu: position callbacks are not supported by a refit", mi); return RTK_AMD_ERR_UNSUPPORTED; }
-		if (m->num_triangles == 0) continue;
-		if (m->position.type != RTK_TYPE_DEFAULT && m->position.type != RTK_TYPE_REAL && m->position.type != RTK_TYPE_F32 && m->position.type != RTK_TYPE_F64) {
-			rtk_set_error("rtk_dev_scene_refit: mesh %zu: bad position type %d", mi, (int)m->position.type);
-			return RTK_AMD_ERR_BAD_ARG;
-		}
-		if (!m->position.data) { rtk_set_error("rtk_dev_scene_refit: mesh %zu has no positions", mi); return RTK_AMD_ERR_BAD_ARG; }
-	}
+	return refit_locked(ds, desc, stream, nullptr, 0);
+}
 
-	const auto t_begin = std::chrono::steady_clock::now();
-	std::lock_guard<std::mutex> lock(ds->refit_mutex);
-	int before = 0;
-	RTK_HIP_CHECK(hipGetDevice(&before), RTK_AMD_ERR_NO_DEVICE);
-	if (before != ds->device) RTK_HIP_CHECK(hipSetDevice(ds->device), RTK_AMD_ERR_NO_DEVICE);
-	WorkspaceLoan loan;
-	const int rc = refit_on_device(ds, desc, (hipStream_t)stream, loan);
-	// (a failure may leave work enqueued that reads this call's tables or the workspace: it has to be over first)
-	if (rc != RTK_AMD_OK) (void)hipStreamSynchronize((hipStream_t)stream);
-	loan.release();
-	if (before != ds->device) (void)hipSetDevice(before);
-	if (rc == RTK_AMD_OK) ds->refit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-	return rc;
+extern "C" int rtk_dev_scene_refit_meshes(rtk_dev_scene *ds, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids, void *stream)
+{
+	// ---- as above: every refusal before HIP is touched; only the listed meshes' positions are looked at
+	const char *who = "rtk_dev_scene_refit_meshes";
+	if (!ds || !desc) { rtk_set_error("%s: NULL argument", who); return RTK_AMD_ERR_BAD_ARG; }
+	if (!mesh_ids && num_ids) { rtk_set_error("%s: NULL mesh_ids with %zu ids", who, num_ids); return RTK_AMD_ERR_BAD_ARG; }
+	int rc = check_desc(who, ds, desc);
+	if (rc != RTK_AMD_OK) return rc;
+	std::vector<uint8_t> listed(desc->num_meshes ? desc->num_meshes : 1, 0);
+	for (size_t k = 0; k < num_ids; k++) {
+		if (mesh_ids[k] >= desc->num_meshes) { rtk_set_error("%s: mesh id %u, the scene has %zu meshes", who, mesh_ids[k], (size_t)desc->num_meshes); return RTK_AMD_ERR_BAD_ARG; }
+		listed[mesh_ids[k]] = 1;                                 // (an id that repeats counts once)
+	}
+	uint64_t listed_tris = 0;
+	for (size_t mi = 0; mi < desc->num_meshes; mi++) {
+		if (!listed[mi]) continue;
+		rc = check_mesh_positions(who, &desc->meshes[mi], mi);
+		if (rc != RTK_AMD_OK) return rc;
+		listed_tris += desc->meshes[mi].num_triangles;
+	}
+	if (listed_tris == 0) {
+		// nothing moves: no bit changes, nothing is launched
+		std::lock_guard<std::mutex> lock(ds->refit_mutex);
+		ds->refit_nodes = 0;
+		ds->refit_ms = 0.0;
+		return RTK_AMD_OK;
+	}
+	// every mesh that has a triangle is listed: that IS the full refit (no mesh it would read is one this call may not read)
+	if (listed_tris == ds->mesh_base.back()) return refit_locked(ds, desc, stream, nullptr, 0);
+	return refit_locked(ds, desc, stream, listed.data(), listed_tris);
 }
 
 extern "C" double rtk_dev_scene_last_refit_ms(const rtk_dev_scene *ds)
 {
 	return ds ? ds->refit_ms : 0.0;
+}
+
+extern "C" uint64_t rtk_dev_scene_last_refit_nodes(const rtk_dev_scene *ds)
+{
+	return ds ? ds->refit_nodes : 0;
 }
