@@ -3,6 +3,7 @@
 // HIP plumbing. No intersection arithmetic lives here and there is no CPU fallback:
 // every trace call runs the HIP kernels of rtk_trace.hip or fails with an error.
 #include "rtk_dev.h"
+#include "rtk_trace_plan.h"
 
 #include <algorithm>
 #include "rtk_layout_check.h"
@@ -586,9 +587,8 @@ extern "C" size_t rtk_trace_rays(const rtk_scene *scene, const rtk_ray *rays, si
 	const rtk_trace_opts *piece_opts = nullptr;
 	{
 		uint32_t iw = 0, ih = 0;
-		static const bool detect = !(getenv("RTK_AMD_DETECT_IMAGE") && atoi(getenv("RTK_AMD_DETECT_IMAGE")) == 0);
-		if (detect) host_detect_image(rays, n, &iw, &ih);
-		if (iw >= 128u && (iw % 64u) == 0u && (ih % 64u) == 0u && (size_t)iw * 64u <= ((size_t)1 << 21)) {
+		if (rtk_trace_knobs().detect_image != 0) host_detect_image(rays, n, &iw, &ih);
+		if (iw >= 128u && whole_blocks(iw, ih) && (size_t)iw * 64u <= ((size_t)1 << 21)) {
 			size_t band_rows = 64;
 			while ((band_rows * 2) * (size_t)iw <= ((size_t)1 << 18) && band_rows * 2 <= ih) band_rows *= 2;
 			PIPE_CHUNK = band_rows * (size_t)iw;

@@ -114,8 +114,8 @@ struct LaunchScratch {
 	void *d_entries = nullptr;                  // packet kernels: entry lists of the image's 64x64-pixel blocks (PkBlockEntries), grown on demand
 	size_t entries_capacity = 0;                // blocks
 	volatile uint32_t *h_verdict = nullptr;     // pinned: where k_detect_check leaves (width, height) of an image nobody announced
-	uint32_t *d_leftover = nullptr;             // tiles the assembly packet kernel hands to the C++ one, grown on demand
-	size_t leftover_capacity = 0;               // tiles
+	uint32_t *d_leftover = nullptr;             // tiles the assembly packet kernel hands to the C++ one, or rays the assembly per-lane kernel hands to rtk_trace_kernel; grown on demand
+	size_t leftover_capacity = 0;               // bytes
 };
 
 // What a refit needs besides the scene (rtk_refit.hip): the node numbers grouped by HEIGHT (0: every child is a leaf or

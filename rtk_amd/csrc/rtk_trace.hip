@@ -873,7 +873,6 @@ trace_kernel_fn trace_variant(int v)
 	default: return rtk_trace_kernel<2, false, true, true>;
 	}
 }
-enum { VARIANT_COLLECT = 16, VARIANT_PACKET = 18, VARIANT_PACKET_COUNTED = 19, NUM_VARIANTS = 20 };
 
 // resident workgroups per CU of each kernel variant, per device; filled on first use
 std::mutex g_occ_mutex;
@@ -973,57 +972,74 @@ LaunchScratch *scratch_for(rtk_dev_scene *ds, hipStream_t stream)
 
 } // namespace
 
-// ---- the hand-written per-lane kernels: a code object of its own (rtk_lane_hot.S, assembled by the Makefile), carried in
-// this library as a byte array and loaded once per device
+// ---- the hand-written kernels' code objects (AsmModule, rtk_trace_shared.h). The per-lane ones (rtk_lane_hot.S) belong to this file.
 #include "rtk_lane_hot_image.h"
 
-namespace {
-struct LaneModule { hipModule_t mod = nullptr; hipFunction_t fn[2] = { nullptr, nullptr }; int blocks_per_cu = 0; bool tried = false; };
-std::mutex g_lane_mutex;
-LaneModule g_lane[RTK_MAX_DEVICES];
+const TraceKnobs &rtk_trace_knobs()
+{
+	static const TraceKnobs knobs = [] {
+		const auto env = [](const char *name, int value) { const char *v = getenv(name); return v ? atoi(v) : value; };
+		TraceKnobs k;
+		k.detect_image = env("RTK_AMD_DETECT_IMAGE", k.detect_image);
+		k.tile_blocks = env("RTK_AMD_TILE_BLOCKS", k.tile_blocks);
+		k.any_packets = env("RTK_AMD_ANY_PACKETS", k.any_packets);
+		k.qnodes = env("RTK_AMD_QNODES", k.qnodes);
+		k.packet_asm = env("RTK_AMD_PACKET_ASM", k.packet_asm);
+		// (a number below 0 is the C++ kernel, one above 2 is 2: the counting and any-hit forms are not for choosing)
+		const int wanted = env("RTK_AMD_PACKET_BEAM", (int)k.packet_beam);
+		k.packet_beam = wanted < 0 ? PacketKernel::Cpp : wanted > (int)PacketKernel::Beam2 ? PacketKernel::Beam2 : (PacketKernel)wanted;
+		k.log_path = getenv("RTK_AMD_LOG_PATH") != nullptr;
+		k.lane_asm = env("RTK_AMD_LANE_ASM", k.lane_asm);
+		k.lane_lds = (size_t)env("RTK_AMD_LANE_LDS", (int)k.lane_lds);
+		k.sort_cell_bits = (uint32_t)env("RTK_AMD_SORT_CELL_BITS", (int)k.sort_cell_bits);
+		k.sort_octant = (uint32_t)env("RTK_AMD_SORT_OCTANT", (int)k.sort_octant);
+		k.sort_key = env("RTK_AMD_SORT_KEY", k.sort_key);
+		k.packet_entries = env("RTK_AMD_PACKET_ENTRIES", k.packet_entries);
+		k.entry_target = (unsigned)env("RTK_AMD_ENTRY_TARGET", (int)k.entry_target);
+		k.entry_levels = (unsigned)env("RTK_AMD_ENTRY_LEVELS", (int)k.entry_levels);
+		k.hot_blocks_per_cu = env("RTK_AMD_HOT_BLOCKS_PER_CU", k.hot_blocks_per_cu);
+		k.lane_stats = env("RTK_AMD_LANE_STATS", k.lane_stats);
+		k.lane_blocks = env("RTK_AMD_LANE_BLOCKS", k.lane_blocks);
+		return k;
+	}();
+	return knobs;
+}
 
-LaneModule *lane_module(int device)
+AsmModule &rtk_lane_module()
+{
+	// 80 VGPRs, 30 KB of LDS per workgroup: five workgroups per CU; the any-hit kernel is launched on the same figure
+	static const AsmKernel table[2] = { { "rtk_lane_hot_closest", rtk_trace_knobs().lane_blocks }, { "rtk_lane_hot_any", 0 } };
+	static AsmModule m(rtk_lane_hot_image, table, 2, "rtk_dev_trace: the assembly per-lane kernels are not loaded");
+	return m;
+}
+
+const AsmModule::Loaded *AsmModule::on(int device)
 {
 	if (device < 0 || device >= RTK_MAX_DEVICES) return nullptr;
-	std::lock_guard<std::mutex> lock(g_lane_mutex);
-	LaneModule &h = g_lane[device];
+	std::lock_guard<std::mutex> lock(mutex);
+	Loaded &h = slot[device];
 	if (!h.tried) {
 		int cur = -1;
-		if (hipGetDevice(&cur) != hipSuccess || cur != device) return nullptr;      // loaded by a thread that has this device current (asked again later)
+		if (hipGetDevice(&cur) != hipSuccess || cur != device) return nullptr;
 		h.tried = true;
-		if (hipModuleLoadData(&h.mod, rtk_lane_hot_image) != hipSuccess ||
-			hipModuleGetFunction(&h.fn[0], h.mod, "rtk_lane_hot_closest") != hipSuccess ||
-			hipModuleGetFunction(&h.fn[1], h.mod, "rtk_lane_hot_any") != hipSuccess) {
-			(void)hipGetLastError();
-			h.fn[0] = h.fn[1] = nullptr;
-		} else {
-			// 80 VGPRs, 30 KB of LDS per workgroup: five workgroups per CU
+		if (hipModuleLoadData(&h.mod, image) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+		for (int k = 0; k < count; k++) {
+			if (hipModuleGetFunction(&h.fn[k], h.mod, table[k].name) != hipSuccess) { (void)hipGetLastError(); h.fn[k] = nullptr; continue; }
+			if (table[k].cap == 0) continue;
 			int nb = 0;
-			if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, h.fn[0], BLOCK_THREADS, 0) != hipSuccess || nb < 1) nb = 1;
-			static const int cap = getenv("RTK_AMD_LANE_BLOCKS") ? atoi(getenv("RTK_AMD_LANE_BLOCKS")) : 5;
-			h.blocks_per_cu = nb > cap ? cap : nb;
+			if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, h.fn[k], TRACE_BLOCK_THREADS, 0) != hipSuccess || nb < 1) nb = 1;
+			h.blocks_per_cu[k] = nb > table[k].cap ? table[k].cap : nb;
 		}
 	}
 	return h.fn[0] ? &h : nullptr;
 }
-} // namespace
 
-bool rtk_lane_hot_available(int device, int *blocks_per_cu)
+int AsmModule::launch(int device, int kernel, void *params, size_t size, unsigned blocks, hipStream_t stream)
 {
-	LaneModule *h = lane_module(device);
-	if (!h) return false;
-	if (blocks_per_cu) *blocks_per_cu = h->blocks_per_cu;
-	return true;
-}
-
-int rtk_lane_hot_launch(int device, const LnHotParams &hp_in, unsigned blocks, hipStream_t stream, bool any_hit)
-{
-	LaneModule *h = lane_module(device);
-	if (!h) { rtk_set_error("rtk_dev_trace: the assembly per-lane kernels are not loaded"); return RTK_AMD_ERR_HIP; }
-	LnHotParams hp = hp_in;
-	size_t size = sizeof(hp);
-	void *config[] = { HIP_LAUNCH_PARAM_BUFFER_POINTER, &hp, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END };
-	RTK_HIP_CHECK(hipModuleLaunchKernel(h->fn[any_hit ? 1 : 0], blocks, 1, 1, BLOCK_THREADS, 1, 1, 0, stream, nullptr, config), RTK_AMD_ERR_HIP);
+	const Loaded *h = on(device);
+	if (!h || kernel < 0 || kernel >= count || !h->fn[kernel]) { rtk_set_error("%s", not_loaded); return RTK_AMD_ERR_HIP; }
+	void *config[] = { HIP_LAUNCH_PARAM_BUFFER_POINTER, params, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END };
+	RTK_HIP_CHECK(hipModuleLaunchKernel(h->fn[kernel], blocks, 1, 1, TRACE_BLOCK_THREADS, 1, 1, 0, stream, nullptr, config), RTK_AMD_ERR_HIP);
 	return RTK_AMD_OK;
 }
 
@@ -1064,6 +1080,187 @@ int rtk_detect_image(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, size_t n,
 	return RTK_AMD_OK;
 }
 
+namespace {
+
+// the scene's memory, its scratch and the stream must all belong to the device this thread has current: a launch from a
+// thread on another GPU would read the scene across devices (a fault without peer access)
+bool on_scene_device(const rtk_dev_scene *ds, const char *caller)
+{
+	int cur = -1;
+	if (hipGetDevice(&cur) == hipSuccess && cur == ds->device) return true;
+	rtk_set_error("%s: the scene lives on device %d, the calling thread's current device is %d", caller, ds->device, cur);
+	return false;
+}
+
+// the kernels address nodes and triangles as SGPR base + 32-bit byte offset
+bool within_4gib(const DevSceneView &v)
+{
+	return (uint64_t)v.num_nodes * 128u <= 0xffffff00ull && (uint64_t)v.num_tris * RTK_TRI_STRIDE <= 0xffffff00ull;
+}
+
+DeviceKernels device_kernels(int device)
+{
+	DeviceKernels dk;
+	if (const AsmModule::Loaded *h = rtk_packet_module().on(device)) {
+		for (int k = 0; k < NUM_PACKET_KERNELS; k++) {
+			dk.packet[k] = h->fn[k] != nullptr;
+			dk.packet_blocks_per_cu[k] = h->blocks_per_cu[k > (int)PacketKernel::Beam2 ? (int)PacketKernel::Beam2 : k];
+		}
+	}
+	if (const AsmModule::Loaded *h = rtk_lane_module().on(device)) {
+		dk.lane = h->fn[0] && h->fn[1];
+		dk.lane_blocks_per_cu = h->blocks_per_cu[0];
+	}
+	return dk;
+}
+
+// A scratch buffer of (scene, stream) that holds `need` units in `bytes` bytes, grown on demand.
+int grow(void **ptr, size_t *capacity, size_t need, size_t bytes, hipStream_t stream)
+{
+	if (*capacity >= need) return RTK_AMD_OK;
+	// an earlier launch on this stream may still be using the old area
+	if (*ptr) { RTK_HIP_CHECK(hipStreamSynchronize(stream), RTK_AMD_ERR_HIP); (void)hipFree(*ptr); }
+	*ptr = nullptr;
+	*capacity = 0;
+	RTK_HIP_CHECK(hipMalloc(ptr, bytes), RTK_AMD_ERR_OOM);
+	*capacity = need;
+	return RTK_AMD_OK;
+}
+
+int grow_scratch(LaunchScratch *sc, const TracePlan &plan, size_t n, hipStream_t stream)
+{
+	int rc = RTK_AMD_OK;
+	if (plan.spill_cap && (sc->spill_lanes < plan.spill_lanes || sc->spill_entries_per_lane < plan.spill_cap)) {
+		sc->spill_lanes = sc->spill_entries_per_lane = 0;       // (two measures: made anew when either is short)
+		rc = grow((void **)&sc->d_spill, &sc->spill_lanes, plan.spill_lanes, plan.spill_lanes * plan.spill_cap * sizeof(uint2), stream);
+		if (rc == RTK_AMD_OK) sc->spill_entries_per_lane = plan.spill_cap;
+	}
+	// [words_a | words_b] 8 B each, bounds 6 words + sort scratch
+	if (rc == RTK_AMD_OK && plan.sort_rays) rc = grow(&sc->d_sort, &sc->sort_capacity, n, n * 16 + (rtk_sort_scratch_words((uint32_t)n) + 16) * 4, stream);
+	if (rc == RTK_AMD_OK && plan.entries) {
+		const size_t nblk = (size_t)(plan.image_w >> 6) * (plan.image_h >> 6);
+		rc = grow(&sc->d_entries, &sc->entries_capacity, nblk, nblk * sizeof(PkBlockEntries), stream);
+	}
+	// one list serves both hand-overs: tile numbers (4 bytes each) or one 8-byte word per left-over ray
+	const size_t left_bytes = plan.hot ? (n >> 6) * sizeof(uint32_t) : plan.lane_hot ? n * sizeof(unsigned long long) : 0;
+	if (rc == RTK_AMD_OK) rc = grow((void **)&sc->d_leftover, &sc->leftover_capacity, left_bytes, left_bytes, stream);
+	return rc;
+}
+
+// optional ray reordering pre-pass (per-lane kernels only): *perm = the order to trace the rays in
+int enqueue_sort(const rtk_dev_scene *ds, LaunchScratch *sc, const rtk_ray *d_rays, size_t n, const TraceKnobs &knobs, hipStream_t stream, const unsigned long long **perm)
+{
+	const uint32_t n32 = (uint32_t)n;
+	unsigned long long *keys_a = (unsigned long long *)sc->d_sort, *keys_b = keys_a + sc->sort_capacity;
+	uint32_t *bounds = (uint32_t *)(keys_b + sc->sort_capacity), *scratch = bounds + 16;
+	const uint32_t cell_bits = knobs.sort_cell_bits, with_octant = knobs.sort_octant;
+	if (knobs.sort_key && ds->view.num_nodes) {
+		hipLaunchKernelGGL(rtk_ray_entry_keys_kernel, dim3((n32 + 255u) / 256u), dim3(256), 0, stream, d_rays, n32, ds->view.nodes, keys_a,
+			cell_bits, with_octant);
+	} else {
+		static const uint32_t init[6] = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u };
+		RTK_HIP_CHECK(hipMemcpyAsync(bounds, init, sizeof(init), hipMemcpyHostToDevice, stream), RTK_AMD_ERR_HIP);
+		hipLaunchKernelGGL(rtk_ray_bounds_kernel, dim3((unsigned)(ds->num_cus * 2)), dim3(256), 0, stream, d_rays, (unsigned long long)n,
+			(unsigned long long)(n >= (1u << 16) ? 61 : 1), bounds);
+		hipLaunchKernelGGL(rtk_ray_keys_kernel, dim3((n32 + 255u) / 256u), dim3(256), 0, stream, d_rays, n32, bounds, keys_a,
+			cell_bits, with_octant);
+	}
+	// one 8-byte word per ray (key over the ray's number), no value array: two passes of 16 B per ray
+	const bool in_b = rtk_sort_words_async(keys_a, keys_b, n32, 32u, 32u + 3u * cell_bits + (with_octant ? 3u : 0u), scratch, stream);
+	*perm = in_b ? keys_b : keys_a;
+	return RTK_AMD_OK;
+}
+
+// The four ways a batch is traced. `p` is complete; each enqueues on `stream` and leaves launch errors to the caller's hipGetLastError.
+
+// a hand-written packet kernel, then the C++ kernel on the tiles it handed back (mixed signs or axes, untame rays, a big leaf, a deep stack)
+int enqueue_packet_hot(const rtk_dev_scene *ds, LaunchScratch *sc, TraceParams &p, const TracePlan &plan, bool any_hit, bool pk_counted, hipStream_t stream)
+{
+	const size_t tiles = (size_t)p.n >> 6;
+	PkHotParams hp = {};
+	hp.nodes = p.sc.nodes; hp.tris = p.sc.tris; hp.rays = p.rays; hp.hits = any_hit ? reinterpret_cast<rtk_hit_record *>(p.occluded) : p.hits; hp.counter = p.counter; hp.leftover = sc->d_leftover;
+	hp.num_blocks = (uint32_t)(tiles >> 6);
+	hp.image_w = p.image_w;
+	hp.blocks_per_row = p.image_w >> 6;
+	hp.bpr_magic = (uint32_t)((0x100000000ull + hp.blocks_per_row - 1u) / hp.blocks_per_row);
+	hp.bound_abs = ds->bound_abs > 1.0f ? ds->bound_abs : 1.0f;
+	hp.entries = p.entries;
+	const int rc = rtk_packet_module().launch(ds->device, (int)plan.kernel, &hp, sizeof(hp), (unsigned)plan.hot_grid, stream);
+	if (rc != RTK_AMD_OK) return rc;
+	// (a small grid: the list is empty for most batches, and a launch that only finds that out should cost next to nothing)
+	p.tile_list = sc->d_leftover;
+	const size_t left_blocks = std::min<size_t>(plan.grid, (size_t)ds->num_cus * 2u);
+	rtk_packet_launch(p, (unsigned)left_blocks, stream, pk_counted);      // (counting: the handed-back tiles' steps are counted too)
+	return RTK_AMD_OK;
+}
+
+// a hand-written per-lane kernel, then rtk_trace_kernel on the rays it left over
+int enqueue_lane_hot(const rtk_dev_scene *ds, LaunchScratch *sc, const TraceParams &p, const TracePlan &plan, bool any_hit, bool refill_given,
+	const TraceKnobs &knobs, hipStream_t stream)
+{
+	LnHotParams hp = {};
+	hp.qnodes = p.sc.qnodes; hp.tris = p.sc.tris; hp.rays = p.rays;
+	hp.out = any_hit ? (void *)p.occluded : (void *)p.hits;
+	hp.counter = p.counter;
+	hp.leftover = reinterpret_cast<unsigned long long *>(sc->d_leftover);
+	hp.perm = p.perm;
+	hp.n = (uint32_t)p.n;
+	// (re-swept for these kernels: refill at 16 idle lanes instead of 8 is +1 % / +2 %, profiles/r04_lane_sweep.log)
+	hp.refill_min = refill_given ? p.refill_min : 16u;
+	hp.node_exit = p.node_exit;
+	hp.bound_abs = ds->bound_raw;             // (no floor of 1: these kernels test child words, not inverted boxes)
+	hp.spill = p.spill;
+	hp.spill_stride = p.spill_stride;
+	hp.spill_cap = p.spill_cap;
+	const int rc = rtk_lane_module().launch(ds->device, any_hit ? 1 : 0, &hp, sizeof(hp), (unsigned)plan.lane_grid, stream);
+	if (rc != RTK_AMD_OK) return rc;
+	if (knobs.lane_stats) {           // (diagnostics: how many rays the assembly kernel handed back; synchronises the stream)
+		unsigned long long left = 0;
+		(void)hipMemcpyAsync(&left, p.counter + RTK_LANE_LEFTOVER_WORD, sizeof(left), hipMemcpyDeviceToHost, stream);
+		(void)hipStreamSynchronize(stream);
+		fprintf(stderr, "rtk_lane_hot: %llu of %zu rays handed back (%.3f %%)\n", left, (size_t)p.n, 100.0 * (double)left / (double)p.n);
+	}
+	// (none in most batches: a small grid that finds an empty list costs next to nothing)
+	TraceParams lp = p;
+	lp.perm = hp.leftover;
+	lp.n_indirect = p.counter + RTK_LANE_LEFTOVER_WORD;
+	lp.n = 0;
+	const size_t left_blocks = std::min<size_t>(plan.grid, (size_t)ds->num_cus);
+	hipLaunchKernelGGL(trace_variant(plan.variant), dim3((unsigned)left_blocks), dim3(BLOCK_THREADS), 0, stream, lp);
+	return RTK_AMD_OK;
+}
+
+int read_packet_counters(LaunchScratch *sc, size_t n, hipStream_t stream, rtk_packet_counters *out)
+{
+	unsigned long long c[16];
+	RTK_HIP_CHECK(hipMemcpyAsync(c, sc->d_counter, sizeof(c), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
+	RTK_HIP_CHECK(hipStreamSynchronize(stream), RTK_AMD_ERR_HIP);
+	out->pairs = c[11]; out->node_steps = c[12]; out->triangles_fetched = c[13]; out->triangle_group_tests = c[14];
+	out->tiles_handed_back = c[RTK_LEFTOVER_COUNT_WORD];
+	out->handed_back_node_steps = c[7]; out->handed_back_triangle_steps = c[8];
+	out->tiles = n >> 6;
+	return RTK_AMD_OK;
+}
+
+int read_counters(LaunchScratch *sc, hipStream_t stream, rtk_trace_counters *out)
+{
+	unsigned long long c[16], err = 0;
+	RTK_HIP_CHECK(hipMemcpyAsync(c, sc->d_counter, sizeof(c), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
+	RTK_HIP_CHECK(hipMemcpyAsync(&err, sc->d_counter + RTK_ERROR_WORD, sizeof(err), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
+	RTK_HIP_CHECK(hipStreamSynchronize(stream), RTK_AMD_ERR_HIP);
+	out->rays = c[1]; out->nodes = c[2]; out->leaves = c[3];
+	out->triangles = c[4]; out->hits = c[5]; out->stack_spills = c[6];
+	out->wave_node_steps = c[7]; out->wave_triangle_steps = c[8]; out->wave_rays = c[9];
+	if (err) {
+		(void)hipMemsetAsync(sc->d_counter + RTK_ERROR_WORD, 0, sizeof(err), stream);
+		rtk_set_error("rtk_dev_trace: traversal stack overflow (corrupted scene)");
+		return RTK_AMD_ERR_BAD_SCENE;
+	}
+	return RTK_AMD_OK;
+}
+
+} // namespace
+
 int rtk_launch_trace(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, size_t n, rtk_hit_record *d_hits,
 	uint8_t *d_occluded, const rtk_trace_opts *opts, hipStream_t stream, bool any_hit, rtk_trace_counters *counted,
 	const rtk_dev_filter *filter, rtk_hit_record *d_cand, uint32_t *d_cand_count, uint32_t cand_k, rtk_packet_counters *pk_counted)
@@ -1075,21 +1272,11 @@ int rtk_launch_trace(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, size_t n,
 	if (collect && (!d_cand_count || cand_k == 0 || any_hit || counted)) { rtk_set_error("rtk_dev_trace: bad collect arguments"); return RTK_AMD_ERR_BAD_ARG; }
 	if (!ds || (!d_rays && n) || (!collect && (any_hit ? !d_occluded : !d_hits) && n)) { rtk_set_error("rtk_dev_trace: bad argument"); return RTK_AMD_ERR_BAD_ARG; }
 	if (n == 0) { if (counted) *counted = rtk_trace_counters(); return RTK_AMD_OK; }
-	{
-		// the scene's memory, its scratch and `stream` must all belong to the device this thread has current: a launch from a
-		// thread on another GPU would read the scene across devices (a fault without peer access)
-		int cur = -1;
-		if (hipGetDevice(&cur) != hipSuccess || cur != ds->device) {
-			rtk_set_error("rtk_dev_trace: the scene lives on device %d, the calling thread's current device is %d", ds->device, cur);
-			return RTK_AMD_ERR_BAD_ARG;
-		}
-	}
-	// the kernel addresses nodes and triangles as SGPR base + 32-bit byte offset
-	if ((uint64_t)ds->view.num_nodes * 128u > 0xffffff00ull || (uint64_t)ds->view.num_tris * RTK_TRI_STRIDE > 0xffffff00ull) {
+	if (!on_scene_device(ds, "rtk_dev_trace")) return RTK_AMD_ERR_BAD_ARG;
+	if (!within_4gib(ds->view)) {
 		rtk_set_error("rtk_dev_trace: scene exceeds 4 GiB of nodes or triangles (%u nodes, %u triangles)", ds->view.num_nodes, ds->view.num_tris);
 		return RTK_AMD_ERR_UNSUPPORTED;
 	}
-
 	TraceParams p = {};
 	p.sc = ds->view;
 	p.rays = d_rays;
@@ -1099,47 +1286,6 @@ int rtk_launch_trace(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, size_t n,
 	p.cand_count = d_cand_count;
 	p.cand_k = cand_k;
 	p.n = n;
-	p.dynamic = n > BLOCK_THREADS ? 1u : 0u;      // a batch that fits one workgroup needs no work queue (and no counter reset)
-	// Defaults from sweeps on MI355X (profiles/r01_sweep_opts*.log, r02_ab_r2o/p.log): leave the node
-	// loop once fewer than 32 lanes still descend (24 for image-shaped batches); image-shaped (tiled, coherent)
-	// batches refill a wave only when it is empty, everything else as soon as 8 lanes are idle.
-	p.refill_min = 8;
-	p.node_exit = 32;
-	uint32_t blocks_per_cu = 0;
-	if (opts && opts->struct_size >= 16) {
-		if (opts->flags & RTK_TRACE_STATIC) p.dynamic = 0;
-		if (opts->image_width && opts->image_height && (size_t)opts->image_width * opts->image_height == n &&
-			(opts->image_width % 8u) == 0 && (opts->image_height % 8u) == 0) {
-			p.image_w = opts->image_width;
-			p.image_h = opts->image_height;
-			p.refill_min = 64;
-			p.node_exit = 24;
-		}
-		if (opts->struct_size >= 24) {
-			if (opts->refill_min) p.refill_min = opts->refill_min > 64 ? 64 : opts->refill_min;
-			blocks_per_cu = opts->blocks_per_cu;
-		}
-		if (opts->struct_size >= 28 && opts->node_exit) p.node_exit = opts->node_exit > 64 ? 64 : opts->node_exit;
-	}
-	// No image hint: is the batch an image anyway? Only worth asking where the packet kernels would take it (a closest-hit or any-hit
-	// batch without filters, whole 64x64-pixel blocks); costs two small launches and one wait for `stream` (~20 us; the wait also
-	// stands between this batch and the host's next enqueue: a caller that knows its image says so in the options).
-	static const int detect_default = getenv("RTK_AMD_DETECT_IMAGE") ? atoi(getenv("RTK_AMD_DETECT_IMAGE")) : 1;
-	if (detect_default != 0 && p.image_w == 0 && !filter && !collect && !counted && !pk_counted && n >= 16384u && (n % 4096u) == 0u && n <= 0x40000000ull &&
-		p.dynamic && ds->stack_entries <= 64 && !(opts && opts->struct_size >= 16 && (opts->flags & (RTK_TRACE_NO_DETECT | RTK_TRACE_NO_PACKET | RTK_TRACE_SORT_RAYS | RTK_TRACE_STATIC)))) {
-		uint32_t w = 0, h = 0;
-		const int rc = rtk_detect_image(ds, d_rays, n, stream, &w, &h);
-		if (rc != RTK_AMD_OK) return rc;
-		if (w >= 128u && (w % 64u) == 0u && (h % 64u) == 0u) {
-			p.image_w = w;
-			p.image_h = h;
-			p.refill_min = 64;
-			p.node_exit = 24;
-		}
-	}
-	static const int tile_blocks_default = getenv("RTK_AMD_TILE_BLOCKS") ? atoi(getenv("RTK_AMD_TILE_BLOCKS")) : 1;
-	p.tile_blocks = (tile_blocks_default && p.image_w && p.image_w % 64u == 0 && p.image_h % 64u == 0) ? 1u : 0u;
-	bool filtered = false;
 	if (filter) {
 		if (filter->struct_size < sizeof(rtk_dev_filter)) { rtk_set_error("rtk_dev_trace: rtk_dev_filter.struct_size is too small"); return RTK_AMD_ERR_BAD_ARG; }
 		if (filter->d_mesh_mask && filter->mesh_mask_bits == 0) { rtk_set_error("rtk_dev_trace: mesh mask without mesh_mask_bits"); return RTK_AMD_ERR_BAD_ARG; }
@@ -1147,235 +1293,62 @@ int rtk_launch_trace(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, size_t n,
 		p.mesh_mask_bits = filter->mesh_mask_bits;
 		p.ignore_prim = filter->d_ignore_prim;
 		p.after = filter->d_after;
-		filtered = p.mesh_mask || p.ignore_prim || p.after;
 	}
 
-	// image-shaped closest-hit batches go to the wave-packet kernels (rtk_trace_packet.hip). So do image-shaped ANY-HIT batches of
-	// whole 64x64-pixel blocks: "is there a hit in (min_t, max_t)" is what a closest-hit traversal answers, at several times the rate of
-	// a ray per lane where the rays run side by side (coherent shadow / visibility rays); rtk_packet_any2 retires a ray at its first
-	// hit and writes the flags, the C++ kernel (the tiles handed back) writes "the closest hit exists". RTK_AMD_ANY_PACKETS=0: per lane.
-	static const int any_packets_default = getenv("RTK_AMD_ANY_PACKETS") ? atoi(getenv("RTK_AMD_ANY_PACKETS")) : 1;
-	const bool any_packet = any_hit && any_packets_default != 0 && !counted && p.image_w >= 128u && (p.image_w % 64u) == 0u && (p.image_h % 64u) == 0u &&
-		!(opts && opts->struct_size >= 16 && (opts->flags & (RTK_TRACE_SORT_RAYS | RTK_TRACE_STATIC)));
-	const bool packet = (!any_hit || any_packet) && !filtered && !collect && p.image_w != 0 && ds->stack_entries <= 64 && !(opts && (opts->flags & RTK_TRACE_NO_PACKET));
-	// per-lane kernels read the 64 B compressed nodes unless told otherwise (A/B, and tests that compare the two)
-	static const int qnodes_default = getenv("RTK_AMD_QNODES") ? atoi(getenv("RTK_AMD_QNODES")) : 1;
-	const bool qn = ds->view.qnodes != nullptr && qnodes_default != 0 && !(opts && opts->struct_size >= 16 && (opts->flags & RTK_TRACE_EXACT_NODES));
-	const int variant = packet ? (counted ? VARIANT_PACKET_COUNTED : VARIANT_PACKET) : collect ? VARIANT_COLLECT + (qn ? 1 : 0)
-		: ((any_hit ? 1 : 0) | (counted ? 2 : 0) | (filtered ? 4 : 0) | (qn ? 8 : 0));
-	// ... and of those, the hand-written kernel (rtk_packet_hot.S) takes every tile it can and hands the rest to the C++ kernel:
-	// whole 64x64-pixel blocks, at least two per row, a scene whose planes bound the slab margins and whose leaves are small
-	static const int asm_default = getenv("RTK_AMD_PACKET_ASM") ? atoi(getenv("RTK_AMD_PACKET_ASM")) : 1;
-	// RTK_AMD_PACKET_BEAM (default 2): 2 = rtk_packet_beam2 (two tiles per wave), 1 = rtk_packet_beam, 0 = rtk_packet_hot (the
-	// per-lane slab tests); A/B and tests
-	static const int beam_default = getenv("RTK_AMD_PACKET_BEAM") ? atoi(getenv("RTK_AMD_PACKET_BEAM")) : 2;
-	int beam = (opts && opts->struct_size >= 16 && (opts->flags & RTK_TRACE_NO_BEAM)) ? 0 : beam_default;
-	if (opts && opts->struct_size >= 16 && (opts->flags & RTK_TRACE_ONE_TILE_BEAM) && beam == 2) beam = 1;
-	while (beam > 0 && !rtk_packet_hot_available(ds->device, nullptr, beam)) beam--;
-	// the counting form of the kernel that is timed (rtk_packet_count2 = rtk_packet_beam2.S with -DRTK_COUNT): only where that kernel runs
-	if (any_hit && packet) beam = (beam == 2 && rtk_packet_hot_available(ds->device, nullptr, 4)) ? 4 : -1;     // (the any-hit form exists of rtk_packet_beam2 only; -1: the C++ kernel)
-	if (pk_counted) {
-		if (beam != 2 || !rtk_packet_hot_available(ds->device, nullptr, 3)) { rtk_set_error("rtk_dev_trace_rays_packet_counted: rtk_packet_beam2 is not the kernel of this launch"); return RTK_AMD_ERR_UNSUPPORTED; }
-		beam = 3;
+	// what is asked, of which scene, on which device: the plan (rtk_trace_plan.h)
+	const TraceKnobs &knobs = rtk_trace_knobs();
+	const TraceOpts o = decode_opts(opts);
+	TraceRequest rq;
+	rq.n = n; rq.any_hit = any_hit; rq.counted = counted != nullptr; rq.pk_counted = pk_counted != nullptr; rq.collect = collect;
+	rq.filtered = p.mesh_mask || p.ignore_prim || p.after; rq.has_filter = filter != nullptr;
+	SceneFacts facts;
+	facts.num_nodes = ds->view.num_nodes; facts.num_tris = ds->view.num_tris; facts.has_qnodes = ds->view.qnodes != nullptr;
+	facts.stack_entries = ds->stack_entries; facts.bound_abs = ds->bound_abs; facts.big_leaf_fraction = ds->big_leaf_fraction;
+	facts.num_cus = ds->num_cus; facts.tri_stride = RTK_TRI_STRIDE;
+	uint32_t look_w = 0, look_h = 0;
+	if (wants_image_look(rq, o, facts, knobs)) {
+		const int rc = rtk_detect_image(ds, d_rays, n, stream, &look_w, &look_h);
+		if (rc != RTK_AMD_OK) return rc;
 	}
-	int hot_blocks_per_cu = 0;
-	const bool hot = packet && beam >= 0 && !counted && asm_default != 0 && p.tile_blocks && p.image_w >= 128u && p.image_w <= 65536u && n <= 0x40000000ull &&
-		ds->bound_abs < 0x1p19f && (beam >= 2 || ds->big_leaf_fraction <= 0.02) && !(opts && (opts->flags & RTK_TRACE_NO_ASM)) &&
-		rtk_packet_hot_available(ds->device, &hot_blocks_per_cu, beam);       // (rtk_packet_beam2 has the group rule for leaves of four and more triangles; the one-tile kernels hand such tiles back)
-	if (pk_counted && !hot) { rtk_set_error("rtk_dev_trace_rays_packet_counted: this batch does not run on the assembly packet kernel (image hint, whole 64x64-pixel blocks, small leaves)"); return RTK_AMD_ERR_UNSUPPORTED; }
-	static const bool path_log = getenv("RTK_AMD_LOG_PATH") != nullptr;
-	if (path_log) fprintf(stderr, "rtk_dev_trace: n %zu image %u x %u packet %d hot %d beam %d opts %p flags %x\n", n, p.image_w, p.image_h, (int)packet, (int)hot, beam, (const void *)opts, opts ? opts->flags : 0u);
-	const int occ = blocks_per_cu_of(ds->device, variant);
-	if (blocks_per_cu == 0 || blocks_per_cu > (uint32_t)occ) blocks_per_cu = (uint32_t)occ;
-	// Plain closest-hit / any-hit batches on compressed nodes go to the hand-written per-lane kernels (rtk_lane_hot.S); the rays
-	// they hand back (not tame, a leaf of four or more triangles, a stack deeper than the LDS column) follow in rtk_trace_kernel.
-	// Byte offsets into nodes, triangles, rays and the ray order are 32-bit and kept below 2^31 there.
-	static const int lane_asm_default = getenv("RTK_AMD_LANE_ASM") ? atoi(getenv("RTK_AMD_LANE_ASM")) : 1;
-	int lane_blocks_per_cu = 0;
-	const bool lane_hot = !packet && !collect && !counted && !filtered && qn && p.dynamic && p.image_w == 0 && lane_asm_default != 0 &&
-		RTK_TRI_STRIDE == 48 && n <= ((size_t)1 << 26) && (uint64_t)ds->view.num_nodes * 64u < 0x80000000ull &&
-		(uint64_t)ds->view.num_tris * RTK_TRI_STRIDE < 0x80000000ull && ds->bound_abs < 0x1p60f && (!any_hit || ds->big_leaf_fraction <= 0.02) &&
-		!(opts && opts->struct_size >= 16 && (opts->flags & (RTK_TRACE_NO_ASM | RTK_TRACE_STATIC))) && ds->stack_entries < 512u &&
-		rtk_lane_hot_available(ds->device, &lane_blocks_per_cu);
-
-	const size_t blocks_needed = (n + BLOCK_THREADS - 1) / BLOCK_THREADS;
-	size_t blocks = (p.dynamic || packet) ? (size_t)ds->num_cus * blocks_per_cu : blocks_needed;
-	if (blocks > blocks_needed) blocks = blocks_needed;
-	if (blocks > 0x7fffffffu) { rtk_set_error("rtk_dev_trace: batch too large for one launch"); return RTK_AMD_ERR_BAD_ARG; }
+	const DeviceKernels kernels = device_kernels(ds->device);
+	const int occ = blocks_per_cu_of(ds->device, variant_of(rq, o, look_w, look_h, facts, kernels, knobs));
+	const TracePlan plan = plan_trace(rq, o, look_w, look_h, facts, kernels, knobs, occ);
+	if (plan.error != RTK_AMD_OK) { rtk_set_error("%s", plan.message); return plan.error; }
+	if (knobs.log_path) fprintf(stderr, "rtk_dev_trace: n %zu image %u x %u packet %d hot %d beam %d opts %p flags %x\n", n, plan.image_w, plan.image_h, (int)plan.packet, (int)plan.hot, (int)plan.kernel, (const void *)opts, o.flags);
+	p.dynamic = plan.dynamic;
+	p.refill_min = plan.refill_min;
+	p.node_exit = plan.node_exit;
+	p.image_w = plan.image_w;
+	p.image_h = plan.image_h;
+	p.tile_blocks = plan.tile_blocks;
 
 	// From here on the launch uses the scratch set of (scene, stream); the mutex is held until everything is
 	// enqueued, so that two host threads feeding one stream cannot interleave "reset queue heads" and "launch".
 	std::lock_guard<std::mutex> lock(ds->scratch_mutex);
 	LaunchScratch *sc = scratch_for(ds, stream);
 	if (!sc) return RTK_AMD_ERR_OOM;
-
-	// spill area for rays whose stack outgrows LDS
-	size_t lane_hot_blocks = (size_t)ds->num_cus * (size_t)lane_blocks_per_cu;
-	if (lane_hot_blocks > blocks_needed) lane_hot_blocks = blocks_needed;
-	const size_t lanes = (lane_hot && lane_hot_blocks > blocks ? lane_hot_blocks : blocks) * BLOCK_THREADS;     // (one spill area serves the assembly kernel and the C++ pass behind it)
-	static const size_t lane_lds = getenv("RTK_AMD_LANE_LDS") ? (size_t)atoi(getenv("RTK_AMD_LANE_LDS")) : LDS_STACK;   // (A/B builds of rtk_lane_hot.S with fewer LDS entries)
-	const size_t lds_entries = packet ? 16 : (lane_hot && lane_lds < LDS_STACK) ? lane_lds : LDS_STACK;   // PK_LDS_STACK in rtk_trace_packet.hip
-	const size_t spill_cap = ds->stack_entries > lds_entries ? ds->stack_entries - lds_entries : 0;
-	if (spill_cap && (sc->spill_lanes < lanes || sc->spill_entries_per_lane < spill_cap)) {
-		// an earlier launch on this stream may still be using the old area
-		if (sc->d_spill) { RTK_HIP_CHECK(hipStreamSynchronize(stream), RTK_AMD_ERR_HIP); (void)hipFree(sc->d_spill); }
-		sc->d_spill = nullptr;
-		sc->spill_lanes = sc->spill_entries_per_lane = 0;
-		RTK_HIP_CHECK(hipMalloc(&sc->d_spill, lanes * spill_cap * sizeof(uint2)), RTK_AMD_ERR_OOM);
-		sc->spill_lanes = lanes;
-		sc->spill_entries_per_lane = spill_cap;
-	}
-	// optional ray reordering pre-pass (per-lane kernels only)
-	p.perm = nullptr;
-	if (!packet && opts && (opts->flags & RTK_TRACE_SORT_RAYS) && n < 0x7fffffffu) {
-		const uint32_t n32 = (uint32_t)n;
-		const size_t words = rtk_sort_scratch_words(n32);
-		if (sc->sort_capacity < n) {
-			if (sc->d_sort) { RTK_HIP_CHECK(hipStreamSynchronize(stream), RTK_AMD_ERR_HIP); (void)hipFree(sc->d_sort); }
-			sc->d_sort = nullptr;
-			sc->sort_capacity = 0;
-			// [words_a | words_b] 8 B each, bounds 6 words + sort scratch
-			RTK_HIP_CHECK(hipMalloc(&sc->d_sort, n * 16 + (words + 16) * 4), RTK_AMD_ERR_OOM);
-			sc->sort_capacity = n;
-		}
-		unsigned long long *keys_a = (unsigned long long *)sc->d_sort, *keys_b = keys_a + sc->sort_capacity;
-		uint32_t *bounds = (uint32_t *)(keys_b + sc->sort_capacity), *scratch = bounds + 16;
-		static const uint32_t cell_bits = getenv("RTK_AMD_SORT_CELL_BITS") ? (uint32_t)atoi(getenv("RTK_AMD_SORT_CELL_BITS")) : 7u;   // 2^7 cells per axis: 3.44 against 3.32 Grays/s at 2^5 on the shadow batch (profiles/r03_ab_sort_cells.log)
-		static const uint32_t with_octant = getenv("RTK_AMD_SORT_OCTANT") ? (uint32_t)atoi(getenv("RTK_AMD_SORT_OCTANT")) : 0u;
-		static const int entry_key = getenv("RTK_AMD_SORT_KEY") ? atoi(getenv("RTK_AMD_SORT_KEY")) : 1;   // 0: origin cell in the batch's origin bounds
-		if (entry_key && ds->view.num_nodes) {
-			hipLaunchKernelGGL(rtk_ray_entry_keys_kernel, dim3((n32 + 255u) / 256u), dim3(256), 0, stream, d_rays, n32, ds->view.nodes, keys_a,
-				cell_bits, with_octant);
-		} else {
-			static const uint32_t init[6] = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u };
-			RTK_HIP_CHECK(hipMemcpyAsync(bounds, init, sizeof(init), hipMemcpyHostToDevice, stream), RTK_AMD_ERR_HIP);
-			hipLaunchKernelGGL(rtk_ray_bounds_kernel, dim3((unsigned)(ds->num_cus * 2)), dim3(256), 0, stream, d_rays, (unsigned long long)n,
-				(unsigned long long)(n >= (1u << 16) ? 61 : 1), bounds);
-			hipLaunchKernelGGL(rtk_ray_keys_kernel, dim3((n32 + 255u) / 256u), dim3(256), 0, stream, d_rays, n32, bounds, keys_a,
-				cell_bits, with_octant);
-		}
-		// one 8-byte word per ray (key over the ray's number), no value array: two passes of 16 B per ray
-		const bool in_b = rtk_sort_words_async(keys_a, keys_b, n32, 32u, 32u + 3u * cell_bits + (with_octant ? 3u : 0u), scratch, stream);
-		p.perm = in_b ? keys_b : keys_a;
-	}
+	int rc = grow_scratch(sc, plan, n, stream);
+	if (rc != RTK_AMD_OK) return rc;
 	p.spill = sc->d_spill;
-	p.spill_stride = (uint32_t)(spill_cap ? sc->spill_lanes : 0);
-	p.spill_cap = (uint32_t)spill_cap;
+	p.spill_stride = (uint32_t)(plan.spill_cap ? sc->spill_lanes : 0);
+	p.spill_cap = (uint32_t)plan.spill_cap;
 	p.counter = sc->d_counter;
-
-	// entry points shared by the tiles of a 64x64-pixel block (rtk_packet_entries_kernel, one small launch ahead of the traversal)
-	static const int entries_default = getenv("RTK_AMD_PACKET_ENTRIES") ? atoi(getenv("RTK_AMD_PACKET_ENTRIES")) : 1;
-	static const unsigned entries_target = getenv("RTK_AMD_ENTRY_TARGET") ? (unsigned)atoi(getenv("RTK_AMD_ENTRY_TARGET")) : 26u;   // (list size at which the walk stops: 20 / 24 / 28 / 32 / 36 -> 17.7 / 18.0 / 18.0 / 17.9 / 17.85 Grays/s on config 2, profiles/r04_packet_entries.log)
-	static const unsigned entries_levels = getenv("RTK_AMD_ENTRY_LEVELS") ? (unsigned)atoi(getenv("RTK_AMD_ENTRY_LEVELS")) : 8u;
-	const bool entries = packet && p.tile_blocks && entries_default != 0 && ds->bound_abs < 0x1p19f && ds->view.num_nodes != 0u &&
-		!(opts && opts->struct_size >= 16 && (opts->flags & RTK_TRACE_NO_ENTRIES));
+	if (plan.sort_rays && (rc = enqueue_sort(ds, sc, d_rays, n, knobs, stream, &p.perm)) != RTK_AMD_OK) return rc;
 	// queue heads and visit counters start from zero; a one-block static launch uses neither. (With entry lists the pre-pass
 	// kernel clears them itself: a 4.6 us fill kernel and its launch gap less per frame.)
-	if ((p.dynamic || packet || counted) && !entries) RTK_HIP_CHECK(hipMemsetAsync(sc->d_counter, 0, RTK_COUNTER_WORDS * sizeof(unsigned long long), stream), RTK_AMD_ERR_HIP);
-	if (entries) {
-		const size_t nblk = (size_t)(p.image_w >> 6) * (p.image_h >> 6);
-		if (sc->entries_capacity < nblk) {
-			if (sc->d_entries) { RTK_HIP_CHECK(hipStreamSynchronize(stream), RTK_AMD_ERR_HIP); (void)hipFree(sc->d_entries); }
-			sc->d_entries = nullptr;
-			sc->entries_capacity = 0;
-			RTK_HIP_CHECK(hipMalloc(&sc->d_entries, nblk * sizeof(PkBlockEntries)), RTK_AMD_ERR_OOM);
-			sc->entries_capacity = nblk;
-		}
-		rtk_packet_entries_launch(p, (PkBlockEntries *)sc->d_entries, ds->bound_abs > 1.0f ? ds->bound_abs : 1.0f, entries_target, entries_levels, stream);
+	if ((plan.dynamic || plan.packet || counted) && !plan.entries) RTK_HIP_CHECK(hipMemsetAsync(sc->d_counter, 0, RTK_COUNTER_WORDS * sizeof(unsigned long long), stream), RTK_AMD_ERR_HIP);
+	if (plan.entries) {
+		rtk_packet_entries_launch(p, (PkBlockEntries *)sc->d_entries, ds->bound_abs > 1.0f ? ds->bound_abs : 1.0f, knobs.entry_target, knobs.entry_levels, stream);
 		p.entries = (const PkBlockEntries *)sc->d_entries;
 	}
-	if (hot) {
-		const size_t tiles = n >> 6;
-		if (sc->leftover_capacity < tiles) {
-			if (sc->d_leftover) { RTK_HIP_CHECK(hipStreamSynchronize(stream), RTK_AMD_ERR_HIP); (void)hipFree(sc->d_leftover); }
-			sc->d_leftover = nullptr;
-			sc->leftover_capacity = 0;
-			RTK_HIP_CHECK(hipMalloc(&sc->d_leftover, tiles * sizeof(uint32_t)), RTK_AMD_ERR_OOM);
-			sc->leftover_capacity = tiles;
-		}
-		PkHotParams hp = {};
-		hp.nodes = p.sc.nodes; hp.tris = p.sc.tris; hp.rays = p.rays; hp.hits = any_hit ? reinterpret_cast<rtk_hit_record *>(p.occluded) : p.hits; hp.counter = p.counter; hp.leftover = sc->d_leftover;
-		hp.num_blocks = (uint32_t)(tiles >> 6);
-		hp.image_w = p.image_w;
-		hp.blocks_per_row = p.image_w >> 6;
-		hp.bpr_magic = (uint32_t)((0x100000000ull + hp.blocks_per_row - 1u) / hp.blocks_per_row);
-		hp.bound_abs = ds->bound_abs > 1.0f ? ds->bound_abs : 1.0f;
-		hp.entries = p.entries;
-		// (RTK_AMD_HOT_BLOCKS_PER_CU: fewer resident workgroups, to tell a latency-bound kernel from a throughput-bound one)
-		static const int hot_bpc_env = getenv("RTK_AMD_HOT_BLOCKS_PER_CU") ? atoi(getenv("RTK_AMD_HOT_BLOCKS_PER_CU")) : 0;
-		size_t hot_blocks = (size_t)ds->num_cus * (size_t)(hot_bpc_env > 0 && hot_bpc_env < hot_blocks_per_cu ? hot_bpc_env : hot_blocks_per_cu);
-		if (hot_blocks > blocks_needed) hot_blocks = blocks_needed;
-		const int rc = rtk_packet_hot_launch(ds->device, hp, (unsigned)hot_blocks, stream, beam);
-		if (rc != RTK_AMD_OK) return rc;
-		// the tiles it handed back (mixed signs or axes, untame rays, a big leaf, a deep stack), by the C++ kernel
-		// (a small grid: the list is empty for most batches, and a launch that only finds that out should cost next to nothing)
-		p.tile_list = sc->d_leftover;
-		const size_t left_blocks = std::min<size_t>(blocks, (size_t)ds->num_cus * 2u);
-		rtk_packet_launch(p, (unsigned)left_blocks, stream, pk_counted != nullptr);      // (counting: the handed-back tiles' steps are counted too)
-	} else if (packet) rtk_packet_launch(p, (unsigned)blocks, stream, counted != nullptr);
-	else if (lane_hot) {
-		if (sc->leftover_capacity < n * 2u) {           // (counted in uint32: the list holds one 8-byte word per left-over ray)
-			if (sc->d_leftover) { RTK_HIP_CHECK(hipStreamSynchronize(stream), RTK_AMD_ERR_HIP); (void)hipFree(sc->d_leftover); }
-			sc->d_leftover = nullptr;
-			sc->leftover_capacity = 0;
-			RTK_HIP_CHECK(hipMalloc(&sc->d_leftover, n * sizeof(unsigned long long)), RTK_AMD_ERR_OOM);
-			sc->leftover_capacity = n * 2u;
-		}
-		LnHotParams hp = {};
-		hp.qnodes = p.sc.qnodes; hp.tris = p.sc.tris; hp.rays = p.rays;
-		hp.out = any_hit ? (void *)p.occluded : (void *)p.hits;
-		hp.counter = p.counter;
-		hp.leftover = reinterpret_cast<unsigned long long *>(sc->d_leftover);
-		hp.perm = p.perm;
-		hp.n = (uint32_t)n;
-		// (re-swept for these kernels: refill at 16 idle lanes instead of 8 is +1 % / +2 %, profiles/r04_lane_sweep.log)
-		hp.refill_min = (opts && opts->struct_size >= 24 && opts->refill_min) ? p.refill_min : 16u;
-		hp.node_exit = p.node_exit;
-		hp.bound_abs = ds->bound_raw;             // (no floor of 1: these kernels test child words, not inverted boxes)
-		hp.spill = p.spill;
-		hp.spill_stride = p.spill_stride;
-		hp.spill_cap = p.spill_cap;
-		const int rc = rtk_lane_hot_launch(ds->device, hp, (unsigned)lane_hot_blocks, stream, any_hit);
-		if (rc != RTK_AMD_OK) return rc;
-		static const int lane_stats = getenv("RTK_AMD_LANE_STATS") ? atoi(getenv("RTK_AMD_LANE_STATS")) : 0;
-		if (lane_stats) {           // (diagnostics: how many rays the assembly kernel handed back; synchronises the stream)
-			unsigned long long left = 0;
-			(void)hipMemcpyAsync(&left, p.counter + RTK_LANE_LEFTOVER_WORD, sizeof(left), hipMemcpyDeviceToHost, stream);
-			(void)hipStreamSynchronize(stream);
-			fprintf(stderr, "rtk_lane_hot: %llu of %zu rays handed back (%.3f %%)\n", left, n, 100.0 * (double)left / (double)n);
-		}
-		// the rays it left over (none in most batches: a small grid that finds an empty list costs next to nothing)
-		TraceParams lp = p;
-		lp.perm = hp.leftover;
-		lp.n_indirect = p.counter + RTK_LANE_LEFTOVER_WORD;
-		lp.n = 0;
-		const size_t left_blocks = std::min<size_t>(blocks, (size_t)ds->num_cus);
-		hipLaunchKernelGGL(trace_variant(variant), dim3((unsigned)left_blocks), dim3(BLOCK_THREADS), 0, stream, lp);
-	} else hipLaunchKernelGGL(trace_variant(variant), dim3((unsigned)blocks), dim3(BLOCK_THREADS), 0, stream, p);
+	if (plan.hot) rc = enqueue_packet_hot(ds, sc, p, plan, any_hit, pk_counted != nullptr, stream);
+	else if (plan.packet) rtk_packet_launch(p, (unsigned)plan.grid, stream, counted != nullptr);
+	else if (plan.lane_hot) rc = enqueue_lane_hot(ds, sc, p, plan, any_hit, o.refill_given, knobs, stream);
+	else hipLaunchKernelGGL(trace_variant(plan.variant), dim3((unsigned)plan.grid), dim3(BLOCK_THREADS), 0, stream, p);
+	if (rc != RTK_AMD_OK) return rc;
 	RTK_HIP_CHECK(hipGetLastError(), RTK_AMD_ERR_HIP);
-	if (pk_counted) {
-		unsigned long long c[16];
-		RTK_HIP_CHECK(hipMemcpyAsync(c, sc->d_counter, sizeof(c), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
-		RTK_HIP_CHECK(hipStreamSynchronize(stream), RTK_AMD_ERR_HIP);
-		pk_counted->pairs = c[11]; pk_counted->node_steps = c[12]; pk_counted->triangles_fetched = c[13]; pk_counted->triangle_group_tests = c[14];
-		pk_counted->tiles_handed_back = c[RTK_LEFTOVER_COUNT_WORD];
-		pk_counted->handed_back_node_steps = c[7]; pk_counted->handed_back_triangle_steps = c[8];
-		pk_counted->tiles = n >> 6;
-	}
-	if (counted) {
-		unsigned long long c[16], err = 0;
-		RTK_HIP_CHECK(hipMemcpyAsync(c, sc->d_counter, sizeof(c), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
-		RTK_HIP_CHECK(hipMemcpyAsync(&err, sc->d_counter + RTK_ERROR_WORD, sizeof(err), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
-		RTK_HIP_CHECK(hipStreamSynchronize(stream), RTK_AMD_ERR_HIP);
-		counted->rays = c[1]; counted->nodes = c[2]; counted->leaves = c[3];
-		counted->triangles = c[4]; counted->hits = c[5]; counted->stack_spills = c[6];
-		counted->wave_node_steps = c[7]; counted->wave_triangle_steps = c[8]; counted->wave_rays = c[9];
-		if (err) {
-			(void)hipMemsetAsync(sc->d_counter + RTK_ERROR_WORD, 0, sizeof(err), stream);
-			rtk_set_error("rtk_dev_trace: traversal stack overflow (corrupted scene)");
-			return RTK_AMD_ERR_BAD_SCENE;
-		}
-	}
+	if (pk_counted && (rc = read_packet_counters(sc, n, stream, pk_counted)) != RTK_AMD_OK) return rc;
+	if (counted) return read_counters(sc, stream, counted);
 	return RTK_AMD_OK;
 }
 
@@ -1423,13 +1396,7 @@ int rtk_launch_expand(const rtk_dev_scene *ds_c, const rtk_hit_record *d_records
 	rtk_dev_scene *ds = const_cast<rtk_dev_scene *>(ds_c);
 	if (!ds || (!d_records && n)) { rtk_set_error("rtk_dev_expand_hits: bad argument"); return RTK_AMD_ERR_BAD_ARG; }
 	if (n == 0) return RTK_AMD_OK;
-	{
-		int cur = -1;
-		if (hipGetDevice(&cur) != hipSuccess || cur != ds->device) {
-			rtk_set_error("rtk_dev_expand_hits: the scene lives on device %d, the calling thread's current device is %d", ds->device, cur);
-			return RTK_AMD_ERR_BAD_ARG;
-		}
-	}
+	if (!on_scene_device(ds, "rtk_dev_expand_hits")) return RTK_AMD_ERR_BAD_ARG;
 	if (d_hits && rtk_scene_side_arrays(ds, stream) != RTK_AMD_OK) return RTK_AMD_ERR_OOM;
 	const unsigned long long *status_word = nullptr;
 	if (h_status) {
@@ -1452,12 +1419,8 @@ int rtk_launch_trace_one(const rtk_dev_scene *ds, const rtk_ray *d_ray, rtk_hit 
 	unsigned long long *h_status, uint32_t ticket)
 {
 	if (!ds || !d_ray || !d_hit || !d_mask || !h_status || !ticket) { rtk_set_error("rtk_trace_ray: bad argument"); return RTK_AMD_ERR_BAD_ARG; }
-	int cur = -1;
-	if (hipGetDevice(&cur) != hipSuccess || cur != ds->device) {
-		rtk_set_error("rtk_trace_ray: the scene lives on device %d, the calling thread's current device is %d", ds->device, cur);
-		return RTK_AMD_ERR_BAD_ARG;
-	}
-	if ((uint64_t)ds->view.num_nodes * 128u > 0xffffff00ull || (uint64_t)ds->view.num_tris * RTK_TRI_STRIDE > 0xffffff00ull) {
+	if (!on_scene_device(ds, "rtk_trace_ray")) return RTK_AMD_ERR_BAD_ARG;
+	if (!within_4gib(ds->view)) {
 		rtk_set_error("rtk_trace_ray: the one-ray kernel addresses nodes and triangles with 32-bit byte offsets (scene: %u nodes, %u triangles)", ds->view.num_nodes, ds->view.num_tris);
 		return RTK_AMD_ERR_UNSUPPORTED;
 	}

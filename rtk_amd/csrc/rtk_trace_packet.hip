@@ -803,75 +803,26 @@ void rtk_packet_entries_launch(const TraceParams &p, PkBlockEntries *out, float 
 	hipLaunchKernelGGL(rtk_packet_entries_kernel, dim3(bpr * rows), dim3(64), 0, stream, p.sc.nodes, p.rays, p.image_w, bpr, bound_abs, target, max_levels, out, p.counter);
 }
 
-// ---- the hand-written kernel: a code object of its own (rtk_packet_hot.S, assembled by the Makefile), carried in this
-// library as a byte array and loaded once per device
+// ---- the hand-written kernels: a code object of its own (rtk_packet_hot.S, rtk_packet_beam2.S; AsmModule, rtk_trace_shared.h)
 #include "rtk_packet_hot_image.h"
-#include <mutex>
 
-namespace {
-struct HotModule { hipModule_t mod = nullptr; hipFunction_t fn = nullptr, fn_beam = nullptr, fn_beam2 = nullptr, fn_count2 = nullptr, fn_any2 = nullptr; int blocks_per_cu = 0, beam_blocks_per_cu = 0, beam2_blocks_per_cu = 0; bool tried = false; };
-std::mutex g_hot_mutex;
-HotModule g_hot[RTK_MAX_DEVICES];
-
-HotModule *hot_module(int device)
+AsmModule &rtk_packet_module()
 {
-	if (device < 0 || device >= RTK_MAX_DEVICES) return nullptr;
-	std::lock_guard<std::mutex> lock(g_hot_mutex);
-	HotModule &h = g_hot[device];
-	if (!h.tried) {
-		int cur = -1;
-		if (hipGetDevice(&cur) != hipSuccess || cur != device) return nullptr;      // loaded by a thread that has this device current (asked again later)
-		h.tried = true;
-		if (hipModuleLoadData(&h.mod, rtk_packet_hot_image) != hipSuccess || hipModuleGetFunction(&h.fn, h.mod, "rtk_packet_hot") != hipSuccess) {
-			(void)hipGetLastError();
-			h.fn = nullptr;
-		} else {
-			// 64 VGPRs, 96 SGPRs, 20 KB of LDS per workgroup (20 stack entries per lane): seven waves per SIMD (the occupancy query reports one more for
-			// kernels at this SGPR count on ROCm 7.2; 800 / (96 + 16) = 7)
-			int nb = 0;
-			if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, h.fn, TRACE_BLOCK_THREADS, 0) != hipSuccess || nb < 1) nb = 1;
-			h.blocks_per_cu = nb > 7 ? 7 : nb;
-			// rtk_packet_beam (the same file assembled with -DRTK_BEAM): 64 VGPRs, 94 SGPRs, no LDS: eight waves per SIMD
-			if (hipModuleGetFunction(&h.fn_beam, h.mod, "rtk_packet_beam") != hipSuccess) { (void)hipGetLastError(); h.fn_beam = nullptr; }
-			else {
-				nb = 0;
-				if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, h.fn_beam, TRACE_BLOCK_THREADS, 0) != hipSuccess || nb < 1) nb = 1;
-				h.beam_blocks_per_cu = nb > 8 ? 8 : nb;
-			}
-			// rtk_packet_beam2 (rtk_packet_beam2.S: two adjacent tiles per wave): 72 VGPRs: seven waves per SIMD
-			if (hipModuleGetFunction(&h.fn_beam2, h.mod, "rtk_packet_beam2") != hipSuccess) { (void)hipGetLastError(); h.fn_beam2 = nullptr; }
-			else {
-				nb = 0;
-				if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, h.fn_beam2, TRACE_BLOCK_THREADS, 0) != hipSuccess || nb < 1) nb = 1;
-				h.beam2_blocks_per_cu = nb > 7 ? 7 : nb;
-			}
-			// rtk_packet_count2: rtk_packet_beam2.S assembled with -DRTK_COUNT (the counting form of the kernel that is timed)
-			if (hipModuleGetFunction(&h.fn_count2, h.mod, "rtk_packet_count2") != hipSuccess) { (void)hipGetLastError(); h.fn_count2 = nullptr; }
-			// rtk_packet_any2: ... with -DRTK_ANY (one flag per ray, a ray retired at its first hit)
-			if (hipModuleGetFunction(&h.fn_any2, h.mod, "rtk_packet_any2") != hipSuccess) { (void)hipGetLastError(); h.fn_any2 = nullptr; }
-		}
-	}
-	return h.fn ? &h : nullptr;
-}
-} // namespace
-
-bool rtk_packet_hot_available(int device, int *blocks_per_cu, int beam)
-{
-	HotModule *h = hot_module(device);
-	if (!h || (beam == 1 && !h->fn_beam) || (beam == 2 && !h->fn_beam2) || (beam == 3 && !h->fn_count2) || (beam == 4 && !h->fn_any2)) return false;
-	if (blocks_per_cu) *blocks_per_cu = beam >= 2 ? h->beam2_blocks_per_cu : beam == 1 ? h->beam_blocks_per_cu : h->blocks_per_cu;
-	return true;
-}
-
-int rtk_packet_hot_launch(int device, const PkHotParams &hp_in, unsigned blocks, hipStream_t stream, int beam)
-{
-	HotModule *h = hot_module(device);
-	if (!h || (beam == 1 && !h->fn_beam) || (beam == 2 && !h->fn_beam2) || (beam == 3 && !h->fn_count2) || (beam == 4 && !h->fn_any2)) { rtk_set_error("rtk_dev_trace: the assembly packet kernel is not loaded"); return RTK_AMD_ERR_HIP; }
-	PkHotParams hp = hp_in;
-	size_t size = sizeof(hp);
-	void *config[] = { HIP_LAUNCH_PARAM_BUFFER_POINTER, &hp, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END };
-	RTK_HIP_CHECK(hipModuleLaunchKernel(beam == 4 ? h->fn_any2 : beam == 3 ? h->fn_count2 : beam == 2 ? h->fn_beam2 : beam == 1 ? h->fn_beam : h->fn, blocks, 1, 1, TRACE_BLOCK_THREADS, 1, 1, 0, stream, nullptr, config), RTK_AMD_ERR_HIP);
-	return RTK_AMD_OK;
+	static const AsmKernel table[NUM_PACKET_KERNELS] = {
+		// 64 VGPRs, 96 SGPRs, 20 KB of LDS per workgroup (20 stack entries per lane): seven waves per SIMD (the occupancy query reports one more for
+		// kernels at this SGPR count on ROCm 7.2; 800 / (96 + 16) = 7)
+		{ "rtk_packet_hot", 7 },
+		// the same file assembled with -DRTK_BEAM: 64 VGPRs, 94 SGPRs, no LDS: eight waves per SIMD
+		{ "rtk_packet_beam", 8 },
+		// rtk_packet_beam2.S, two adjacent tiles per wave: 72 VGPRs: seven waves per SIMD
+		{ "rtk_packet_beam2", 7 },
+		// ... assembled with -DRTK_COUNT (the counting form of the kernel that is timed) and with -DRTK_ANY (one flag per ray, a ray
+		// retired at its first hit): launched on rtk_packet_beam2's figure
+		{ "rtk_packet_count2", 0 },
+		{ "rtk_packet_any2", 0 },
+	};
+	static AsmModule m(rtk_packet_hot_image, table, NUM_PACKET_KERNELS, "rtk_dev_trace: the assembly packet kernel is not loaded");
+	return m;
 }
 
 int rtk_packet_occupancy(bool counted)

@@ -3,15 +3,11 @@
 #pragma once
 
 #include "rtk_dev.h"
+#include "rtk_trace_plan.h"
 
 #include <stddef.h>
+#include <mutex>
 
-#ifndef LDS_STACK
-#define LDS_STACK 15           // entries per lane held in LDS: 30 KB per workgroup, so that FIVE workgroups share a CU's 160 KB (with 16
-                               // entries = 32 KB only four are placed: -5 % on incoherent rays, -4 % on shadow rays; 14 and 13 spill more)
-#endif
-#define TRACE_WAVES_PER_BLOCK 4
-#define TRACE_BLOCK_THREADS (64 * TRACE_WAVES_PER_BLOCK)
 #define WAVES_PER_BLOCK TRACE_WAVES_PER_BLOCK
 #define BLOCK_THREADS TRACE_BLOCK_THREADS
 
@@ -146,17 +142,32 @@ __device__ __forceinline__ unsigned long long map_index(unsigned long long i, ui
 }
 
 
-// the hand-written per-lane kernels (rtk_lane_hot.S; loader in rtk_trace.hip)
-bool rtk_lane_hot_available(int device, int *blocks_per_cu);
-int rtk_lane_hot_launch(int device, const LnHotParams &hp, unsigned blocks, hipStream_t stream, bool any_hit);
 // rtk_trace_packet.hip
 int rtk_packet_occupancy(bool counted);
 void rtk_packet_launch(const TraceParams &p, unsigned blocks, hipStream_t stream, bool counted);
 // the blocks' entry lists (p.image_w / image_h, 64x64-pixel blocks numbered row by row) into `out`, one wave per block
 void rtk_packet_entries_launch(const TraceParams &p, PkBlockEntries *out, float bound_abs, unsigned target, unsigned max_levels, hipStream_t stream);
-// the hand-written kernel (rtk_packet_hot.S): can this device run it (module loads), and its launch. blocks_per_cu: resident workgroups.
-// beam = 1: rtk_packet_beam, the variant whose node test is the interval test of the tile's own beam (one child plane per lane);
-// 2: rtk_packet_beam2, two adjacent tiles per wave (the two halves of the wave test a node for the two tiles' beams);
-// 3: rtk_packet_count2, the counting form of rtk_packet_beam2 (the same source assembled with -DRTK_COUNT)
-bool rtk_packet_hot_available(int device, int *blocks_per_cu, int beam = 0);
-int rtk_packet_hot_launch(int device, const PkHotParams &hp, unsigned blocks, hipStream_t stream, int beam = 0);
+
+// The hand-written kernels: a code object assembled by the Makefile, carried in this library as a byte array and loaded once per
+// device, by a thread that has this device current. One object per .S family, its kernels named by a table; all of them run
+// TRACE_BLOCK_THREADS lanes per workgroup and take their arguments as one parameter block.
+struct AsmKernel {
+	const char *name;
+	int cap;                       // most workgroups per CU, whatever the occupancy query says; 0: launched on another kernel's figure, not asked
+};
+struct AsmModule {
+	enum { MAX_KERNELS = NUM_PACKET_KERNELS };
+	struct Loaded { hipModule_t mod = nullptr; hipFunction_t fn[MAX_KERNELS] = {}; int blocks_per_cu[MAX_KERNELS] = {}; bool tried = false; };
+	const void *image;
+	const AsmKernel *table;        // [count]; the object counts as loaded if table[0] is found
+	int count;
+	const char *not_loaded;        // the error of a launch without the kernel
+	std::mutex mutex;
+	Loaded slot[RTK_MAX_DEVICES];
+	AsmModule(const void *image_, const AsmKernel *table_, int count_, const char *not_loaded_) : image(image_), table(table_), count(count_), not_loaded(not_loaded_) {}
+	// the device's kernels, or NULL: the object does not load, or this thread has another device current (asked again later)
+	const Loaded *on(int device);
+	int launch(int device, int kernel, void *params, size_t size, unsigned blocks, hipStream_t stream);
+};
+AsmModule &rtk_lane_module();      // rtk_lane_hot.S: 0 rtk_lane_hot_closest, 1 rtk_lane_hot_any (rtk_trace.hip)
+AsmModule &rtk_packet_module();    // rtk_packet_hot.S, rtk_packet_beam2.S: kernels numbered by PacketKernel (rtk_trace_packet.hip)
