@@ -142,7 +142,7 @@ rtk_scene *rtk_dev_scene_export(const rtk_dev_scene *ds, void *buffer, size_t si
  *     unknown position type, a mesh without positions. RTK_AMD_ERR_UNSUPPORTED: a mesh with position_cb set (callbacks
  *     are out of scope for a refit). These are decided before anything is launched: the scene is untouched.
  *   - The tree's QUALITY is the topology's: after a large deformation the scene traces correctly, but slower than a
- *     rebuild of the new positions would. Nothing detects that; the host decides when to rebuild.
+ *     rebuild of the new positions would. rtk_dev_scene_quality (below) measures that; the host decides when to rebuild.
  * rtk_dev_scene_last_refit_ms: wall time inside the last successful refit of the scene (0 if there was none). */
 int rtk_dev_scene_refit(rtk_dev_scene *ds, const rtk_scene_desc *desc, void *stream);
 double rtk_dev_scene_last_refit_ms(const rtk_dev_scene *ds);
@@ -171,6 +171,47 @@ double rtk_dev_scene_last_refit_ms(const rtk_dev_scene *ds);
  * calls (0 after a call that had nothing to do). */
 int rtk_dev_scene_refit_meshes(rtk_dev_scene *ds, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids, void *stream);
 uint64_t rtk_dev_scene_last_refit_nodes(const rtk_dev_scene *ds);
+
+/* How good the tree is NOW: the surface-area-heuristic cost of the scene's exact child boxes, measured on the device. What
+ * a host that refits every frame asks to learn that a rebuild pays: measure once after rtk_dev_scene_build (or an upload),
+ * refit, measure again every frame or every few, and rebuild when sah_cost has grown past a ratio of the host's choosing.
+ *   - Area of a box: 2 * (dx*dy + dy*dz + dz*dx) with dx = (double)max - (double)min, in this order. A child slot counts by
+ *     its child word: empty slots are skipped whatever their planes hold; a leaf child's triangle count is the one its first
+ *     triangle record carries. A child box whose area is not finite (NaN or inf positions) is counted in nonfinite_boxes and
+ *     left out of every sum (it still counts as an inner or a leaf child).
+ *   - cost_node and cost_tri are the builder's own constants (0.5 and 1.0; environment RTK_AMD_SAH_CN / RTK_AMD_SAH_CT
+ *     override both the builder and this call).
+ *   - A root_area that is 0 or not finite gives node_visits = triangle_tests = sah_cost = 0; the sums are still reported
+ *     and the call succeeds. A scene without triangles gives all zeros.
+ *   - sah_cost_at_build: the sah_cost of the first successful call made while the scene had never had a successful refit
+ *     (either refit call); the scene keeps it and every later call reports it. If the first call comes after a refit the
+ *     field stays 0 (not known) for good: a host that wants sah_cost / sah_cost_at_build calls once right after the build
+ *     or the upload. A refit measures nothing by itself.
+ *   - DETERMINISTIC: two calls on a scene with the same bits return the same bits (measure_ms apart), so a scene and its
+ *     replicas on other GPUs of the same kind agree, and a refit back to the build's positions gives the build's cost.
+ *   - Reads only: no bit of the scene changes (rtk_dev_scene_validate's content_hash stays); safe beside traces of the
+ *     scene on other streams and threads. It must not overlap a refit of the scene: the two take the same lock, and a
+ *     measurement beside a refit on another thread waits for it. Synchronous: the call returns with the result in *out;
+ *     work queued earlier on `stream` is ordered before it. The first call of a scene allocates 64 KB of device memory
+ *     (counted in total_device_bytes); later calls allocate nothing.
+ *   - RTK_AMD_ERR_BAD_ARG: ds or out NULL, or out->struct_size < sizeof(rtk_dev_scene_quality_info); decided before any
+ *     HIP call. Works unchanged on the replicas of a multi-GPU context, rtk_mgpu_scene(m, i). */
+typedef struct rtk_dev_scene_quality_info {
+	uint32_t struct_size;        /* sizeof(rtk_dev_scene_quality_info), set by the caller */
+	uint32_t nonfinite_boxes;    /* child boxes whose area is not finite: counted, left out of every sum */
+	uint64_t inner_children;     /* child slots that name a node */
+	uint64_t leaf_children;      /* child slots that name a leaf */
+	double root_area;            /* surface area of the union of the root node's non-empty child boxes */
+	double inner_area;           /* sum of the areas of all inner child boxes */
+	double leaf_area;            /* sum of the areas of all leaf child boxes */
+	double leaf_area_triangles;  /* sum over leaf children of area * triangles in the leaf */
+	double node_visits;          /* 1 + inner_area / root_area */
+	double triangle_tests;       /* leaf_area_triangles / root_area */
+	double sah_cost;             /* cost_node * node_visits + cost_tri * triangle_tests */
+	double sah_cost_at_build;    /* see above; 0 = not known */
+	double measure_ms;           /* wall time inside this call */
+} rtk_dev_scene_quality_info;
+int rtk_dev_scene_quality(const rtk_dev_scene *ds, rtk_dev_scene_quality_info *out, void *stream);
 
 /* Structural check of a device scene, run on the device (the loader/validator the reference lacks,
  * SURVEY.md section 5; blob-level checks happen in rtk_dev_scene_upload). Every child box must contain

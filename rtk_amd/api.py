@@ -47,6 +47,17 @@ class SceneCheck(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class SceneQuality(C.Structure):
+    """rtk_dev_scene_quality_info: the SAH cost of a scene's tree as it is now."""
+    _fields_ = [("struct_size", C.c_uint32), ("nonfinite_boxes", C.c_uint32), ("inner_children", C.c_uint64),
+                ("leaf_children", C.c_uint64), ("root_area", C.c_double), ("inner_area", C.c_double), ("leaf_area", C.c_double),
+                ("leaf_area_triangles", C.c_double), ("node_visits", C.c_double), ("triangle_tests", C.c_double),
+                ("sah_cost", C.c_double), ("sah_cost_at_build", C.c_double), ("measure_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_}
+
+
 class TraceOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("image_width", C.c_uint32),
                 ("image_height", C.c_uint32), ("refill_min", C.c_uint32), ("blocks_per_cu", C.c_uint32),
@@ -95,7 +106,8 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_amd_set_builder", "rtk_amd_get_builder", "rtk_amd_set_per_ray",
                      "rtk_mgpu_trace_rays_device_striped", "rtk_mgpu_striped_segment",
                      "rtk_dev_scene_refit", "rtk_dev_scene_last_refit_ms", "rtk_mgpu_refit",
-                     "rtk_dev_scene_refit_meshes", "rtk_dev_scene_last_refit_nodes", "rtk_mgpu_refit_meshes"]
+                     "rtk_dev_scene_refit_meshes", "rtk_dev_scene_last_refit_nodes", "rtk_mgpu_refit_meshes",
+                     "rtk_dev_scene_quality"]
 
 _lib = None
 
@@ -170,6 +182,8 @@ def lib():
     L.rtk_dev_scene_refit_meshes.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_size_t, C.c_void_p]
     L.rtk_dev_scene_last_refit_nodes.restype = C.c_uint64
     L.rtk_dev_scene_last_refit_nodes.argtypes = [C.c_void_p]
+    L.rtk_dev_scene_quality.restype = C.c_int
+    L.rtk_dev_scene_quality.argtypes = [C.c_void_p, C.POINTER(SceneQuality), C.c_void_p]
     L.rtk_mgpu_refit_meshes.restype = C.c_int
     L.rtk_mgpu_refit_meshes.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_size_t]
     L.rtk_mgpu_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(TraceOpts)]
@@ -311,6 +325,18 @@ class DeviceScene:
     def last_refit_nodes(self):
         """Nodes whose boxes the last successful refit remade (rtk_dev_scene_last_refit_nodes)."""
         return int(lib().rtk_dev_scene_last_refit_nodes(self.handle))
+
+    def quality(self):
+        """The SAH cost of the tree as it is now (rtk_dev_scene_quality), measured on the device on the current stream: the
+        fields of rtk_dev_scene_quality_info as a dict, plus ratio = sah_cost / sah_cost_at_build (None while the scene has
+        no cost from before its first refit: call once right after build() or upload()). Reads only; deterministic."""
+        _torch()
+        q = SceneQuality()
+        q.struct_size = C.sizeof(SceneQuality)
+        _check(lib().rtk_dev_scene_quality(self.handle, C.byref(q), _stream_ptr()), "rtk_dev_scene_quality")
+        d = q.as_dict()
+        d["ratio"] = d["sah_cost"] / d["sah_cost_at_build"] if d["sah_cost_at_build"] != 0.0 else None
+        return d
 
     def free(self):
         if self.handle:

@@ -1887,6 +1887,12 @@ extern "C" void rtk_amd_release_workspace(void)
 	}
 }
 
+void rtk_sah_costs(float *cost_node, float *cost_tri)
+{
+	*cost_tri = env_float("RTK_AMD_SAH_CT", 1.0f);
+	*cost_node = env_float("RTK_AMD_SAH_CN", 0.5f);     // sweeps on MI355X: small leaves win (profiles/r01_sweep_sah2.log)
+}
+
 // Caller memory that is already device memory (hipMalloc) is read in place (the ingest kernel, a refit's gather).
 bool rtk_is_device_ptr(const void *p)
 {
@@ -2146,8 +2152,7 @@ static rtk_dev_scene *build_impl(const rtk_scene_desc *desc, uint32_t force_bits
 	stage("ingest");
 
 	BuildParams bp;
-	bp.cost_tri = env_float("RTK_AMD_SAH_CT", 1.0f);
-	bp.cost_node = env_float("RTK_AMD_SAH_CN", 0.5f);   // sweeps on MI355X: small leaves win (profiles/r01_sweep_sah2.log)
+	rtk_sah_costs(&bp.cost_node, &bp.cost_tri);
 	// leaves of at most three triangles: a leaf of fewer than four is one partial group for the reference's group-of-four rule
 	// (rtk.c:302-336: double-precision edge functions, no redo), which is all the hand-written packet kernel implements; with
 	// cn = 0.5 the SAH rule made 1.008 triangles per leaf at a limit of 8, so nothing of substance changes

@@ -148,6 +148,15 @@ struct RefitPartial {
 	uint32_t epoch = 0;                        // of the last call (0: none yet; d_dirty starts cleared)
 };
 
+// What rtk_dev_scene_quality keeps per scene (rtk_quality.hip): its partial records and result slot on the device, made by the
+// first measurement and owned through rtk_dev_scene::allocs, and the cost the scene had before any refit.
+struct QualityState {
+	void *d_mem = nullptr;
+	bool refitted = false;                     // a refit of the scene has succeeded (set by the refit, read by the measurement)
+	bool baseline_known = false;               // a measurement was made before any refit ...
+	double sah_cost_at_build = 0.0;            // ... and gave this cost
+};
+
 struct rtk_dev_scene {
 	int device = 0;
 	DevSceneView view = {};
@@ -185,6 +194,7 @@ struct rtk_dev_scene {
 	bool boxes_exact = false;                  // every box is known to be the exact union of what is below it (a device build, a full refit; not an upload)
 	uint64_t refit_nodes = 0;                  // nodes whose boxes the last successful refit remade
 	uint32_t partial_readback = 0;             // the dirty count of a partial refit, brought home with the constants
+	QualityState quality;                      // under refit_mutex, like the schedule
 };
 // makes the side arrays if they are not there yet (synchronises `stream` the one time it has to work)
 int rtk_scene_side_arrays(const rtk_dev_scene *ds, hipStream_t stream);
@@ -245,6 +255,9 @@ struct WorkspaceLoan {
 bool rtk_is_device_ptr(const void *p);         // hipMalloc'ed memory?
 static inline size_t rtk_padded(size_t bytes) { return ((bytes ? bytes : 1) + 255u) & ~(size_t)255u; }   // sizes inside one allocation: 256-byte steps
 void rtk_export_forget(const rtk_dev_scene *ds);   // the scene's cached export plan, if any (rtk_build.hip)
+// the two constants of the surface area heuristic, for the builder that splits by them and for rtk_dev_scene_quality that
+// measures by them: 0.5 per node visited, 1.0 per triangle tested, RTK_AMD_SAH_CN / RTK_AMD_SAH_CT override (rtk_build.hip)
+void rtk_sah_costs(float *cost_node, float *cost_tri);
 
 // -- radix sort shared with the builder (rtk_build.hip) --
 size_t rtk_sort_scratch_words(uint32_t n);

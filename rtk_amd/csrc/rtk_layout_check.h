@@ -18,3 +18,5 @@ static_assert(sizeof(rtk_scene) == 56 && offsetof(rtk_scene, size_in_bytes) == 2
 static_assert(sizeof(rtk_scene_desc) == 32, "rtk_scene_desc");
 static_assert(sizeof(rtk_task) == 40 && offsetof(rtk_task, cost) == 16 && offsetof(rtk_task, arg) == 32, "rtk_task");
 static_assert(sizeof(rtk_hit_record) == 16, "rtk_hit_record");
+static_assert(sizeof(rtk_dev_scene_quality_info) == 96 && offsetof(rtk_dev_scene_quality_info, inner_children) == 8 &&
+	offsetof(rtk_dev_scene_quality_info, root_area) == 24 && offsetof(rtk_dev_scene_quality_info, measure_ms) == 88, "rtk_dev_scene_quality_info");

@@ -771,6 +771,7 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 	}
 	rtk_export_forget(ds);
 	ds->boxes_exact = true;
+	ds->quality.refitted = true;               // (rtk_dev_scene_quality: a cost measured from now on is no longer the build's)
 	ds->refit_nodes = dirty_set ? ds->partial_readback : v.num_nodes;
 	return RTK_AMD_OK;
 }
