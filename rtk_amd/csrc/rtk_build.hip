@@ -12,12 +12,13 @@
 //   1 ingest     decode indices + positions of every mesh into 48-B staged triangles; centroid bounds in passing
 //   2 bounds     (separate pass only for host-decoded meshes)
 //   3 morton     63-bit Morton code per triangle; below 2^24 triangles its top 40 bits over the triangle's number
-//   4 sort       LSD radix sort, 8-bit digits, per-wave LDS histograms and counters
+//   4 sort       LSD radix sort, 8-bit digits, per-wave LDS histograms and counters (rtk_sort.hip)
 //   5 emit       triangles gathered into Morton order = final 48 B leaf records
 //   6 + 7 refit  binary radix tree built bottom-up together with its AABBs and the SAH leaf decision: tile-local in
 //                LDS, then the nodes that cross tile borders with memory-side atomics
 //   8 collapse   breadth-first, level by level: binary tree -> 128 B 4-wide nodes
 #include "rtk_dev.h"
+#include "rtk_build_layout.h"
 #include "rtk_node_finish.h"
 
 #include <limits.h>
@@ -30,14 +31,10 @@
 #include <atomic>
 #include <chrono>
 #include <mutex>
-#include <unordered_map>
 
 void rtk_cache_adopt(const rtk_scene *scene, rtk_dev_scene *ds);
 
 namespace {
-
-#define SORT_TILE 4096u           // keys handled by one workgroup per pass (4 waves x 16 chunks of 64)
-#define SORT_BLOCK 256
 
 struct BinNode {                  // 32 B, written by refit
 	float mn[3];
@@ -245,199 +242,6 @@ __global__ void k_morton(const float *cent, uint32_t n, const uint32_t *bounds, 
 		// fewer than 2^24 triangles: the top `63 - drop_bits` (24 ... 40, a multiple of 8) bits of the code above the triangle's
 		// own number. One 8-byte word per triangle goes through three to five sort passes instead of a 12-byte pair through six.
 		keys[i] = ((code >> drop_bits) << 24) | (unsigned long long)i;
-	}
-}
-
-// ---------------------------------------------------------------------------------- 4 radix sort
-// Unit of work = one workgroup = SORT_TILE consecutive keys (4 waves x 1024). hist is digit-major:
-// hist[digit * num_units + unit], so one exclusive scan over the whole array yields, for
-// every (digit, unit), the first output position of that unit's keys with that digit.
-
-__global__ void __launch_bounds__(SORT_BLOCK) k_sort_hist(const unsigned long long *keys, uint32_t n, uint32_t shift,
-	uint32_t num_units, uint32_t *hist)
-{
-	__shared__ uint32_t s_h[256];
-	const uint32_t unit = blockIdx.x;
-	s_h[threadIdx.x] = 0;
-	__syncthreads();
-	const size_t base = (size_t)unit * SORT_TILE;
-	for (uint32_t c = 0; c < SORT_TILE / SORT_BLOCK; c++) {
-		const size_t i = base + (size_t)c * SORT_BLOCK + threadIdx.x;     // coalesced 2 KB per step
-		if (i < n) atomicAdd(&s_h[(uint32_t)(keys[i] >> shift) & 255u], 1u);
-	}
-	__syncthreads();
-	hist[(size_t)threadIdx.x * num_units + unit] = s_h[threadIdx.x];
-}
-
-// exclusive scan of a uint32 array, three launches (block sums -> scan of sums -> add)
-#define SCAN_BLOCK 256
-#define SCAN_ITEMS 16             // per thread -> 4096 per block
-
-__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_block(uint32_t *data, size_t n, uint32_t *block_sums)
-{
-	__shared__ uint32_t s_wave[SCAN_BLOCK / 64];
-	const size_t base = (size_t)blockIdx.x * (SCAN_BLOCK * SCAN_ITEMS) + (size_t)threadIdx.x * SCAN_ITEMS;
-	uint32_t v[SCAN_ITEMS];
-	uint32_t sum = 0;
-#pragma unroll
-	for (int k = 0; k < SCAN_ITEMS; k++) { v[k] = base + k < n ? data[base + k] : 0u; sum += v[k]; }
-	// inclusive scan of `sum` across the wave
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	uint32_t inc = sum;
-	for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += t; }
-	if (lane == 63u) s_wave[wave] = inc;
-	__syncthreads();
-	uint32_t wave_off = 0;
-	for (uint32_t w = 0; w < wave; w++) wave_off += s_wave[w];
-	uint32_t run = wave_off + inc - sum;
-#pragma unroll
-	for (int k = 0; k < SCAN_ITEMS; k++) { if (base + k < n) data[base + k] = run; run += v[k]; }
-	if (threadIdx.x == SCAN_BLOCK - 1) block_sums[blockIdx.x] = run;
-}
-
-__global__ void __launch_bounds__(1024) k_scan_sums(uint32_t *sums, uint32_t n)
-{
-	// single block; n block sums, processed in strips of 1024 with a running carry
-	__shared__ uint32_t s_wave[16];
-	__shared__ uint32_t s_carry;
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	if (threadIdx.x == 0) s_carry = 0;
-	__syncthreads();
-	for (uint32_t base = 0; base < n; base += 1024u) {
-		const uint32_t i = base + threadIdx.x;
-		const uint32_t v = i < n ? sums[i] : 0u;
-		uint32_t inc = v;
-		for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += t; }
-		if (lane == 63u) s_wave[wave] = inc;
-		__syncthreads();
-		uint32_t off = s_carry;
-		for (uint32_t w = 0; w < wave; w++) off += s_wave[w];
-		if (i < n) sums[i] = off + inc - v;
-		__syncthreads();
-		if (threadIdx.x == 1023u) s_carry = off + inc;
-		__syncthreads();
-	}
-}
-
-__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_add(uint32_t *data, size_t n, const uint32_t *block_sums)
-{
-	const uint32_t add = block_sums[blockIdx.x];
-	const size_t base = (size_t)blockIdx.x * (SCAN_BLOCK * SCAN_ITEMS) + (size_t)threadIdx.x * SCAN_ITEMS;
-#pragma unroll
-	for (int k = 0; k < SCAN_ITEMS; k++) if (base + k < n) data[base + k] += add;
-}
-
-// Scatter pass with an LDS-staged tile. Each wave ranks its 1024 keys in order (16 chunks of 64;
-// the rank of a key inside a chunk comes from 8 ballots, the running per-digit counts of the wave
-// live in LDS), the four waves' counts are combined into tile-wide digit offsets, the (key, value)
-// pairs are written to their SORTED position inside the tile in LDS, and the tile is then streamed
-// out in that order: neighbouring threads hold neighbouring keys of the same digit, so the global
-// stores form contiguous runs (16 keys on average for random digits) instead of one store per key.
-// Stable: tile order = wave order = chunk order = lane order.
-// VALS = false: the words carry their payload themselves (sorted field above, index below): no value arrays at all.
-template <bool VALS>
-__global__ void __launch_bounds__(SORT_BLOCK) k_sort_scatter(const unsigned long long *keys_in, const uint32_t *vals_in, uint32_t n,
-	uint32_t shift, uint32_t num_units, const uint32_t *hist, unsigned long long *keys_out, uint32_t *vals_out,
-	const uint32_t *scan_sums, uint32_t scan_blocks)
-{
-	// (LDS: 36.9 KB without values -- 16-bit counts, s_bp inside s_key -- so that four workgroups fit a CU with room to spare; with
-	// 39.9 KB the four of them came to 159.8 of the CU's 160 KB. No measurable difference in the pass time either way.)
-	__shared__ unsigned long long s_key[SORT_TILE];          // 32 KB
-	uint32_t *const s_bp = reinterpret_cast<uint32_t *>(s_key);   // scan_sums != NULL: exclusive prefix of the scan blocks' totals; used before s_key is
-	__shared__ uint32_t s_val[SORT_TILE];                    // 16 KB
-	__shared__ uint16_t s_cnt[SORT_BLOCK / 64][256];         // per wave: running count (<= 1024), then prefix over earlier waves (<= 4096)
-	__shared__ uint32_t s_start[256];                        // first tile position of each digit
-	__shared__ uint32_t s_global[256];                       // first output position of this tile's keys of each digit
-	__shared__ uint32_t s_wsum[SORT_BLOCK / 64];
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	const uint32_t unit = blockIdx.x;
-	const size_t tile_base = (size_t)unit * SORT_TILE;
-	const uint32_t tile_n = (uint32_t)((size_t)n - tile_base < SORT_TILE ? (size_t)n - tile_base : SORT_TILE);
-
-	for (int j = 0; j < 4; j++) s_cnt[wave][lane + 64 * j] = 0;
-	if (scan_sums) {
-		// hist holds scans local to blocks of SCAN_BLOCK * SCAN_ITEMS entries (k_scan_block); the totals of the blocks
-		// before an entry's block are added here (at most SORT_BLOCK of them) instead of by two more launches per pass
-		const uint32_t v = threadIdx.x < scan_blocks ? scan_sums[threadIdx.x] : 0u;
-		uint32_t inc = v;
-		for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += t; }
-		if (lane == 63u) s_wsum[wave] = inc;
-		__syncthreads();
-		uint32_t off = 0;
-		for (uint32_t w = 0; w < wave; w++) off += s_wsum[w];
-		s_bp[threadIdx.x] = off + inc - v;
-		__syncthreads();
-		const size_t idx = (size_t)threadIdx.x * num_units + unit;
-		s_global[threadIdx.x] = hist[idx] + s_bp[idx / ((size_t)SCAN_BLOCK * SCAN_ITEMS)];
-	} else s_global[threadIdx.x] = hist[(size_t)threadIdx.x * num_units + unit];
-	__syncthreads();
-
-	// ---- phase 1: rank every key among the keys of its digit inside its wave
-	constexpr uint32_t CHUNKS = SORT_TILE / SORT_BLOCK;      // 16 chunks of 64 keys per wave
-	unsigned long long key[CHUNKS];
-	uint32_t val[CHUNKS], rnk[CHUNKS];
-	const unsigned long long lt_mask = lane == 0 ? 0ull : (~0ull >> (64u - lane));
-	const size_t wave_base = tile_base + (size_t)wave * (SORT_TILE / (SORT_BLOCK / 64));
-#pragma unroll
-	for (uint32_t c = 0; c < CHUNKS; c++) {
-		const size_t i = wave_base + (size_t)c * 64u + lane;
-		const bool valid = i < n;
-		key[c] = valid ? keys_in[i] : ~0ull;
-		val[c] = (VALS && valid) ? vals_in[i] : 0u;
-		const uint32_t d = (uint32_t)(key[c] >> shift) & 255u;
-		unsigned long long same = __ballot(valid);
-#pragma unroll
-		for (int b = 0; b < 8; b++) {
-			const bool bit = (d >> b) & 1u;
-			const unsigned long long vote = __ballot(bit);
-			same &= bit ? vote : ~vote;
-		}
-		rnk[c] = 0;
-		if (valid) {
-			const uint32_t r = (uint32_t)__popcll(same & lt_mask);
-			const uint32_t before = s_cnt[wave][d];            // every lane reads before any leader writes (wave program order)
-			rnk[c] = before + r;
-			if (r == 0u) s_cnt[wave][d] = (uint16_t)(before + (uint32_t)__popcll(same));
-		}
-	}
-	__syncthreads();
-
-	// ---- phase 2: tile-wide digit offsets. Thread d owns digit d.
-	{
-		const uint32_t d = threadIdx.x;
-		uint32_t run = 0;
-		for (uint32_t w = 0; w < SORT_BLOCK / 64; w++) { const uint32_t c = s_cnt[w][d]; s_cnt[w][d] = (uint16_t)run; run += c; }
-		// exclusive scan of the 256 digit totals
-		uint32_t inc = run;
-		for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += t; }
-		if (lane == 63u) s_wsum[wave] = inc;
-		__syncthreads();
-		uint32_t off = 0;
-		for (uint32_t w = 0; w < wave; w++) off += s_wsum[w];
-		s_start[d] = off + inc - run;
-	}
-	__syncthreads();
-
-	// ---- phase 3: stage the tile in sorted order
-#pragma unroll
-	for (uint32_t c = 0; c < CHUNKS; c++) {
-		const size_t i = wave_base + (size_t)c * 64u + lane;
-		if (i < n) {
-			const uint32_t d = (uint32_t)(key[c] >> shift) & 255u;
-			const uint32_t pos = s_start[d] + s_cnt[wave][d] + rnk[c];
-			s_key[pos] = key[c];
-			if (VALS) s_val[pos] = val[c];
-		}
-	}
-	__syncthreads();
-
-	// ---- phase 4: stream the tile out; runs of one digit are contiguous in LDS and in HBM
-	for (uint32_t i = threadIdx.x; i < tile_n; i += SORT_BLOCK) {
-		const unsigned long long k = s_key[i];
-		const uint32_t d = (uint32_t)(k >> shift) & 255u;
-		const uint32_t dst = s_global[d] + (i - s_start[d]);
-		keys_out[dst] = k;
-		if (VALS) vals_out[dst] = s_val[i];
 	}
 }
 
@@ -1636,14 +1440,6 @@ __global__ void __launch_bounds__(256) k_top_finish(const DevNode *top, const ui
 
 // ---------------------------------------------------------------------------------- host side
 
-template <typename T>
-struct DevBuf {
-	T *p = nullptr;
-	~DevBuf() { if (p) (void)hipFree(p); }
-	bool alloc(size_t n) { return hipMalloc(&p, (n ? n : 1) * sizeof(T)) == hipSuccess; }
-	T *release() { T *r = p; p = nullptr; return r; }
-};
-
 float env_float(const char *name, float def)
 {
 	const char *s = getenv(name);
@@ -1699,19 +1495,18 @@ hipError_t upload_staged(void *dst, const void *src, size_t bytes, hipStream_t s
 	return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream);
 }
 
-#define BUILD_CHECK(expr)                                                                               \
-	do {                                                                                                \
-		hipError_t e_ = (expr);                                                                         \
-		if (e_ != hipSuccess) {                                                                         \
-			rtk_set_error("device build: %s failed: %s (line %d)", #expr, hipGetErrorString(e_), __LINE__); \
-			return nullptr;                                                                             \
-		}                                                                                               \
-	} while (0)
-
-rtk_dev_scene *build_tiny(const rtk_scene_desc *desc, const std::vector<uint64_t> &mesh_base, const std::vector<float> &pos,
-	const std::vector<uint32_t> &vidx)
+// ---- fewer than two triangles: no radix tree to build, no workspace; one root node, at most one leaf ----
+rtk_dev_scene *build_tiny(const rtk_scene_desc *desc, const std::vector<uint64_t> &mesh_base)
 {
-	// 0 or 1 triangle: no radix tree to build; one root node, at most one leaf.
+	std::vector<float> pos;
+	std::vector<uint32_t> vidx;
+	for (size_t mi = 0; mi < desc->num_meshes; mi++) {
+		const rtk_mesh *m = &desc->meshes[mi];
+		if (m->num_triangles == 0) continue;
+		pos.resize(9 * m->num_triangles);
+		vidx.resize(3 * m->num_triangles);
+		decode_mesh_on_host(m, pos.data(), vidx.data());
+	}
 	HostBvh h;
 	h.mesh_base = mesh_base;
 	h.max_depth = 1;
@@ -1744,68 +1539,10 @@ rtk_dev_scene *build_tiny(const rtk_scene_desc *desc, const std::vector<uint64_t
 		root.child[0] = RTK_REF_LEAF | 0u;
 	}
 	h.nodes.push_back(root);
-	(void)desc;
 	return rtk_dev_scene_from_host_bvh(h);
 }
 
 } // namespace
-
-// Asynchronous radix sort of (64-bit key, 32-bit value) pairs on `stream`, low `key_bits` bits only
-// (rounded up to whole 8-bit passes). Ping-pongs between the a/b buffers; returns true if the result
-// is in the b buffers. scratch: rtk_sort_scratch_words(n) uint32 words. No allocation, no sync.
-size_t rtk_sort_scratch_words(uint32_t n)
-{
-	const size_t num_units = ((size_t)n + SORT_TILE - 1u) / SORT_TILE;
-	const size_t hist = 256 * num_units;
-	const size_t sums = (hist + (size_t)SCAN_BLOCK * SCAN_ITEMS - 1) / ((size_t)SCAN_BLOCK * SCAN_ITEMS);
-	return hist + sums + 16;
-}
-
-// Bits [first_bit, last_bit) of the keys, 8 at a time, least significant digit first. vals_a == NULL: keys only.
-static bool sort_async(unsigned long long *keys_a, unsigned long long *keys_b, uint32_t *vals_a, uint32_t *vals_b,
-	uint32_t n, uint32_t first_bit, uint32_t last_bit, uint32_t *scratch, hipStream_t stream)
-{
-	const uint32_t num_units = (n + SORT_TILE - 1u) / SORT_TILE;
-	const size_t hist_n = 256 * (size_t)num_units;
-	uint32_t *hist = scratch, *sums = scratch + hist_n;
-	const size_t scan_blocks = (hist_n + (size_t)SCAN_BLOCK * SCAN_ITEMS - 1) / ((size_t)SCAN_BLOCK * SCAN_ITEMS);
-	unsigned long long *kin = keys_a, *kout = keys_b;
-	uint32_t *vin = vals_a, *vout = vals_b;
-	bool in_b = false;
-	for (uint32_t shift = first_bit; shift < last_bit; shift += 8) {
-		hipLaunchKernelGGL(k_sort_hist, dim3(num_units), dim3(SORT_BLOCK), 0, stream, kin, n, shift, num_units, hist);
-		hipLaunchKernelGGL(k_scan_block, dim3((unsigned)scan_blocks), dim3(SCAN_BLOCK), 0, stream, hist, hist_n, sums);
-		// up to 2^24 keys the scatter pass finishes the scan itself (three launches per pass instead of five)
-		static const bool allow_fused = !(getenv("RTK_AMD_SORT_FUSED_SCAN") && atoi(getenv("RTK_AMD_SORT_FUSED_SCAN")) == 0);   // 0: test the large-n path on small scenes
-		const uint32_t *fused_sums = (allow_fused && scan_blocks <= SORT_BLOCK) ? sums : nullptr;
-		if (!fused_sums) {
-			hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, stream, sums, (uint32_t)scan_blocks);
-			hipLaunchKernelGGL(k_scan_add, dim3((unsigned)scan_blocks), dim3(SCAN_BLOCK), 0, stream, hist, hist_n, sums);
-		}
-		if (vals_a) hipLaunchKernelGGL((k_sort_scatter<true>), dim3(num_units), dim3(SORT_BLOCK), 0, stream, kin, vin, n, shift, num_units, hist, kout, vout,
-			fused_sums, (uint32_t)scan_blocks);
-		else hipLaunchKernelGGL((k_sort_scatter<false>), dim3(num_units), dim3(SORT_BLOCK), 0, stream, kin, (const uint32_t *)nullptr, n, shift, num_units, hist,
-			kout, (uint32_t *)nullptr, fused_sums, (uint32_t)scan_blocks);
-		std::swap(kin, kout);
-		std::swap(vin, vout);
-		in_b = !in_b;
-	}
-	return in_b;
-}
-
-bool rtk_sort_pairs_async(unsigned long long *keys_a, unsigned long long *keys_b, uint32_t *vals_a, uint32_t *vals_b,
-	uint32_t n, uint32_t key_bits, uint32_t *scratch, hipStream_t stream)
-{
-	return sort_async(keys_a, keys_b, vals_a, vals_b, n, 0u, key_bits, scratch, stream);
-}
-
-// 64-bit words sorted by their bits [first_bit, last_bit); the bits below first_bit ride along (an index, a payload).
-// Stable, so words that start out in index order stay in index order inside equal fields. True: the result is in keys_b.
-bool rtk_sort_words_async(unsigned long long *keys_a, unsigned long long *keys_b, uint32_t n, uint32_t first_bit, uint32_t last_bit,
-	uint32_t *scratch, hipStream_t stream)
-{
-	return sort_async(keys_a, keys_b, nullptr, nullptr, n, first_bit, last_bit, scratch, stream);
-}
 
 // =====================================================================================
 // rtk_dev_scene_build
@@ -1830,17 +1567,23 @@ struct Workspace {
 };
 Workspace g_workspace[RTK_MAX_DEVICES];
 
-struct Arena {
-	char *base;
-	size_t cap, off;
-	template <typename T> T *take(size_t n)
-	{
-		off = (off + 255u) & ~(size_t)255u;
-		T *p = reinterpret_cast<T *>(base + off);
-		off += (n ? n : 1) * sizeof(T);
-		return off <= cap ? p : nullptr;
+// The workspace (its mutex held) grown to at least `bytes`: asks for bytes + bytes / slack_div (0: no slack), and once more for
+// exactly `bytes` if that much cannot be had. False: out of device memory, the workspace is empty.
+bool workspace_grow(Workspace &w, size_t bytes, unsigned slack_div)
+{
+	if (w.base && w.cap >= bytes) return true;
+	if (w.base) (void)hipFree(w.base);
+	w.base = nullptr;
+	w.cap = 0;
+	const size_t want = bytes + (slack_div ? bytes / slack_div : 0);
+	for (const size_t ask : { want, bytes }) {
+		if (hipMalloc(&w.base, ask) == hipSuccess) { w.cap = ask; return true; }
+		(void)hipGetLastError();
+		w.base = nullptr;
+		if (want == bytes) break;
 	}
-};
+	return false;
+}
 
 // How one mesh reaches the ingest kernel.
 struct MeshPlan {
@@ -1851,8 +1594,6 @@ struct MeshPlan {
 	size_t pbytes = 0, ibytes = 0;  // bytes to upload (0: already device memory / nothing)
 	const char *pos_src = nullptr, *idx_src = nullptr;
 	bool pos_on_device = false, idx_on_device = false;
-	bool direct = false;            // implicit indices, float positions: nothing staged, k_emit_tris gathers from the position buffer itself
-	const char *dev_pos = nullptr;  // where the ingest kernel read the positions (the caller's device buffer or the uploaded copy)
 };
 
 int cached_cu_count(int device)
@@ -1908,19 +1649,11 @@ bool WorkspaceLoan::take(int dev, size_t bytes)
 	if (dev < 0 || dev >= RTK_MAX_DEVICES) { rtk_set_error("workspace: device %d out of range", dev); return false; }
 	Workspace &w = g_workspace[dev];
 	w.mutex.lock();
-	if (w.cap < bytes || !w.base) {
-		if (w.base) (void)hipFree(w.base);
-		w.base = nullptr;
-		w.cap = 0;
-		const size_t want = bytes ? bytes : 256;
-		if (hipMalloc(&w.base, want) != hipSuccess) {
-			(void)hipGetLastError();
-			w.base = nullptr;
-			w.mutex.unlock();
-			rtk_set_error("workspace: out of device memory (%zu bytes)", want);
-			return false;
-		}
-		w.cap = want;
+	const size_t want = bytes ? bytes : 256;
+	if (!workspace_grow(w, want, 0)) {
+		w.mutex.unlock();
+		rtk_set_error("workspace: out of device memory (%zu bytes)", want);
+		return false;
 	}
 	device = dev;
 	base = w.base;
@@ -1935,51 +1668,184 @@ void WorkspaceLoan::release()
 	base = nullptr;
 }
 
-// force_bits: 0 = key width from the number of triangles; else the width of the Morton code in the packed sort words.
-// *narrow_key: the build was made with fewer than 40 bits and more than an eighth of the sorted neighbours share their code.
-static rtk_dev_scene *build_impl(const rtk_scene_desc *desc, uint32_t force_bits, bool *narrow_key)
+namespace {
+
+// ---- knobs: every environment variable the build reads, read in one place at the top of a build ----
+
+// "set it to 0 to turn it off": true unless the variable is there and reads as 0
+bool env_unless_zero(const char *name)
 {
-	*narrow_key = false;
-	if (!desc || (!desc->meshes && desc->num_meshes)) { rtk_set_error("rtk_dev_scene_build: NULL scene description"); return nullptr; }
-	std::vector<uint64_t> mesh_base(desc->num_meshes + 1, 0);
-	for (size_t m = 0; m < desc->num_meshes; m++) mesh_base[m + 1] = mesh_base[m] + desc->meshes[m].num_triangles;
-	const uint64_t n64 = mesh_base.back();
-	if (n64 >= 0x3ffffff0ull) { rtk_set_error("rtk_dev_scene_build: more than 2^30 triangles"); return nullptr; }
-	const uint32_t n = (uint32_t)n64;
-	if (desc->log_fn) desc->log_fn(desc->log_user, nullptr, "rtk_amd: device LBVH build");
-	const auto t_begin = std::chrono::steady_clock::now();
-	const bool timing = getenv("RTK_AMD_BUILD_TIMING") != nullptr;
-	auto t_last = t_begin;
-	// RTK_AMD_BUILD_HOSTTIME=1: where the HOST is when (no synchronisation: how far ahead of the GPU the enqueueing thread runs)
-	const bool host_time = getenv("RTK_AMD_BUILD_HOSTTIME") && atoi(getenv("RTK_AMD_BUILD_HOSTTIME")) != 0;
-	auto stage = [&](const char *name) {
-		if (host_time) fprintf(stderr, "rtk_amd build host: %-10s at %8.3f ms\n", name, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-		if (!timing) return;
+	const char *s = getenv(name);
+	return !(s && atoi(s) == 0);
+}
+
+struct BuildKnobs {
+	bool timing;             // RTK_AMD_BUILD_TIMING (set at all): the device time of every stage, with a device synchronisation after each
+	bool host_time;          // RTK_AMD_BUILD_HOSTTIME=1: where the HOST is when (no synchronisation: how far ahead of the GPU the enqueueing thread runs)
+	uint32_t max_leaf;       // RTK_AMD_MAX_LEAF, 1 .. 63
+	bool sort_packed;        // RTK_AMD_SORT_PACKED=0: the >= 2^24-triangle path (key, index pairs), for tests on small scenes
+	uint32_t key_bits;       // RTK_AMD_KEY_BITS: 8 .. 40 in steps of 8, the width of the Morton code in the packed sort words (0: from the number of triangles)
+	bool direct;             // RTK_AMD_BUILD_DIRECT=0: every mesh is staged, none gathered in place by the emit. Read once per process.
+	bool fused_emit;         // RTK_AMD_FUSED_EMIT=0: the triangle records are made by a pass of their own, not inside k_refit_tile (A/B)
+	uint64_t tile_min;       // RTK_AMD_TILE_COLLAPSE_MIN: triangles from which the tile collapse is used (see below)
+	uint32_t top_cap;        // RTK_AMD_TOP_CAP: at most so many nodes above the tiles, to drive the way back to the level-by-level collapse from tests
+	int est_div;             // RTK_AMD_NODE_ESTIMATE_DIV: node arrays of n / div + 16 nodes at first, to drive the repeat path from tests (0: the usual estimate)
+	bool keep_workspace;     // RTK_AMD_KEEP_WORKSPACE=0: the workspace is freed after every build
+	bool key_rebuild;        // RTK_AMD_KEY_REBUILD=0: a scene whose narrow keys collide too often is not built again with wide ones
+};
+
+BuildKnobs read_build_knobs()
+{
+	BuildKnobs k;
+	k.timing = getenv("RTK_AMD_BUILD_TIMING") != nullptr;
+	k.host_time = getenv("RTK_AMD_BUILD_HOSTTIME") && atoi(getenv("RTK_AMD_BUILD_HOSTTIME")) != 0;
+	// leaves of at most three triangles: a leaf of fewer than four is one partial group for the reference's group-of-four rule
+	// (rtk.c:302-336: double-precision edge functions, no redo), which is all the hand-written packet kernel implements; with
+	// cn = 0.5 the SAH rule made 1.008 triangles per leaf at a limit of 8, so nothing of substance changes
+	k.max_leaf = (uint32_t)env_float("RTK_AMD_MAX_LEAF", 3.0f);
+	if (k.max_leaf < 1) k.max_leaf = 1;
+	if (k.max_leaf > 63) k.max_leaf = 63;     // 6-bit count in the blob's leaf header (rtk.c:188)
+	k.sort_packed = env_unless_zero("RTK_AMD_SORT_PACKED");
+	k.key_bits = 0;
+	if (getenv("RTK_AMD_KEY_BITS")) { const int kb = atoi(getenv("RTK_AMD_KEY_BITS")); if (kb >= 8 && kb <= 40 && kb % 8 == 0) k.key_bits = (uint32_t)kb; }
+	static const bool allow_direct = env_unless_zero("RTK_AMD_BUILD_DIRECT");
+	k.direct = allow_direct;
+	k.fused_emit = env_unless_zero("RTK_AMD_FUSED_EMIT");
+	// Tile mode (the subtrees inside a refit tile collapsed by k_collapse_tile), measured on MI355X (profiles/r05_build_timing.log, level
+	// by level / tile mode): 0.47 / 0.46 ms at 0.5M triangles, 0.555 / 0.540 at 1M, 0.785 / 0.748 at 2M, 1.005 / 0.935 at 3M -- since the
+	// tiles' kernels run beside pass 2 and the top collapse, tile mode is never slower; its trees have ~2 % more nodes (tile roots are never
+	// opened from above: ~1 % more node visits per ray), so it starts where the build time it saves is worth more than that: 1.5M
+	// triangles. RTK_AMD_TILE_COLLAPSE_MIN (triangles; read per build) moves that: 0 = whenever there are two tiles, a huge value =
+	// never (everything level by level: A/B).
+	const char *tile_env = getenv("RTK_AMD_TILE_COLLAPSE_MIN");
+	k.tile_min = tile_env ? (uint64_t)atoll(tile_env) : (3ull << 19);
+	k.top_cap = getenv("RTK_AMD_TOP_CAP") ? (uint32_t)atoi(getenv("RTK_AMD_TOP_CAP")) : 0xffffffffu;
+	k.est_div = getenv("RTK_AMD_NODE_ESTIMATE_DIV") ? atoi(getenv("RTK_AMD_NODE_ESTIMATE_DIV")) : 0;
+	k.keep_workspace = env_unless_zero("RTK_AMD_KEEP_WORKSPACE");
+	k.key_rebuild = env_unless_zero("RTK_AMD_KEY_REBUILD");
+	return k;
+}
+
+static_assert(sizeof(InTri) == RTK_BUILD_SIZEOF_INTRI && sizeof(BinNode) == RTK_BUILD_SIZEOF_BINNODE && sizeof(Climb) == RTK_BUILD_SIZEOF_CLIMB &&
+	sizeof(LevelState) == RTK_BUILD_SIZEOF_LEVELSTATE && sizeof(MeshSrc) == RTK_BUILD_SIZEOF_MESHSRC && sizeof(DevNode) == RTK_BUILD_SIZEOF_DEVNODE,
+	"rtk_build_layout.h sizes the workspace by these");
+static_assert(REFIT_TILE == RTK_BUILD_REFIT_TILE && COLLAPSE_BLOCK == RTK_BUILD_COLLAPSE_BLOCK && COLLAPSE_RING == RTK_BUILD_COLLAPSE_RING, "rtk_build_layout.h");
+
+// ---- one build: what its stages share ----
+struct Build {
+	const rtk_scene_desc *desc = nullptr;
+	uint32_t n = 0;
+	int device = 0, num_cus = 0;
+	BuildKnobs knobs;
+	BuildParams bp;
+	std::vector<uint64_t> mesh_base;
+	std::vector<MeshPlan> plans;
+	// what n and the knobs decide
+	bool packed = false;              // the triangle's number fits under a 40-bit code in one sort word
+	uint32_t packed_bits = 40u;       // the width of that code
+	uint32_t num_tiles = 0;
+	bool tile_mode = false;           // more than one refit tile, and enough triangles: the subtrees inside a tile are collapsed by k_collapse_tile,
+	                                  // only the nodes above them go through the level-by-level collapse
+	uint32_t top_cap = 0;             // nodes above the tiles that the workspace holds
+	// the workspace (its mutex is held by build_impl), the two streams, the scene under construction
+	Workspace *ws = nullptr;
+	hipStream_t bs = nullptr;         // the build's stream
+	hipStream_t cs = nullptr;         // where the tiles' own kernels run: ws->side once it has forked off, else bs
+	bool forked = false;
+	bool side_busy = false;           // kernels on ws->side may still be reading the workspace
+	BuildResults *results = nullptr;
+	rtk_dev_scene *ds = nullptr;
+	// the layout (byte offsets) and its pointers; what else the stages hand on
+	BuildLayout L;
+	InTri *in_tris = nullptr;
+	float *d_cent = nullptr, *d_area = nullptr;
+	uint32_t *d_bounds = nullptr, *d_vidx_in = nullptr, *d_tile_count = nullptr, *d_tile_base = nullptr, *d_depth_word = nullptr, *d_tile_nclimb = nullptr, *d_tile_nroots = nullptr, *d_top_level = nullptr;
+	int2 *d_lr = nullptr;
+	uint2 *d_range = nullptr;
+	Climb *d_climbers = nullptr;
+	unsigned long long *d_half = nullptr, *d_root_info = nullptr, *d_mesh_base = nullptr;
+	int *d_climb_idx = nullptr, *d_root = nullptr, *d_root_list = nullptr;
+	BinNode *d_bin = nullptr;
+	DevNode *d_nodes_tmp = nullptr;
+	uint4 *d_top_refs = nullptr;
+	MeshSrc *d_mesh_src = nullptr;
+	LevelState *d_ring = nullptr;
+	CollapseBufs cb = {};
+	TopAux top_aux = { nullptr, nullptr };
+	std::vector<MeshSrc> mesh_src;            // sources of async copies: they live until the final wait
+	std::vector<unsigned long long> mb;
+	const unsigned long long *keys = nullptr; // sorted. packed: all different (the index is part of the word), in ascending order
+	const uint32_t *vals = nullptr;
+	DevTri *d_tris = nullptr;
+	EmitSrc emit_src = {};
+	// the collapse
+	void *node_mem = nullptr;         // [DevNode x node_cap | DevNodeQ x node_cap], owned by the scene (the last of its allocs)
+	size_t node_cap = 0;
+	LevelState h_state = {};
+	bool tiles_done = false;
+	uint32_t total_nodes = 0, depth = 0;
+	uint32_t equal_codes = 0;         // sorted neighbours with one and the same Morton code (counted by k_refit_tile)
+	std::chrono::steady_clock::time_point t_begin, t_last;
+
+	template <typename T> T *at(size_t offset) const { return offset == RTK_BUILD_NO_BUFFER ? nullptr : reinterpret_cast<T *>(ws->base + offset); }
+
+	void stage(const char *name)
+	{
+		if (knobs.host_time) fprintf(stderr, "rtk_amd build host: %-10s at %8.3f ms\n", name, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+		if (!knobs.timing) return;
 		(void)hipDeviceSynchronize();
 		const auto now = std::chrono::steady_clock::now();
 		fprintf(stderr, "rtk_amd build: %-10s %8.3f ms\n", name, std::chrono::duration<double, std::milli>(now - t_last).count());
 		t_last = now;
-	};
+	}
 
-	int device = 0;
-	BUILD_CHECK(hipGetDevice(&device));
-	if (device < 0 || device >= RTK_MAX_DEVICES) { rtk_set_error("rtk_dev_scene_build: device %d out of range", device); return nullptr; }
-	const int num_cus = cached_cu_count(device);
+	// The one way out of a failed build; every stage returns what these return (false). Before the scene exists nothing has been
+	// enqueued and there is nothing to free. From then on kernels already enqueued may still read or write the persistent
+	// workspace (the next build on this device reuses it as soon as build_impl lets go of the workspace mutex) and the scene's
+	// own allocations (freed here): BOTH streams are joined first, the side stream if anything was enqueued on it.
+	bool give_up()
+	{
+		if (!ds) return false;
+		(void)hipStreamSynchronize(bs);
+		if (side_busy) (void)hipStreamSynchronize(ws->side);
+		rtk_dev_scene_free(ds);
+		ds = nullptr;
+		return false;
+	}
+	// (the error text is made before the streams are joined: the wait may change the last error)
+	bool fail(const char *what)
+	{
+		rtk_set_error("device build: %s: %s", what, hipGetErrorString(hipGetLastError()));
+		return give_up();
+	}
+	// a device allocation the scene owns
+	char *dev_alloc(size_t bytes)
+	{
+		void *p = nullptr;
+		if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr;
+		ds->allocs.push_back(p);
+		ds->total_bytes += bytes;
+		return (char *)p;
+	}
+};
 
-	// ---- plan the meshes -----------------------------------------------------------------
-	std::vector<MeshPlan> plans(desc->num_meshes);
-	size_t upload_bytes = 0;
+// ---- plan the meshes: host only; everything that can be wrong with the description is found here ----
+bool plan_meshes(Build &b)
+{
+	const rtk_scene_desc *desc = b.desc;
+	b.plans.assign(desc->num_meshes, MeshPlan());
 	for (size_t mi = 0; mi < desc->num_meshes; mi++) {
 		const rtk_mesh *m = &desc->meshes[mi];
-		MeshPlan &pl = plans[mi];
+		MeshPlan &pl = b.plans[mi];
 		const size_t nt = m->num_triangles;
 		if (nt == 0) continue;
 		if (!m->position_cb && m->position.type != RTK_TYPE_DEFAULT && m->position.type != RTK_TYPE_REAL && m->position.type != RTK_TYPE_F32 &&
-			m->position.type != RTK_TYPE_F64) { rtk_set_error("rtk_dev_scene_build: mesh %zu: bad position type %d", mi, (int)m->position.type); return nullptr; }
+			m->position.type != RTK_TYPE_F64) { rtk_set_error("rtk_dev_scene_build: mesh %zu: bad position type %d", mi, (int)m->position.type); return false; }
+		// RTK_TYPE_DEFAULT on an index buffer means 32-bit indices (the reference's default index type, rtk.c:1049-1059)
 		if (!m->index_cb && m->index.data && m->index.type != RTK_TYPE_DEFAULT && m->index.type != RTK_TYPE_U16 && m->index.type != RTK_TYPE_U32) {
-			rtk_set_error("rtk_dev_scene_build: mesh %zu: bad index type %d", mi, (int)m->index.type); return nullptr; }
-		if (m->position_cb || m->index_cb || n < 2) { pl.on_host_decode = true; continue; }
-		if (!m->position.data) { rtk_set_error("rtk_dev_scene_build: mesh %zu has no positions", mi); return nullptr; }
+			rtk_set_error("rtk_dev_scene_build: mesh %zu: bad index type %d", mi, (int)m->index.type); return false; }
+		if (m->position_cb || m->index_cb || b.n < 2) { pl.on_host_decode = true; continue; }
+		if (!m->position.data) { rtk_set_error("rtk_dev_scene_build: mesh %zu has no positions", mi); return false; }
 		pl.f64 = m->position.type == RTK_TYPE_F64;
 		pl.pstride = m->position.stride ? m->position.stride : (pl.f64 ? 24 : 12);
 		pl.pos_src = (const char *)m->position.data;
@@ -1987,13 +1853,11 @@ static rtk_dev_scene *build_impl(const rtk_scene_desc *desc, uint32_t force_bits
 		uint64_t max_vertex = 3ull * nt - 1;
 		if (m->index.data) {
 			const bool u16 = m->index.type == RTK_TYPE_U16;
-			// RTK_TYPE_DEFAULT on an index buffer means 32-bit indices (the reference's default index type, rtk.c:1049-1059)
-			if (!u16 && m->index.type != RTK_TYPE_U32 && m->index.type != RTK_TYPE_DEFAULT) { rtk_set_error("rtk_dev_scene_build: bad index type"); return nullptr; }
 			pl.idx_kind = u16 ? 1 : 2;
 			pl.istride = m->index.stride ? m->index.stride : (u16 ? 6 : 12);
 			pl.idx_src = (const char *)m->index.data;
 			pl.idx_on_device = rtk_is_device_ptr(m->index.data);
-			if (pl.idx_on_device && !pl.pos_on_device) { rtk_set_error("rtk_dev_scene_build: mesh %zu has device indices but host positions", mi); return nullptr; }
+			if (pl.idx_on_device && !pl.pos_on_device) { rtk_set_error("rtk_dev_scene_build: mesh %zu has device indices but host positions", mi); return false; }
 			if (!pl.idx_on_device) {
 				if (!pl.pos_on_device) {
 					// the position buffer's extent is only known through the largest index used
@@ -2010,106 +1874,100 @@ static rtk_dev_scene *build_impl(const rtk_scene_desc *desc, uint32_t force_bits
 			}
 		}
 		if (!pl.pos_on_device) pl.pbytes = (size_t)max_vertex * pl.pstride + (pl.f64 ? 24 : 12);
-		upload_bytes += rtk_padded(pl.pbytes) + rtk_padded(pl.ibytes);
 	}
+	return true;
+}
 
-	if (n < 2) {
-		std::vector<float> tiny_pos;
-		std::vector<uint32_t> tiny_vidx;
-		for (size_t mi = 0; mi < desc->num_meshes; mi++) {
-			const rtk_mesh *m = &desc->meshes[mi];
-			if (m->num_triangles == 0) continue;
-			tiny_pos.resize(9 * m->num_triangles);
-			tiny_vidx.resize(3 * m->num_triangles);
-			decode_mesh_on_host(m, tiny_pos.data(), tiny_vidx.data());
-		}
-		return build_tiny(desc, mesh_base, tiny_pos, tiny_vidx);
-	}
+// ---- what n and the knobs decide before anything is placed: sort words, key width, tile mode ----
+void plan_build(Build &b, uint32_t force_bits)
+{
+	const uint32_t n = b.n;
+	// index fits under a 40-bit code in one word
+	b.packed = n < (1u << 24) && b.knobs.sort_packed;
+	// Key width from n: ceil(log2 n) + 8 bits of the code, rounded up to whole 8-bit passes -- every triangle still gets hundreds
+	// of cells of its own on average, the splits below that are decided by the triangle's number (words are all different). The lab
+	// found identical trees down to 30 bits at 1M triangles, and the 10M-triangle build has the same 4 709 302 nodes at 32 bits as at
+	// 40 (profiles/r04_build_ab.log): 32 bits = FOUR passes wherever the index fits the word (n < 2^24), three below 64 k triangles.
+	uint32_t lg = 0;
+	while ((1ull << lg) < (unsigned long long)n) lg++;
+	b.packed_bits = ((lg + 8u + 7u) / 8u) * 8u;
+	if (b.packed_bits < 24u) b.packed_bits = 24u;
+	if (b.packed_bits > 40u) b.packed_bits = 40u;
+	if (force_bits) b.packed_bits = force_bits;
+	if (b.knobs.key_bits) b.packed_bits = b.knobs.key_bits;
+	b.num_tiles = (n + REFIT_TILE - 1u) / REFIT_TILE;
+	b.tile_mode = b.num_tiles > 1u && (uint64_t)n >= b.knobs.tile_min;
+	b.top_cap = std::min<uint32_t>(n / 2u, b.knobs.top_cap);
+	rtk_sah_costs(&b.bp.cost_node, &b.bp.cost_tri);
+	b.bp.max_leaf = b.knobs.max_leaf;
+}
 
-	// ---- workspace -----------------------------------------------------------------------
-	// 63-bit Morton keys resolve 2^-21 of the scene per axis; for < 2^24 triangles the low bits never decide a
-	// split that matters (lab: identical visit counts down to 30 bits at 1M triangles), so the top 40 bits are kept
-	// and share one 64-bit word with the triangle's number: 5 radix passes over 8-byte words (see k_morton) instead of
-	// 8 over 12-byte pairs.
-	const uint32_t key_bits = 63u;
-	const size_t sort_words = rtk_sort_scratch_words(n);
-	const size_t collapse_blocks = ((size_t)n + COLLAPSE_BLOCK - 1) / COLLAPSE_BLOCK;
-	size_t need = upload_bytes + 64 * 256;
-	need += rtk_padded((size_t)n * sizeof(InTri)) + rtk_padded((size_t)n * 12) + rtk_padded((desc->num_meshes + 1) * sizeof(MeshSrc));   // staged triangles, doubled centroids, where each mesh is gathered from
-	need += 2 * rtk_padded((size_t)n * 8) + 2 * rtk_padded((size_t)n * 4);                  // keys a/b, vals a/b
-	need += rtk_padded(sort_words * 4) + rtk_padded(64) + rtk_padded(mesh_base.size() * 8);     // sort scratch, bounds, mesh_base
-	need += 2 * rtk_padded((size_t)n * 8) + rtk_padded((size_t)n * 12) + rtk_padded((size_t)n * 16) + rtk_padded((size_t)n * 4) + rtk_padded(16);   // lr, range, climbers, halves, arrive, root
-	need += rtk_padded((size_t)n * sizeof(BinNode));                                    // bin
-	need += rtk_padded((size_t)n * 16) + 2 * rtk_padded((size_t)n * 4) + rtk_padded(collapse_blocks * 4) + rtk_padded(sizeof(LevelState) * COLLAPSE_RING);   // collapse: dec, info, jobs, block sums, ring
-	need += rtk_padded((size_t)n * sizeof(DevNode));                                    // nodes (worst case; unused in tile mode)
-	need += 4 * rtk_padded(((size_t)n / REFIT_TILE + 4) * 4) + rtk_padded(16) + rtk_padded((size_t)n * 4);   // tile counts, tile bases, climbers and roots per tile, depth word, areas
-	Workspace &ws = g_workspace[device];
-	std::lock_guard<std::mutex> ws_lock(ws.mutex);
-	if (ws.cap < need) {
-		if (ws.base) (void)hipFree(ws.base);
-		ws.base = nullptr;
-		ws.cap = 0;
-		const size_t want = need + need / 8;
-		if (hipMalloc(&ws.base, want) != hipSuccess) {
-			(void)hipGetLastError();
-			if (hipMalloc(&ws.base, need) != hipSuccess) { ws.base = nullptr; rtk_set_error("device build: out of device memory (%zu bytes of workspace)", need); return nullptr; }
-			ws.cap = need;
-		} else ws.cap = want;
-	}
-	Arena ar = { ws.base, ws.cap, 0 };
-	if (!ws.stream && hipStreamCreateWithFlags(&ws.stream, hipStreamNonBlocking) != hipSuccess) { ws.stream = nullptr; rtk_set_error("device build: hipStreamCreate failed"); return nullptr; }
+// ---- the workspace: sized and placed by the one carve of rtk_build_layout.h; the build's stream and pinned results ----
+bool prepare_workspace(Build &b)
+{
+	Workspace &ws = *b.ws;
+	std::vector<BuildUpload> uploads(b.plans.size());
+	for (size_t mi = 0; mi < b.plans.size(); mi++) uploads[mi] = BuildUpload{ b.plans[mi].ibytes, b.plans[mi].pbytes };
+	BuildLayout &L = b.L;
+	if (!rtk_build_layout(b.n, uploads, b.packed, b.tile_mode, b.top_cap, rtk_sort_scratch_words(b.n), &L)) { rtk_set_error("device build: workspace too small (internal error)"); return false; }
+	if (!workspace_grow(ws, L.bytes, 8) || L.bytes > ws.cap) { rtk_set_error("device build: out of device memory (%zu bytes of workspace)", L.bytes); return false; }
+	if (!ws.stream && hipStreamCreateWithFlags(&ws.stream, hipStreamNonBlocking) != hipSuccess) { ws.stream = nullptr; rtk_set_error("device build: hipStreamCreate failed"); return false; }
 	if (!ws.h_results && hipHostMalloc(reinterpret_cast<void **>(&ws.h_results), sizeof(BuildResults), hipHostMallocDefault) != hipSuccess) {
 		(void)hipGetLastError();
 		ws.h_results = nullptr;
 		rtk_set_error("device build: no pinned host memory for the build's results");
-		return nullptr;
+		return false;
 	}
-	BuildResults *const results = ws.h_results;
-	const hipStream_t bs = ws.stream;
+	b.results = ws.h_results;
+	b.bs = b.cs = ws.stream;
+	b.in_tris = b.at<InTri>(L.in_tris); b.d_cent = b.at<float>(L.cent); b.d_bounds = b.at<uint32_t>(L.bounds); b.d_mesh_src = b.at<MeshSrc>(L.mesh_src);
+	b.d_lr = b.at<int2>(L.lr); b.d_range = b.at<uint2>(L.range); b.d_climbers = b.at<Climb>(L.climbers); b.d_root = b.at<int>(L.root); b.d_bin = b.at<BinNode>(L.bin);
+	b.d_half = b.at<unsigned long long>(L.half);      // two subtrees meet through the first n words
+	b.d_climb_idx = b.at<int>(L.arrive);              // pass 2 finds its climbers through their positions, packed per tile, and d_tile_nclimb
+	b.d_tile_count = b.at<uint32_t>(L.tile_count); b.d_tile_base = b.at<uint32_t>(L.tile_base); b.d_tile_nclimb = b.at<uint32_t>(L.tile_nclimb); b.d_tile_nroots = b.at<uint32_t>(L.tile_nroots);
+	b.d_depth_word = b.at<uint32_t>(L.depth_word); b.d_area = b.at<float>(L.area); b.d_nodes_tmp = b.at<DevNode>(L.nodes_tmp);
+	b.d_top_refs = b.at<uint4>(L.top_refs); b.d_top_level = b.at<uint32_t>(L.top_level); b.d_root_info = b.at<unsigned long long>(L.root_info); b.d_root_list = b.at<int>(L.root_list);
+	b.cb = CollapseBufs{ b.at<int>(L.jobs), b.at<int4>(L.dec), b.at<uint32_t>(L.info), b.at<uint32_t>(L.sums) };
+	b.d_ring = b.at<LevelState>(L.ring);
+	b.top_aux = TopAux{ b.d_top_refs, b.d_top_level };
 	// a mesh that already lives in device memory was written by the caller's own work, possibly still in flight on the NULL
 	// stream or a blocking stream: that work is waited for here (a build stream of our own does not order itself behind it)
-	{
-		bool device_mesh = false;
-		for (size_t mi = 0; mi < desc->num_meshes; mi++) device_mesh = device_mesh || plans[mi].pos_on_device || plans[mi].idx_on_device;
-		if (device_mesh) BUILD_CHECK(hipStreamSynchronize(0));
-	}
-	stage("workspace");
+	bool device_mesh = false;
+	for (const MeshPlan &pl : b.plans) device_mesh = device_mesh || pl.pos_on_device || pl.idx_on_device;
+	if (device_mesh && hipStreamSynchronize(0) != hipSuccess) return b.fail("hipStreamSynchronize(0)");
+	b.stage("workspace");
+	return true;
+}
 
-	// ---- 1 ingest ------------------------------------------------------------------
-	InTri *in_tris = ar.take<InTri>(n);
-	float *d_cent = ar.take<float>(3 * (size_t)n);
-	uint32_t *d_bounds = ar.take<uint32_t>(16);
+// ---- 1 ingest: the scene object; every mesh decoded into staged triangles, doubled centroids and their bounds ----
+bool ingest(Build &b)
+{
+	const rtk_scene_desc *desc = b.desc;
+	const hipStream_t bs = b.bs;
 	// the scene keeps the original vertex indices in input order (for rtk_hit.vertex[].index: rtk_scene_side_arrays) only if some
 	// mesh HAS indices; with implicit indices everywhere they are 3 * triangle + corner
 	bool any_indexed = false;
-	for (size_t mi = 0; mi < desc->num_meshes; mi++) any_indexed = any_indexed || (desc->meshes[mi].num_triangles && (plans[mi].on_host_decode || plans[mi].idx_kind != 0));
-	rtk_dev_scene *ds = new rtk_dev_scene();
-	ds->device = device;
-	ds->num_cus = num_cus;
-	ds->mesh_base = mesh_base;
+	for (size_t mi = 0; mi < desc->num_meshes; mi++) any_indexed = any_indexed || (desc->meshes[mi].num_triangles && (b.plans[mi].on_host_decode || b.plans[mi].idx_kind != 0));
+	rtk_dev_scene *ds = b.ds = new rtk_dev_scene();
+	ds->device = b.device;
+	ds->num_cus = b.num_cus;
+	ds->mesh_base = b.mesh_base;
 	ds->side_ready = false;
-	uint32_t *d_vidx_in = nullptr;
 	if (any_indexed) {
-		void *pv = nullptr;
-		if (hipMalloc(&pv, 3 * (size_t)n * 4) != hipSuccess) { (void)hipGetLastError(); delete ds; rtk_set_error("device build: out of device memory (vertex indices)"); return nullptr; }
-		ds->allocs.push_back(pv); ds->total_bytes += 3 * (size_t)n * 4;
-		d_vidx_in = (uint32_t *)pv;
-		ds->d_vidx_in = d_vidx_in;
+		b.d_vidx_in = (uint32_t *)b.dev_alloc(3 * (size_t)b.n * 4);
+		if (!b.d_vidx_in) { (void)hipGetLastError(); rtk_set_error("device build: out of device memory (vertex indices)"); return b.give_up(); }
+		ds->d_vidx_in = b.d_vidx_in;
 	}
-	std::vector<MeshSrc> mesh_src(desc->num_meshes + 1, MeshSrc{ nullptr, 0ull });
-	// Every exit that gives the scene up from here on joins the build stream first (kernels already enqueued may still touch
-	// the workspace and the scene's allocations)
-#define INGEST_FAIL(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { rtk_set_error("device build: %s failed: %s (line %d)", #expr, hipGetErrorString(e__), __LINE__); (void)hipStreamSynchronize(bs); rtk_dev_scene_free(ds); return nullptr; } } while (0)
+	b.mesh_src.assign(desc->num_meshes + 1, MeshSrc{ nullptr, 0ull });
 	// centroid bounds: min words start at all ones, max words at zero (ordered-uint encoding): two fills, nothing the host
 	// waits for. The decode kernels below take them in passing.
-	INGEST_FAIL(hipMemsetAsync(d_bounds, 0xff, 12, bs));
-	INGEST_FAIL(hipMemsetAsync(d_bounds + 3, 0, 12, bs));
+	if (hipMemsetAsync(b.d_bounds, 0xff, 12, bs) != hipSuccess || hipMemsetAsync(b.d_bounds + 3, 0, 12, bs) != hipSuccess) return b.fail("memset");
 	for (size_t mi = 0; mi < desc->num_meshes; mi++) {
 		const rtk_mesh *m = &desc->meshes[mi];
-		const MeshPlan &pl = plans[mi];
+		const MeshPlan &pl = b.plans[mi];
 		const size_t nt = m->num_triangles;
 		if (nt == 0) continue;
-		const uint32_t base = (uint32_t)mesh_base[mi];
+		const uint32_t base = (uint32_t)b.mesh_base[mi];
 		if (pl.on_host_decode) {
 			std::vector<float> pos9(9 * nt);
 			std::vector<uint32_t> vidx3(3 * nt);
@@ -2119,178 +1977,102 @@ static rtk_dev_scene *build_impl(const rtk_scene_desc *desc, uint32_t force_bits
 				for (int c = 0; c < 9; c++) recs[t].p[c] = pos9[9 * t + c];
 				for (int c = 0; c < 3; c++) recs[t].vi[c] = vidx3[3 * t + c];
 			}
-			INGEST_FAIL(hipMemcpyAsync(in_tris + base, recs.data(), recs.size() * sizeof(InTri), hipMemcpyHostToDevice, bs));
+			if (hipMemcpyAsync(b.in_tris + base, recs.data(), recs.size() * sizeof(InTri), hipMemcpyHostToDevice, bs) != hipSuccess) return b.fail("copy of host-decoded triangles");
 			// centroids, vertex indices and centroid bounds of these records (the decode kernels below do this in passing)
-			const unsigned bblocks = (unsigned)std::min<size_t>((nt + BOUNDS_BLOCK - 1) / BOUNDS_BLOCK, (size_t)num_cus);
-			hipLaunchKernelGGL(k_bounds, dim3(bblocks), dim3(BOUNDS_BLOCK), 0, bs, in_tris, base, (uint32_t)nt, d_bounds, d_cent, d_vidx_in);
-			INGEST_FAIL(hipStreamSynchronize(bs));      // (recs goes out of scope)
+			const unsigned bblocks = (unsigned)std::min<size_t>((nt + BOUNDS_BLOCK - 1) / BOUNDS_BLOCK, (size_t)b.num_cus);
+			hipLaunchKernelGGL(k_bounds, dim3(bblocks), dim3(BOUNDS_BLOCK), 0, bs, b.in_tris, base, (uint32_t)nt, b.d_bounds, b.d_cent, b.d_vidx_in);
+			if (hipStreamSynchronize(bs) != hipSuccess) return b.fail("host-decoded mesh");      // (recs goes out of scope)
 			continue;
 		}
 		// raw buffers go to the device as they are; the decode runs there
 		const char *idx_ptr = pl.idx_src, *pos_ptr = pl.pos_src;
 		if (pl.ibytes) {
-			char *d = ar.take<char>(pl.ibytes);
-			INGEST_FAIL(upload_staged(d, pl.idx_src, pl.ibytes, bs));
+			char *d = b.at<char>(b.L.mesh_idx[mi]);
+			if (upload_staged(d, pl.idx_src, pl.ibytes, bs) != hipSuccess) return b.fail("upload of indices");
 			idx_ptr = d;
 		}
 		if (pl.pbytes) {
-			char *d = ar.take<char>(pl.pbytes);
-			INGEST_FAIL(upload_staged(d, pl.pos_src, pl.pbytes, bs));
+			char *d = b.at<char>(b.L.mesh_pos[mi]);
+			if (upload_staged(d, pl.pos_src, pl.pbytes, bs) != hipSuccess) return b.fail("upload of positions");
 			pos_ptr = d;
 		}
 		// implicit indices and float positions whose three components can be read as floats in place: gathered in place by k_emit_tris
-		static const bool allow_direct = !(getenv("RTK_AMD_BUILD_DIRECT") && atoi(getenv("RTK_AMD_BUILD_DIRECT")) == 0);
-		const bool direct = allow_direct && pl.idx_kind == 0 && !pl.f64 && (pl.pstride % 4u) == 0u && ((uintptr_t)pos_ptr % 4u) == 0u;
-		if (direct) mesh_src[mi] = MeshSrc{ pos_ptr, (unsigned long long)pl.pstride };
-		const unsigned iblocks = (unsigned)std::min<size_t>((nt + INGEST_BLOCK - 1) / INGEST_BLOCK, (size_t)num_cus);
-		if (pl.idx_kind == 0) launch_ingest<0>(pl.f64, direct, iblocks, pos_ptr, pl.pstride, idx_ptr, pl.istride, (uint32_t)nt, base, in_tris, d_cent, d_vidx_in, d_bounds, bs);
-		else if (pl.idx_kind == 1) launch_ingest<1>(pl.f64, false, iblocks, pos_ptr, pl.pstride, idx_ptr, pl.istride, (uint32_t)nt, base, in_tris, d_cent, d_vidx_in, d_bounds, bs);
-		else launch_ingest<2>(pl.f64, false, iblocks, pos_ptr, pl.pstride, idx_ptr, pl.istride, (uint32_t)nt, base, in_tris, d_cent, d_vidx_in, d_bounds, bs);
-		INGEST_FAIL(hipGetLastError());
+		const bool direct = b.knobs.direct && pl.idx_kind == 0 && !pl.f64 && (pl.pstride % 4u) == 0u && ((uintptr_t)pos_ptr % 4u) == 0u;
+		if (direct) b.mesh_src[mi] = MeshSrc{ pos_ptr, (unsigned long long)pl.pstride };
+		const unsigned iblocks = (unsigned)std::min<size_t>((nt + INGEST_BLOCK - 1) / INGEST_BLOCK, (size_t)b.num_cus);
+		if (pl.idx_kind == 0) launch_ingest<0>(pl.f64, direct, iblocks, pos_ptr, pl.pstride, idx_ptr, pl.istride, (uint32_t)nt, base, b.in_tris, b.d_cent, b.d_vidx_in, b.d_bounds, bs);
+		else if (pl.idx_kind == 1) launch_ingest<1>(pl.f64, false, iblocks, pos_ptr, pl.pstride, idx_ptr, pl.istride, (uint32_t)nt, base, b.in_tris, b.d_cent, b.d_vidx_in, b.d_bounds, bs);
+		else launch_ingest<2>(pl.f64, false, iblocks, pos_ptr, pl.pstride, idx_ptr, pl.istride, (uint32_t)nt, base, b.in_tris, b.d_cent, b.d_vidx_in, b.d_bounds, bs);
+		if (hipGetLastError() != hipSuccess) return b.fail("ingest launch");
 	}
-#undef INGEST_FAIL
-	stage("ingest");
+	b.stage("ingest");
+	return true;
+}
 
-	BuildParams bp;
-	rtk_sah_costs(&bp.cost_node, &bp.cost_tri);
-	// leaves of at most three triangles: a leaf of fewer than four is one partial group for the reference's group-of-four rule
-	// (rtk.c:302-336: double-precision edge functions, no redo), which is all the hand-written packet kernel implements; with
-	// cn = 0.5 the SAH rule made 1.008 triangles per leaf at a limit of 8, so nothing of substance changes
-	bp.max_leaf = (uint32_t)env_float("RTK_AMD_MAX_LEAF", 3.0f);
-	if (bp.max_leaf < 1) bp.max_leaf = 1;
-	if (bp.max_leaf > 63) bp.max_leaf = 63;     // 6-bit count in the blob's leaf header (rtk.c:188)
+// ---- 2 bounds, 3 morton, 4 sort: no allocation, no host synchronisation ----
+// 63-bit Morton keys resolve 2^-21 of the scene per axis; for < 2^24 triangles the low bits never decide a
+// split that matters (lab: identical visit counts down to 30 bits at 1M triangles), so the top 40 bits are kept
+// and share one 64-bit word with the triangle's number: 5 radix passes over 8-byte words (see k_morton) instead of
+// 8 over 12-byte pairs.
+constexpr uint32_t BUILD_KEY_BITS = 63u;
+bool keys_and_sort(Build &b)
+{
+	const uint32_t n = b.n;
+	unsigned long long *keys_a = b.at<unsigned long long>(b.L.keys_a), *keys_b = b.at<unsigned long long>(b.L.keys_b);
+	uint32_t *vals_a = b.at<uint32_t>(b.L.vals_a), *vals_b = b.at<uint32_t>(b.L.vals_b);       // (NULL when packed)
+	uint32_t *sort_scratch = b.at<uint32_t>(b.L.sort_scratch);
+	hipLaunchKernelGGL(k_morton, dim3((n + 255u) / 256u), dim3(256), 0, b.bs, b.d_cent, n, b.d_bounds, keys_a, vals_a, 63u - (b.packed ? b.packed_bits : BUILD_KEY_BITS));
+	if (hipGetLastError() != hipSuccess) return b.fail("morton launch");
+	b.stage("morton");
+	const bool in_b = b.packed ? rtk_sort_words_async(keys_a, keys_b, n, 24u, 24u + b.packed_bits, sort_scratch, b.bs)
+	                           : rtk_sort_pairs_async(keys_a, keys_b, vals_a, vals_b, n, BUILD_KEY_BITS, sort_scratch, b.bs);
+	b.keys = in_b ? keys_b : keys_a;
+	b.vals = b.packed ? nullptr : (in_b ? vals_b : vals_a);
+	if (hipGetLastError() != hipSuccess) return b.fail("sort launch");
+	b.stage("sort");
+	return true;
+}
 
-	// ---- 2 bounds, 3 morton -----------------------------------------------------------
-	unsigned long long *keys_a = ar.take<unsigned long long>(n), *keys_b = ar.take<unsigned long long>(n);
-	// index fits under a 40-bit code in one word (RTK_AMD_SORT_PACKED=0: the >= 2^24-triangle path, for tests on small scenes)
-	const bool packed = n < (1u << 24) && !(getenv("RTK_AMD_SORT_PACKED") && atoi(getenv("RTK_AMD_SORT_PACKED")) == 0);
-	// Key width from n: ceil(log2 n) + 8 bits of the code, rounded up to whole 8-bit passes -- every triangle still gets hundreds
-	// of cells of its own on average, the splits below that are decided by the triangle's number (words are all different). The lab
-	// found identical trees down to 30 bits at 1M triangles, and the 10M-triangle build has the same 4 709 302 nodes at 32 bits as at
-	// 40 (profiles/r04_build_ab.log): 32 bits = FOUR passes wherever the index fits the word (n < 2^24), three below 64 k triangles.
-	uint32_t packed_bits = 40u;
-	{
-		uint32_t lg = 0;
-		while ((1ull << lg) < (unsigned long long)n) lg++;
-		packed_bits = ((lg + 8u + 7u) / 8u) * 8u;
-		if (packed_bits < 24u) packed_bits = 24u;
-		if (packed_bits > 40u) packed_bits = 40u;
-		if (force_bits) packed_bits = force_bits;
-		if (getenv("RTK_AMD_KEY_BITS")) { const int kb = atoi(getenv("RTK_AMD_KEY_BITS")); if (kb >= 8 && kb <= 40 && kb % 8 == 0) packed_bits = (uint32_t)kb; }
-	}
-	uint32_t *vals_a = packed ? nullptr : ar.take<uint32_t>(n), *vals_b = packed ? nullptr : ar.take<uint32_t>(n);
-	uint32_t *sort_scratch = ar.take<uint32_t>(sort_words);
-	MeshSrc *d_mesh_src = ar.take<MeshSrc>(desc->num_meshes + 1);
-	{
-		hipLaunchKernelGGL(k_morton, dim3((n + 255u) / 256u), dim3(256), 0, bs, d_cent, n, d_bounds, keys_a, vals_a, 63u - (packed ? packed_bits : key_bits));
-		if (hipGetLastError() != hipSuccess) { rtk_set_error("device build: morton launch failed"); (void)hipStreamSynchronize(bs); rtk_dev_scene_free(ds); return nullptr; }
-	}
-	stage("morton");
-
-	// ---- 4 sort: no allocation, no host synchronisation ------------------------------------
-	const bool in_b = packed ? rtk_sort_words_async(keys_a, keys_b, n, 24u, 24u + packed_bits, sort_scratch, bs)
-	                         : rtk_sort_pairs_async(keys_a, keys_b, vals_a, vals_b, n, key_bits, sort_scratch, bs);
-	const unsigned long long *keys = in_b ? keys_b : keys_a;      // packed: all different (the index is part of the word), in ascending order
-	const uint32_t *vals = packed ? nullptr : (in_b ? vals_b : vals_a);
-	if (hipGetLastError() != hipSuccess) { rtk_set_error("device build: sort launch failed"); (void)hipStreamSynchronize(bs); rtk_dev_scene_free(ds); return nullptr; }
-	stage("sort");
-
-	// ---- 5 emit: final triangle records in Morton order ----------------------------------
-	const std::vector<unsigned long long> mb(mesh_base.begin(), mesh_base.end());   // source of an async copy: lives until the final sync
-	bool side_busy = false;             // kernels on ws.side may still be reading the workspace
-	// Every exit that gives the scene up joins BOTH streams first: kernels already enqueued may still read or write the
-	// persistent workspace (the next build on this device reuses it as soon as the workspace mutex is released) and the
-	// scene's own allocations (freed below).
-	auto give_up = [&]() -> rtk_dev_scene * {
-		(void)hipStreamSynchronize(bs);
-		if (side_busy) (void)hipStreamSynchronize(ws.side);
-		rtk_dev_scene_free(ds);
-		return nullptr;
-	};
-	auto fail = [&](const char *what) -> rtk_dev_scene * {
-		rtk_set_error("device build: %s: %s", what, hipGetErrorString(hipGetLastError()));
-		return give_up();
-	};
-	auto dev_alloc = [&](size_t bytes) -> char * {
-		void *p = nullptr;
-		if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr;
-		ds->allocs.push_back(p);
-		ds->total_bytes += bytes;
-		return (char *)p;
-	};
+// ---- 5 emit: final triangle records in Morton order ----
+bool emit(Build &b)
+{
+	const uint32_t n = b.n;
+	b.mb.assign(b.mesh_base.begin(), b.mesh_base.end());
 	// the triangle records; the mesh table (a few words the scene keeps: rtk_scene_side_arrays reads it)
-	const size_t o_mb = rtk_padded((size_t)n * sizeof(DevTri)), tri_block = o_mb + rtk_padded(mb.size() * 8);
-	char *tri_mem = dev_alloc(tri_block);
-	if (!tri_mem) return fail("out of device memory");
-	DevTri *d_tris = (DevTri *)tri_mem;
-	unsigned long long *d_mesh_base = (unsigned long long *)(tri_mem + o_mb);
-	ds->d_mesh_base = d_mesh_base;
-	{
-		if (hipMemcpyAsync(d_mesh_base, mb.data(), mb.size() * 8, hipMemcpyHostToDevice, bs) != hipSuccess ||
-			hipMemcpyAsync(d_mesh_src, mesh_src.data(), mesh_src.size() * sizeof(MeshSrc), hipMemcpyHostToDevice, bs) != hipSuccess) return fail("copy");
-	}
+	const size_t o_mb = rtk_padded((size_t)n * sizeof(DevTri)), tri_block = o_mb + rtk_padded(b.mb.size() * 8);
+	char *tri_mem = b.dev_alloc(tri_block);
+	if (!tri_mem) return b.fail("out of device memory");
+	b.d_tris = (DevTri *)tri_mem;
+	b.d_mesh_base = (unsigned long long *)(tri_mem + o_mb);
+	b.ds->d_mesh_base = b.d_mesh_base;
+	if (hipMemcpyAsync(b.d_mesh_base, b.mb.data(), b.mb.size() * 8, hipMemcpyHostToDevice, b.bs) != hipSuccess ||
+		hipMemcpyAsync(b.d_mesh_src, b.mesh_src.data(), b.mesh_src.size() * sizeof(MeshSrc), hipMemcpyHostToDevice, b.bs) != hipSuccess) return b.fail("copy");
 	// the triangle records in sorted order are made by k_refit_tile, which needs them next (RTK_AMD_FUSED_EMIT=0: by a pass of their own, A/B)
-	EmitSrc emit_src = { in_tris, d_mesh_src, vals, keys, d_mesh_base, (uint32_t)desc->num_meshes };
-	const bool fused_emit = !(getenv("RTK_AMD_FUSED_EMIT") && atoi(getenv("RTK_AMD_FUSED_EMIT")) == 0);
-	if (!fused_emit) {
-		hipLaunchKernelGGL(k_emit_tris, dim3((n + 255u) / 256u), dim3(256), 0, bs, emit_src, n, d_tris);
-		if (hipGetLastError() != hipSuccess) return fail("emit launch");
-		emit_src.src = nullptr;
+	b.emit_src = EmitSrc{ b.in_tris, b.d_mesh_src, b.vals, b.keys, b.d_mesh_base, (uint32_t)b.desc->num_meshes };
+	if (!b.knobs.fused_emit) {
+		hipLaunchKernelGGL(k_emit_tris, dim3((n + 255u) / 256u), dim3(256), 0, b.bs, b.emit_src, n, b.d_tris);
+		if (hipGetLastError() != hipSuccess) return b.fail("emit launch");
+		b.emit_src.src = nullptr;
 	}
-	stage("emit");
+	b.stage("emit");
+	return true;
+}
 
-	// ---- 6 + 7 tree topology and refit in one bottom-up pass ------------------------------------
-	int2 *d_lr = ar.take<int2>(n);
-	uint2 *d_range = ar.take<uint2>(n);
-	Climb *d_climbers = ar.take<Climb>(n);
-	unsigned long long *d_half = ar.take<unsigned long long>(2 * (size_t)n);
-	uint32_t *d_arrive = ar.take<uint32_t>(n);
-	int *d_root = ar.take<int>(4);
-	BinNode *d_bin = ar.take<BinNode>(n);
-	// tile mode (more than one refit tile): the subtrees inside a tile are collapsed by k_collapse_tile, only the nodes above
-	// them go through the level-by-level collapse.
-	const uint32_t num_tiles = (n + REFIT_TILE - 1u) / REFIT_TILE;
-	// Measured on MI355X (profiles/r05_build_timing.log, level by level / tile mode): 0.47 / 0.46 ms at 0.5M triangles, 0.555 / 0.540
-	// at 1M, 0.785 / 0.748 at 2M, 1.005 / 0.935 at 3M -- since the tiles' kernels run beside pass 2 and the top collapse, tile mode
-	// is never slower; its trees have ~2 % more nodes (tile roots are never opened from above: ~1 % more node visits per ray), so
-	// it starts where the build time it saves is worth more than that: 1.5M triangles. RTK_AMD_TILE_COLLAPSE_MIN (triangles; read
-	// per build) moves that: 0 = whenever there are two tiles, a huge value = never (everything level by level: A/B).
-	const char *tile_env = getenv("RTK_AMD_TILE_COLLAPSE_MIN");
-	const uint64_t tile_min = tile_env ? (uint64_t)atoll(tile_env) : (3ull << 19);
-	const bool tile_mode = num_tiles > 1u && (uint64_t)n >= tile_min;
-	uint32_t *d_tile_count = ar.take<uint32_t>(num_tiles + 1u), *d_tile_base = ar.take<uint32_t>(num_tiles + 1u);
-	uint32_t *d_depth_word = ar.take<uint32_t>(4);
-	float *d_area = tile_mode ? ar.take<float>(n) : (float *)nullptr;
-	// pass 2 finds its climbers through d_arrive (their positions, packed per tile) and d_tile_nclimb; two subtrees meet through
-	// the first n words of d_half
-	uint32_t *d_tile_nclimb = ar.take<uint32_t>(num_tiles + 1u);
-	int *d_climb_idx = reinterpret_cast<int *>(d_arrive);
-	// n nodes' worth of workspace: every node of the tree without tile mode (worst case). In tile mode it holds the nodes above
-	// the tiles until k_top_finish moves them to their places (at most n / 2 of them; a tree with more goes the other way), their
-	// tile-root and level words, a word per binary node for what k_collapse_tile tells k_top_finish about the tile roots, and
-	// the tiles' lists of roots (k_refit_tile).
-	DevNode *d_nodes_tmp = ar.take<DevNode>(n);
-	if (!d_nodes_tmp) return fail("workspace too small (internal error)");
-	// (RTK_AMD_TOP_CAP: a smaller capacity, to drive the way back to the level-by-level collapse from tests)
-	const uint32_t top_cap = getenv("RTK_AMD_TOP_CAP") ? std::min<uint32_t>(n / 2u, (uint32_t)atoi(getenv("RTK_AMD_TOP_CAP"))) : n / 2u;
-	uint4 *d_top_refs = reinterpret_cast<uint4 *>(d_nodes_tmp + top_cap);
-	uint32_t *d_top_level = reinterpret_cast<uint32_t *>(d_top_refs + top_cap);
-	unsigned long long *d_root_info = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(d_nodes_tmp) + rtk_padded((size_t)top_cap * (sizeof(DevNode) + 16u + 4u)));
-	int *d_root_list = reinterpret_cast<int *>(d_root_info + n);
-	static_assert(sizeof(DevNode) == 128, "the carving above: n / 2 * 148 + 8 n + 4 n + padding <= 128 n");
-	uint32_t *d_tile_nroots = ar.take<uint32_t>(num_tiles + 1u);
-	if (hipMemsetAsync(d_depth_word, 0, 16, bs) != hipSuccess) return fail("memset");
+// ---- 6 + 7 tree topology and refit in one bottom-up pass (no separate tree-building kernel), then the nodes that cross tile borders ----
+bool refit(Build &b)
+{
+	Workspace &ws = *b.ws;
+	const hipStream_t bs = b.bs;
+	const uint32_t num_tiles = b.num_tiles;
+	if (hipMemsetAsync(b.d_depth_word, 0, 16, bs) != hipSuccess) return b.fail("memset");
 	// (the scene's constants block: allocated and cleared here, not between the collapse and the last kernel -- a hipMalloc there was 40 us
 	// in which the GPU waited; in tile mode also before the second stream forks off. The callee's error text stands.)
-	if (rtk_scene_consts(ds, bs) != RTK_AMD_OK) return give_up();
-	// topology and boxes in one bottom-up pass (no separate tree-building kernel), then the nodes that cross tile borders
-	hipLaunchKernelGGL(k_refit_tile, dim3(num_tiles), dim3(REFIT_BLOCK), 0, bs, d_tris, (int)n, keys, d_lr, d_range,
-		d_bin, d_climbers, d_half, d_climb_idx, d_tile_nclimb, d_root, bp, d_area, d_depth_word + 1, tile_mode ? d_root_list : (int *)nullptr,
-		tile_mode ? d_tile_nroots : (uint32_t *)nullptr, emit_src);
-	bool forked = false;
-	hipStream_t cs = bs;
-	if (tile_mode) {
-		// how many wide nodes every tile makes, and where they start, then (below, once the node arrays are allocated) the tiles' nodes
+	if (rtk_scene_consts(b.ds, bs) != RTK_AMD_OK) return b.give_up();
+	hipLaunchKernelGGL(k_refit_tile, dim3(num_tiles), dim3(REFIT_BLOCK), 0, bs, b.d_tris, (int)b.n, b.keys, b.d_lr, b.d_range,
+		b.d_bin, b.d_climbers, b.d_half, b.d_climb_idx, b.d_tile_nclimb, b.d_root, b.bp, b.d_area, b.d_depth_word + 1, b.d_root_list,
+		b.tile_mode ? b.d_tile_nroots : (uint32_t *)nullptr, b.emit_src);
+	if (b.tile_mode) {
+		// how many wide nodes every tile makes, and where they start, then (collapse_tiles, once the node arrays are allocated) the tiles' nodes
 		// themselves: on a stream of their own, beside pass 2 of the refit and the collapse of the nodes above the tiles -- a chain of
 		// latency-bound launches with host round trips between them, 0.3 ms at 10M triangles in which the chip would have next to
 		// nothing to do. (The tiles' kernels read what pass 1 wrote and nothing that pass 2 writes: k_refit_tile lists the roots.)
@@ -2300,193 +2082,239 @@ static rtk_dev_scene *build_impl(const rtk_scene_desc *desc, uint32_t force_bits
 			if (ws.side) (void)hipStreamDestroy(ws.side);
 			ws.side = nullptr;                       // (events created so far are kept for the next attempt: a handful of bytes)
 		}
-		forked = ws.side && hipEventRecord(ws.fork, bs) == hipSuccess && hipStreamWaitEvent(ws.side, ws.fork, 0) == hipSuccess;
-		cs = forked ? ws.side : bs;
-		hipLaunchKernelGGL(k_count_tile, dim3(num_tiles), dim3(64), 0, cs, (int)n, d_lr, d_area, d_root_list, d_tile_nroots, d_tile_count);
-		hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, cs, d_tile_count, num_tiles, d_tile_base);
-		if (forked) side_busy = true;
+		b.forked = ws.side && hipEventRecord(ws.fork, bs) == hipSuccess && hipStreamWaitEvent(ws.side, ws.fork, 0) == hipSuccess;
+		b.cs = b.forked ? ws.side : bs;
+		hipLaunchKernelGGL(k_count_tile, dim3(num_tiles), dim3(64), 0, b.cs, (int)b.n, b.d_lr, b.d_area, b.d_root_list, b.d_tile_nroots, b.d_tile_count);
+		hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, b.cs, b.d_tile_count, num_tiles, b.d_tile_base);
+		if (b.forked) b.side_busy = true;
 	}
-	hipLaunchKernelGGL(k_refit_top, dim3(num_tiles), dim3(64), 0, bs, d_tris, (int)n, keys, d_climbers, d_climb_idx, d_tile_nclimb, d_half, d_bin, d_lr, d_range,
-		d_root, bp, tile_mode);
-	if (hipGetLastError() != hipSuccess) return fail("refit");
-	stage("refit");
+	hipLaunchKernelGGL(k_refit_top, dim3(num_tiles), dim3(64), 0, bs, b.d_tris, (int)b.n, b.keys, b.d_climbers, b.d_climb_idx, b.d_tile_nclimb, b.d_half, b.d_bin, b.d_lr, b.d_range,
+		b.d_root, b.bp, b.tile_mode);
+	if (hipGetLastError() != hipSuccess) return b.fail("refit");
+	b.stage("refit");
+	return true;
+}
 
-	// ---- 8 collapse: level by level for the nodes above the tiles (all nodes without tile mode), then the tiles ---------
-	CollapseBufs cb;
-	cb.jobs = ar.take<int>(n);
-	cb.dec = ar.take<int4>(n);
-	cb.info = ar.take<uint32_t>(n);
-	cb.sums = ar.take<uint32_t>(collapse_blocks);
-	LevelState *d_ring = ar.take<LevelState>(COLLAPSE_RING);
-	TopAux top_aux = { tile_mode ? d_top_refs : (uint4 *)nullptr, tile_mode ? d_top_level : (uint32_t *)nullptr };
-	LevelState h_state = {};
-	// The node arrays of the scene, [DevNode x node_cap | DevNodeQ x node_cap], are allocated now -- the GPU is still busy
-	// with the refit -- at the size 4-wide trees over n triangles usually have (0.47 n on the benchmark scenes), and the
-	// collapse writes its nodes straight into them. A tree with more nodes than that drops the writes beyond the capacity
-	// (the kernels check) and is collapsed once more: into an exact allocation (tile mode) or into the workspace.
-	void *node_mem = nullptr;
-	// (RTK_AMD_NODE_ESTIMATE_DIV: n / div + 16 instead, to drive the repeat path from tests)
-	const int est_div = getenv("RTK_AMD_NODE_ESTIMATE_DIV") ? atoi(getenv("RTK_AMD_NODE_ESTIMATE_DIV")) : 0;
-	size_t node_cap = est_div > 0 ? (size_t)n / (size_t)est_div + 16 : (size_t)n / 2 + 4096;
-	if (hipMalloc(&node_mem, node_cap * (sizeof(DevNode) + sizeof(DevNodeQ))) != hipSuccess) { (void)hipGetLastError(); node_mem = nullptr; node_cap = 0; }
-	else ds->allocs.push_back(node_mem);      // owned by the scene from here on (error paths free it with the scene)
-	auto run_collapse = [&](DevNode *target, uint32_t cap, uint64_t jobs_hint) -> bool {
-		const unsigned big_blocks = (unsigned)std::min<uint64_t>((jobs_hint + COLLAPSE_BLOCK - 1) / COLLAPSE_BLOCK, (uint64_t)num_cus * 16);
-		// levels with more than COLLAPSE_SMALL jobs in a balanced 4-wide tree over jobs_hint leaves, plus slack; a tree that is
-		// deeper than that takes further rounds
-		unsigned big_levels = 2;
-		for (uint64_t c = COLLAPSE_SMALL_JOBS; c < jobs_hint; c *= 4) big_levels++;
-		uint32_t step = 0;
-		for (unsigned round = 0;; round++) {
-			hipLaunchKernelGGL(k_collapse_small, dim3(1), dim3(COLLAPSE_SMALL), 0, bs, cb, d_ring, step++, 16u, d_lr, d_range, d_bin, d_tris, target, cap, d_root, top_aux, (LevelState *)nullptr);
-			for (unsigned k = 0; k < big_levels; k++) {
-				// number the level of ring entry `step` (-> entry step + 1: the next level, not opened yet), then open that
-				hipLaunchKernelGGL(k_collapse_number, dim3(big_blocks), dim3(COLLAPSE_BLOCK), 0, bs, cb, d_ring, step, target, cap);
-				step++;
-				hipLaunchKernelGGL(k_collapse_open, dim3(big_blocks), dim3(COLLAPSE_BLOCK), 0, bs, cb, d_ring, step, d_lr, d_range, d_bin, d_tris, target, cap, top_aux);
-			}
-			// (the level the round ends at goes straight into pinned host memory)
-			hipLaunchKernelGGL(k_collapse_small, dim3(1), dim3(COLLAPSE_SMALL), 0, bs, cb, d_ring, step++, 16u, d_lr, d_range, d_bin, d_tris, target, cap, d_root, top_aux, &results->level);
-			if (hipGetLastError() != hipSuccess || hipStreamSynchronize(bs) != hipSuccess) return false;
-			memcpy(&h_state, const_cast<const LevelState *>(&results->level), sizeof(h_state));
-			if (h_state.count == 0) return true;
-			if (round > 4096) return false;
-			big_levels = 4;
+// ---- 8 collapse ----
+// The node arrays of the scene, [DevNode x node_cap | DevNodeQ x node_cap], are allocated before the collapse -- the GPU is still
+// busy with the refit -- at the size 4-wide trees over n triangles usually have (0.47 n on the benchmark scenes), and the
+// collapse writes its nodes straight into them. A tree with more nodes than that drops the writes beyond the capacity
+// (the kernels check) and is collapsed once more: into an exact allocation (tile mode) or into the workspace.
+// (no node memory afterwards: the estimate could not be allocated -- a dry round gives the exact size)
+void alloc_node_estimate(Build &b)
+{
+	b.node_cap = b.knobs.est_div > 0 ? (size_t)b.n / (size_t)b.knobs.est_div + 16 : (size_t)b.n / 2 + 4096;
+	if (hipMalloc(&b.node_mem, b.node_cap * (sizeof(DevNode) + sizeof(DevNodeQ))) != hipSuccess) { (void)hipGetLastError(); b.node_mem = nullptr; b.node_cap = 0; }
+	else b.ds->allocs.push_back(b.node_mem);      // owned by the scene from here on (error paths free it with the scene)
+}
+
+// The level-by-level collapse into `target` (room for `cap` nodes; more are counted but not written). False: a launch or the
+// wait failed (nothing is cleaned up here). b.h_state: the last level, with the number of nodes.
+bool run_collapse(Build &b, DevNode *target, uint32_t cap, uint64_t jobs_hint)
+{
+	const hipStream_t bs = b.bs;
+	const unsigned big_blocks = (unsigned)std::min<uint64_t>((jobs_hint + COLLAPSE_BLOCK - 1) / COLLAPSE_BLOCK, (uint64_t)b.num_cus * 16);
+	// levels with more than COLLAPSE_SMALL jobs in a balanced 4-wide tree over jobs_hint leaves, plus slack; a tree that is
+	// deeper than that takes further rounds
+	unsigned big_levels = 2;
+	for (uint64_t c = COLLAPSE_SMALL_JOBS; c < jobs_hint; c *= 4) big_levels++;
+	uint32_t step = 0;
+	for (unsigned round = 0;; round++) {
+		hipLaunchKernelGGL(k_collapse_small, dim3(1), dim3(COLLAPSE_SMALL), 0, bs, b.cb, b.d_ring, step++, 16u, b.d_lr, b.d_range, b.d_bin, b.d_tris, target, cap, b.d_root, b.top_aux, (LevelState *)nullptr);
+		for (unsigned k = 0; k < big_levels; k++) {
+			// number the level of ring entry `step` (-> entry step + 1: the next level, not opened yet), then open that
+			hipLaunchKernelGGL(k_collapse_number, dim3(big_blocks), dim3(COLLAPSE_BLOCK), 0, bs, b.cb, b.d_ring, step, target, cap);
+			step++;
+			hipLaunchKernelGGL(k_collapse_open, dim3(big_blocks), dim3(COLLAPSE_BLOCK), 0, bs, b.cb, b.d_ring, step, b.d_lr, b.d_range, b.d_bin, b.d_tris, target, cap, b.top_aux);
 		}
-	};
-	uint32_t total_nodes = 0, depth = 0;
-	uint32_t h_equal_codes = 0;          // sorted neighbours with one and the same Morton code (counted by k_refit_tile)
-	bool tiles_done = false;
-	if (tile_mode) {
-		DevSceneConsts *consts = const_cast<DevSceneConsts *>(ds->view.consts);
-		uint32_t h_tail[2] = { 0u, 0u };      // { wide nodes of all tiles, deepest level }
-		uint32_t top_nodes = 0;
-		for (int attempt = 0;; attempt++) {
-			// (no node memory: the estimate could not be allocated -- a dry round gives the exact size)
-			if (!node_mem) node_cap = 0;
-			DevNode *d_nodes_ = (DevNode *)node_mem;
-			DevNodeQ *d_qnodes_ = (DevNodeQ *)(d_nodes_ + node_cap);
-			// the tiles' nodes, numbers 1 ... (0 is the root): beside the collapse of the nodes above them the first time
-			const hipStream_t ts = attempt == 0 ? cs : bs;
-			hipLaunchKernelGGL(k_collapse_tile, dim3(num_tiles), dim3(TILE_THREADS), 0, ts, d_tris, (int)n, d_lr, d_range, d_bin, d_area, d_root_list, d_tile_nroots, d_root_info,
-				d_tile_base, 1u, d_nodes_, d_qnodes_, (uint32_t)node_cap, consts);
-			if (hipGetLastError() != hipSuccess) return fail("tile collapse launch");
-			if (attempt == 0) {
-				if (forked && hipEventRecord(ws.join, ws.side) != hipSuccess) return fail("event record");
-				// the nodes above the tiles (~4 per tile; ~15 tile roots per tile hang below them), into the workspace
-				if (!run_collapse(d_nodes_tmp, top_cap, (uint64_t)num_tiles * 16u)) return fail("collapse");
-				top_nodes = h_state.total_nodes;
-				if (forked && hipStreamWaitEvent(bs, ws.join, 0) != hipSuccess) return fail("stream wait");
-				if (top_nodes > top_cap) break;           // (more of them than the workspace holds: everything level by level, below)
-			}
-			hipLaunchKernelGGL(k_top_finish, dim3((top_nodes + 255u) / 256u), dim3(256), 0, bs, d_nodes_tmp, d_top_refs, d_top_level, top_nodes, d_tile_base + num_tiles, d_root_info,
-				d_nodes_, d_qnodes_, (uint32_t)node_cap, consts, d_depth_word);
-			hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, bs, results, d_tile_base + num_tiles, d_depth_word, consts);
-			if (hipGetLastError() != hipSuccess || hipStreamSynchronize(bs) != hipSuccess) return fail("tile collapse");
-			h_tail[0] = results->tiles_total;
-			h_tail[1] = results->depth;
-			h_equal_codes = results->equal_codes;
-			ds->consts_readback = results->consts;
+		// (the level the round ends at goes straight into pinned host memory)
+		hipLaunchKernelGGL(k_collapse_small, dim3(1), dim3(COLLAPSE_SMALL), 0, bs, b.cb, b.d_ring, step++, 16u, b.d_lr, b.d_range, b.d_bin, b.d_tris, target, cap, b.d_root, b.top_aux, &b.results->level);
+		if (hipGetLastError() != hipSuccess || hipStreamSynchronize(bs) != hipSuccess) return false;
+		memcpy(&b.h_state, const_cast<const LevelState *>(&b.results->level), sizeof(b.h_state));
+		if (b.h_state.count == 0) return true;
+		if (round > 4096) return false;
+		big_levels = 4;
+	}
+}
+
+// Tile mode: the tiles' nodes by k_collapse_tile beside the level-by-level collapse of the nodes above them (into the workspace),
+// then k_top_finish moves those behind the tiles' nodes. Once more into an exact allocation if the estimate was too small.
+// b.tiles_done stays false if there are more nodes above the tiles than the workspace holds: collapse_levels does everything then.
+bool collapse_tiles(Build &b)
+{
+	Workspace &ws = *b.ws;
+	const hipStream_t bs = b.bs;
+	const uint32_t num_tiles = b.num_tiles;
+	BuildResults *const results = b.results;
+	DevSceneConsts *consts = const_cast<DevSceneConsts *>(b.ds->view.consts);
+	uint32_t top_nodes = 0;
+	for (int attempt = 0;; attempt++) {
+		DevNode *d_nodes_ = (DevNode *)b.node_mem;
+		DevNodeQ *d_qnodes_ = (DevNodeQ *)(d_nodes_ + b.node_cap);
+		// the tiles' nodes, numbers 1 ... (0 is the root): beside the collapse of the nodes above them the first time
+		const hipStream_t ts = attempt == 0 ? b.cs : bs;
+		hipLaunchKernelGGL(k_collapse_tile, dim3(num_tiles), dim3(TILE_THREADS), 0, ts, b.d_tris, (int)b.n, b.d_lr, b.d_range, b.d_bin, b.d_area, b.d_root_list, b.d_tile_nroots, b.d_root_info,
+			b.d_tile_base, 1u, d_nodes_, d_qnodes_, (uint32_t)b.node_cap, consts);
+		if (hipGetLastError() != hipSuccess) return b.fail("tile collapse launch");
+		if (attempt == 0) {
+			if (b.forked && hipEventRecord(ws.join, ws.side) != hipSuccess) return b.fail("event record");
+			// the nodes above the tiles (~4 per tile; ~15 tile roots per tile hang below them), into the workspace
+			if (!run_collapse(b, b.d_nodes_tmp, b.top_cap, (uint64_t)num_tiles * 16u)) return b.fail("collapse");
+			top_nodes = b.h_state.total_nodes;
+			if (b.forked && hipStreamWaitEvent(bs, ws.join, 0) != hipSuccess) return b.fail("stream wait");
+			if (top_nodes > b.top_cap) break;           // (more of them than the workspace holds: everything level by level)
+		}
+		hipLaunchKernelGGL(k_top_finish, dim3((top_nodes + 255u) / 256u), dim3(256), 0, bs, b.d_nodes_tmp, b.d_top_refs, b.d_top_level, top_nodes, b.d_tile_base + num_tiles, b.d_root_info,
+			d_nodes_, d_qnodes_, (uint32_t)b.node_cap, consts, b.d_depth_word);
+		hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, bs, results, b.d_tile_base + num_tiles, b.d_depth_word, consts);
+		if (hipGetLastError() != hipSuccess || hipStreamSynchronize(bs) != hipSuccess) return b.fail("tile collapse");
+		const uint32_t tile_nodes = results->tiles_total;      // wide nodes of all tiles
+		b.depth = results->depth;
+		b.equal_codes = results->equal_codes;
+		b.ds->consts_readback = results->consts;
 #ifdef RTK_TILE_PHASES
-			{
-				unsigned long long h[8] = {}, z[8] = {};
-				(void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tile_phase), sizeof(h));
-				(void)hipMemcpyToSymbol(HIP_SYMBOL(g_tile_phase), z, sizeof(z));
-				if (h[4]) fprintf(stderr, "rtk_amd tile phases (10 ns ticks per tile): load %.0f bfs %.0f number %.0f finish %.0f; tiles %llu jobs/tile %.0f\n",
-					(double)h[0] / h[4], (double)h[1] / h[4], (double)h[2] / h[4], (double)h[3] / h[4], h[4], (double)h[5] / h[4]);
-				fprintf(stderr, "rtk_amd tile phases: slowest tile %llu ticks (tile %llu); slowest finish %llu ticks (%llu jobs)\n", h[6] >> 32, h[6] & 0xffffffffull, h[7] >> 32, h[7] & 0xffffffffull);
-			}
+		{
+			unsigned long long h[8] = {}, z[8] = {};
+			(void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tile_phase), sizeof(h));
+			(void)hipMemcpyToSymbol(HIP_SYMBOL(g_tile_phase), z, sizeof(z));
+			if (h[4]) fprintf(stderr, "rtk_amd tile phases (10 ns ticks per tile): load %.0f bfs %.0f number %.0f finish %.0f; tiles %llu jobs/tile %.0f\n",
+				(double)h[0] / h[4], (double)h[1] / h[4], (double)h[2] / h[4], (double)h[3] / h[4], h[4], (double)h[5] / h[4]);
+			fprintf(stderr, "rtk_amd tile phases: slowest tile %llu ticks (tile %llu); slowest finish %llu ticks (%llu jobs)\n", h[6] >> 32, h[6] & 0xffffffffull, h[7] >> 32, h[7] & 0xffffffffull);
+		}
 #endif
-			if (timing) {
-				std::vector<uint32_t> hc(num_tiles + 1), hb(num_tiles + 1);
-				(void)hipMemcpy(hc.data(), d_tile_count, (num_tiles) * 4, hipMemcpyDeviceToHost);
-				(void)hipMemcpy(hb.data(), d_tile_base, (num_tiles + 1) * 4, hipMemcpyDeviceToHost);
-				fprintf(stderr, "rtk_amd build: top %u tiles %u tail %u depth %u cap %zu counts %u %u %u bases %u %u %u\n", top_nodes, num_tiles, h_tail[0], h_tail[1], node_cap,
-					hc[0], hc[1], hc[num_tiles - 1], hb[0], hb[1], hb[num_tiles]);
-			}
-			total_nodes = top_nodes + h_tail[0];
-			depth = h_tail[1];
-			if (total_nodes <= node_cap) {
-				ds->view.nodes = d_nodes_;
-				ds->view.qnodes = d_qnodes_;
-				ds->view.num_nodes = total_nodes;
-				ds->first_top = 1u + h_tail[0];
-				tiles_done = true;
-				break;
-			}
-			if (attempt > 0) return fail("collapse (internal error: node count changed between two runs)");
-			// the estimate was too small: an exact allocation, and the tiles and the move once more (the nodes above the tiles stay
-			// where they are in the workspace; every pass is deterministic)
-			if (node_mem) { ds->allocs.pop_back(); (void)hipFree(node_mem); node_mem = nullptr; }     // it was the last one pushed
-			node_cap = total_nodes;
-			if (hipMalloc(&node_mem, node_cap * (sizeof(DevNode) + sizeof(DevNodeQ))) != hipSuccess) return fail("out of device memory");
-			ds->allocs.push_back(node_mem);
-			if (hipMemsetAsync(consts, 0, sizeof(DevSceneConsts), bs) != hipSuccess || hipMemsetAsync(d_depth_word, 0, 4, bs) != hipSuccess) return fail("memset");
+		if (b.knobs.timing) {
+			std::vector<uint32_t> hc(num_tiles + 1), hb(num_tiles + 1);
+			(void)hipMemcpy(hc.data(), b.d_tile_count, (num_tiles) * 4, hipMemcpyDeviceToHost);
+			(void)hipMemcpy(hb.data(), b.d_tile_base, (num_tiles + 1) * 4, hipMemcpyDeviceToHost);
+			fprintf(stderr, "rtk_amd build: top %u tiles %u tail %u depth %u cap %zu counts %u %u %u bases %u %u %u\n", top_nodes, num_tiles, tile_nodes, b.depth, b.node_cap,
+				hc[0], hc[1], hc[num_tiles - 1], hb[0], hb[1], hb[num_tiles]);
 		}
-		if (tiles_done) stage("collapse");
-		else {
-			// (the other way needs the level-by-level kernels without their tile-mode arguments, and clean counters)
-			top_aux = TopAux{ nullptr, nullptr };
-			if (hipMemsetAsync(d_depth_word, 0, 4, bs) != hipSuccess) return fail("memset");
+		b.total_nodes = top_nodes + tile_nodes;
+		if (b.total_nodes <= b.node_cap) {
+			b.ds->view.nodes = d_nodes_;
+			b.ds->view.qnodes = d_qnodes_;
+			b.ds->view.num_nodes = b.total_nodes;
+			b.ds->first_top = 1u + tile_nodes;
+			b.tiles_done = true;
+			break;
 		}
+		if (attempt > 0) return b.fail("collapse (internal error: node count changed between two runs)");
+		// the estimate was too small: an exact allocation, and the tiles and the move once more (the nodes above the tiles stay
+		// where they are in the workspace; every pass is deterministic)
+		if (b.node_mem) { b.ds->allocs.pop_back(); (void)hipFree(b.node_mem); b.node_mem = nullptr; }     // it was the last one pushed
+		b.node_cap = b.total_nodes;
+		if (hipMalloc(&b.node_mem, b.node_cap * (sizeof(DevNode) + sizeof(DevNodeQ))) != hipSuccess) { b.node_mem = nullptr; return b.fail("out of device memory"); }
+		b.ds->allocs.push_back(b.node_mem);
+		if (hipMemsetAsync(consts, 0, sizeof(DevSceneConsts), bs) != hipSuccess || hipMemsetAsync(b.d_depth_word, 0, 4, bs) != hipSuccess) return b.fail("memset");
 	}
-	if (!tiles_done) {
-		bool in_place = node_mem != nullptr;
-		if (!run_collapse(in_place ? (DevNode *)node_mem : d_nodes_tmp, in_place ? (uint32_t)node_cap : n, n)) return fail("collapse");
-		if (in_place && h_state.total_nodes > node_cap) {
-			// the estimate was too small: once more, into the workspace; then an exact allocation
-			ds->allocs.pop_back(); (void)hipFree(node_mem); node_mem = nullptr;      // it was the last one pushed
-			in_place = false;
-			if (!run_collapse(d_nodes_tmp, n, n)) return fail("collapse");
-		}
-		total_nodes = h_state.total_nodes;
-		depth = h_state.depth;
-		stage("collapse");
-		if (!node_mem) {
-			node_cap = total_nodes ? total_nodes : 1;
-			if (hipMalloc(&node_mem, node_cap * (sizeof(DevNode) + sizeof(DevNodeQ))) != hipSuccess) return fail("out of device memory");
-			ds->allocs.push_back(node_mem);
-		}
-		DevNode *d_nodes_ = (DevNode *)node_mem;
-		ds->view.nodes = d_nodes_;
-		ds->view.num_nodes = total_nodes;
-		// compressed nodes beside the exact ones (and, if the collapse had to go through the workspace, the exact ones out of it)
-		DevSceneConsts *consts = const_cast<DevSceneConsts *>(ds->view.consts);
-		if (tile_mode && hipMemsetAsync(consts, 0, sizeof(DevSceneConsts), bs) != hipSuccess) return fail("memset");     // (the way back from tile mode: its kernels have counted in there)
-		if (rtk_quantize_nodes(ds, bs, in_place ? nullptr : d_nodes_tmp, (DevNodeQ *)(d_nodes_ + node_cap), 0.0f, 0xffffffffu, true, false) != RTK_AMD_OK) return give_up();
-		hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, bs, results, (const uint32_t *)nullptr, d_depth_word, consts);
-		if (hipGetLastError() != hipSuccess) return fail("publish launch");
+	if (b.tiles_done) b.stage("collapse");
+	else {
+		// (the other way needs the level-by-level kernels without their tile-mode arguments, and clean counters)
+		b.top_aux = TopAux{ nullptr, nullptr };
+		if (hipMemsetAsync(b.d_depth_word, 0, 4, bs) != hipSuccess) return b.fail("memset");
 	}
-	ds->total_bytes += node_cap * (sizeof(DevNode) + sizeof(DevNodeQ));
-	if (hipStreamSynchronize(bs) != hipSuccess || (side_busy && hipStreamSynchronize(ws.side) != hipSuccess)) return fail("sync");   // the workspace is handed back below
-	if (!tiles_done) {
-		h_equal_codes = results->equal_codes;
-		ds->consts_readback = results->consts;
+	return true;
+}
+
+// Every node level by level, straight into the scene's node array; through the workspace and then into an exact allocation if
+// the estimate was too small (or could not be had). The compressed nodes follow (rtk_quantize_nodes).
+bool collapse_levels(Build &b)
+{
+	const hipStream_t bs = b.bs;
+	bool in_place = b.node_mem != nullptr;
+	if (!run_collapse(b, in_place ? (DevNode *)b.node_mem : b.d_nodes_tmp, in_place ? (uint32_t)b.node_cap : b.n, b.n)) return b.fail("collapse");
+	if (in_place && b.h_state.total_nodes > b.node_cap) {
+		// the estimate was too small: once more, into the workspace; then an exact allocation
+		b.ds->allocs.pop_back(); (void)hipFree(b.node_mem); b.node_mem = nullptr;      // it was the last one pushed
+		in_place = false;
+		if (!run_collapse(b, b.d_nodes_tmp, b.n, b.n)) return b.fail("collapse");
+	}
+	b.total_nodes = b.h_state.total_nodes;
+	b.depth = b.h_state.depth;
+	b.stage("collapse");
+	if (!b.node_mem) {
+		b.node_cap = b.total_nodes ? b.total_nodes : 1;
+		if (hipMalloc(&b.node_mem, b.node_cap * (sizeof(DevNode) + sizeof(DevNodeQ))) != hipSuccess) { b.node_mem = nullptr; return b.fail("out of device memory"); }
+		b.ds->allocs.push_back(b.node_mem);
+	}
+	DevNode *d_nodes_ = (DevNode *)b.node_mem;
+	b.ds->view.nodes = d_nodes_;
+	b.ds->view.num_nodes = b.total_nodes;
+	// compressed nodes beside the exact ones (and, if the collapse had to go through the workspace, the exact ones out of it)
+	DevSceneConsts *consts = const_cast<DevSceneConsts *>(b.ds->view.consts);
+	if (b.tile_mode && hipMemsetAsync(consts, 0, sizeof(DevSceneConsts), bs) != hipSuccess) return b.fail("memset");     // (the way back from tile mode: its kernels have counted in there)
+	if (rtk_quantize_nodes(b.ds, bs, in_place ? nullptr : b.d_nodes_tmp, (DevNodeQ *)(d_nodes_ + b.node_cap), 0.0f, 0xffffffffu, true, false) != RTK_AMD_OK) return b.give_up();
+	hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, bs, b.results, (const uint32_t *)nullptr, b.d_depth_word, consts);
+	if (hipGetLastError() != hipSuccess) return b.fail("publish launch");
+	return true;
+}
+
+// ---- finish: the one wait for both streams (the workspace is handed back when build_impl returns), the scene's view ----
+bool finish(Build &b)
+{
+	rtk_dev_scene *ds = b.ds;
+	ds->total_bytes += b.node_cap * (sizeof(DevNode) + sizeof(DevNodeQ));
+	if (hipStreamSynchronize(b.bs) != hipSuccess || (b.side_busy && hipStreamSynchronize(b.ws->side) != hipSuccess)) return b.fail("sync");
+	if (!b.tiles_done) {
+		b.equal_codes = b.results->equal_codes;
+		ds->consts_readback = b.results->consts;
 	}
 	rtk_quantize_finish(ds);
-
-	ds->view.tris = d_tris;
-	ds->view.vertex_index = nullptr;           // (the four side arrays: rtk_scene_side_arrays, on first use)
-	ds->view.prim_slot = nullptr;
-	ds->view.slot_mesh = nullptr;
-	ds->view.slot_tri = nullptr;
-	ds->view.num_nodes = total_nodes;
-	ds->view.num_tris = n;
-	ds->view.num_prims = n;
-	ds->max_depth = depth;
-	ds->stack_entries = 3u * depth + 1u;
-	stage("finish");
-	ds->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-	*narrow_key = packed && packed_bits < 40u && (uint64_t)h_equal_codes * 8u > (uint64_t)n;
-	if (timing) fprintf(stderr, "rtk_amd build: %u key bits, %u of %u sorted neighbours share a code%s\n", packed ? packed_bits : key_bits, h_equal_codes, n,
-		*narrow_key ? " -> key too narrow for this scene" : "");
-	if (getenv("RTK_AMD_KEEP_WORKSPACE") && atoi(getenv("RTK_AMD_KEEP_WORKSPACE")) == 0) {
-		(void)hipFree(ws.base);
-		ws.base = nullptr;
-		ws.cap = 0;
-	}
-	return ds;
+	ds->view.tris = b.d_tris;
+	ds->view.vertex_index = ds->view.prim_slot = ds->view.slot_mesh = ds->view.slot_tri = nullptr;      // (the four side arrays: rtk_scene_side_arrays, on first use)
+	ds->view.num_nodes = b.total_nodes;
+	ds->view.num_tris = b.n;
+	ds->view.num_prims = b.n;
+	ds->max_depth = b.depth;
+	ds->stack_entries = 3u * b.depth + 1u;
+	b.stage("finish");
+	ds->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - b.t_begin).count();
+	return true;
 }
+
+// force_bits: 0 = key width from the number of triangles; else the width of the Morton code in the packed sort words.
+// *narrow_key: the build was made with fewer than 40 bits and more than an eighth of the sorted neighbours share their code.
+rtk_dev_scene *build_impl(const rtk_scene_desc *desc, const BuildKnobs &knobs, uint32_t force_bits, bool *narrow_key)
+{
+	*narrow_key = false;
+	if (!desc || (!desc->meshes && desc->num_meshes)) { rtk_set_error("rtk_dev_scene_build: NULL scene description"); return nullptr; }
+	Build b;
+	b.desc = desc;
+	b.knobs = knobs;
+	b.mesh_base.assign(desc->num_meshes + 1, 0);
+	for (size_t m = 0; m < desc->num_meshes; m++) b.mesh_base[m + 1] = b.mesh_base[m] + desc->meshes[m].num_triangles;
+	const uint64_t n64 = b.mesh_base.back();
+	if (n64 >= 0x3ffffff0ull) { rtk_set_error("rtk_dev_scene_build: more than 2^30 triangles"); return nullptr; }
+	b.n = (uint32_t)n64;
+	if (desc->log_fn) desc->log_fn(desc->log_user, nullptr, "rtk_amd: device LBVH build");
+	b.t_begin = b.t_last = std::chrono::steady_clock::now();
+	if (hipGetDevice(&b.device) != hipSuccess) { b.fail("hipGetDevice"); return nullptr; }
+	if (b.device < 0 || b.device >= RTK_MAX_DEVICES) { rtk_set_error("rtk_dev_scene_build: device %d out of range", b.device); return nullptr; }
+	b.num_cus = cached_cu_count(b.device);
+	if (!plan_meshes(b)) return nullptr;
+	if (b.n < 2) return build_tiny(desc, b.mesh_base);
+	plan_build(b, force_bits);
+
+	b.ws = &g_workspace[b.device];
+	std::lock_guard<std::mutex> ws_lock(b.ws->mutex);      // held to the end: every exit below has waited for what it enqueued (Build::give_up, finish)
+	if (!prepare_workspace(b) || !ingest(b) || !keys_and_sort(b) || !emit(b) || !refit(b)) return nullptr;
+	alloc_node_estimate(b);
+	if (b.tile_mode && !collapse_tiles(b)) return nullptr;
+	if (!b.tiles_done && !collapse_levels(b)) return nullptr;
+	if (!finish(b)) return nullptr;
+
+	*narrow_key = b.packed && b.packed_bits < 40u && (uint64_t)b.equal_codes * 8u > (uint64_t)b.n;
+	if (knobs.timing) fprintf(stderr, "rtk_amd build: %u key bits, %u of %u sorted neighbours share a code%s\n", b.packed ? b.packed_bits : BUILD_KEY_BITS, b.equal_codes, b.n,
+		*narrow_key ? " -> key too narrow for this scene" : "");
+	if (!knobs.keep_workspace) {
+		(void)hipFree(b.ws->base);
+		b.ws->base = nullptr;
+		b.ws->cap = 0;
+	}
+	return b.ds;
+}
+
+} // namespace
 
 // The key width follows the NUMBER of triangles (ceil(log2 n) + 8 bits of the 63-bit code: four radix passes up to 2^24
 // triangles), which assumes they are spread over the scene box. Where they are not -- a dense mesh in 1 % of the box --
@@ -2496,13 +2324,14 @@ static rtk_dev_scene *build_impl(const rtk_scene_desc *desc, uint32_t force_bits
 // scene, the same tree quality as before the narrow keys, nothing for scenes that do not need it.
 extern "C" rtk_dev_scene *rtk_dev_scene_build(const rtk_scene_desc *desc)
 {
+	const BuildKnobs knobs = read_build_knobs();
 	bool narrow = false;
-	rtk_dev_scene *ds = build_impl(desc, 0u, &narrow);
+	rtk_dev_scene *ds = build_impl(desc, knobs, 0u, &narrow);
 	if (ds) ds->boxes_exact = true;            // (every box the union of what is below it: what a refit of some meshes relies on)
-	if (!ds || !narrow || (getenv("RTK_AMD_KEY_REBUILD") && atoi(getenv("RTK_AMD_KEY_REBUILD")) == 0)) return ds;
+	if (!ds || !narrow || !knobs.key_rebuild) return ds;
 	const double first_ms = ds->build_ms;
 	rtk_dev_scene_free(ds);
-	ds = build_impl(desc, 40u, &narrow);
+	ds = build_impl(desc, knobs, 40u, &narrow);
 	if (ds) { ds->build_ms += first_ms; ds->boxes_exact = true; }
 	return ds;
 }
@@ -2539,205 +2368,6 @@ int rtk_scene_side_arrays(const rtk_dev_scene *ds_c, hipStream_t stream)
 	ds->view.slot_tri = slot_tri;
 	ds->side_ready = true;
 	return RTK_AMD_OK;
-}
-
-// =====================================================================================
-// export: device BVH -> reference-format blob (writer intent rtk.c:1719-1774)
-// =====================================================================================
-
-namespace {
-
-struct ExportPlan {
-	std::vector<DevNode> nodes;
-	std::vector<DevTri> tris;
-	std::vector<uint32_t> vertex_index, slot_mesh, slot_tri;
-	// per leaf (in slot order)
-	struct Leaf { uint32_t first, count; uint64_t offset; uint64_t group_byte; uint32_t num_meshes; std::vector<uint8_t> vix; };
-	std::vector<Leaf> leaves;
-	std::unordered_map<uint32_t, uint32_t> leaf_of_slot;
-	std::vector<rtk_vertex> vertices;
-	uint64_t node_off = 128, leaf_off = 0, vert_off = 0, total = 0;
-};
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
-
-bool download(const rtk_dev_scene *ds, ExportPlan &ep)
-{
-	if (rtk_scene_side_arrays(ds, nullptr) != RTK_AMD_OK) return false;
-	const DevSceneView &v = ds->view;
-	ep.nodes.resize(v.num_nodes);
-	ep.tris.resize(v.num_tris);
-	ep.vertex_index.resize(3 * (size_t)v.num_tris);
-	ep.slot_mesh.resize(v.num_tris);
-	ep.slot_tri.resize(v.num_tris);
-	bool ok = hipMemcpy(ep.nodes.data(), v.nodes, ep.nodes.size() * sizeof(DevNode), hipMemcpyDeviceToHost) == hipSuccess;
-	if (v.num_tris) {
-		ok = ok && hipMemcpy(ep.tris.data(), v.tris, ep.tris.size() * sizeof(DevTri), hipMemcpyDeviceToHost) == hipSuccess;
-		ok = ok && hipMemcpy(ep.vertex_index.data(), v.vertex_index, ep.vertex_index.size() * 4, hipMemcpyDeviceToHost) == hipSuccess;
-		ok = ok && hipMemcpy(ep.slot_mesh.data(), v.slot_mesh, ep.slot_mesh.size() * 4, hipMemcpyDeviceToHost) == hipSuccess;
-		ok = ok && hipMemcpy(ep.slot_tri.data(), v.slot_tri, ep.slot_tri.size() * 4, hipMemcpyDeviceToHost) == hipSuccess;
-	}
-	if (!ok) rtk_set_error("export: device to host copy failed: %s", hipGetErrorString(hipGetLastError()));
-	return ok;
-}
-
-// Lay out leaves and vertex groups. Leaves are visited in slot order (= Morton order), so
-// consecutive leaves are neighbours in space and share vertices of indexed meshes; a
-// vertex group (<= 256 vertices, u8 indices, rtk.c:83, 1186) is closed when the next leaf
-// would not fit.
-bool plan(ExportPlan &ep)
-{
-	std::vector<uint32_t> firsts;
-	for (const DevNode &n : ep.nodes)
-		for (int k = 0; k < 4; k++)
-			if (n.child[k] != RTK_REF_NONE && (n.child[k] & RTK_REF_LEAF)) firsts.push_back(n.child[k] & 0x7fffffffu);
-	std::sort(firsts.begin(), firsts.end());
-	firsts.erase(std::unique(firsts.begin(), firsts.end()), firsts.end());
-	ep.leaves.resize(firsts.size());
-	std::unordered_map<uint64_t, uint32_t> group;   // (mesh<<32 | vertex index) -> index in the open group
-	size_t group_start = 0;                          // in vertices
-	uint64_t leaf_bytes = 64;                        // null leaf first (rtk.c:1763-1765)
-	for (size_t li = 0; li < firsts.size(); li++) {
-		ExportPlan::Leaf &lf = ep.leaves[li];
-		lf.first = firsts[li];
-		if (lf.first >= ep.tris.size()) { rtk_set_error("export: leaf reference out of range"); return false; }
-		lf.count = ep.tris[lf.first].spare;
-		if (lf.count == 0 || lf.count > 63 || (size_t)lf.first + lf.count > ep.tris.size()) { rtk_set_error("export: leaf of %u triangles cannot be written (1..63)", lf.count); return false; }
-		ep.leaf_of_slot[lf.first] = (uint32_t)li;
-		// distinct vertices this leaf would add
-		std::vector<uint64_t> keys(3 * (size_t)lf.count);
-		for (uint32_t i = 0; i < lf.count; i++)
-			for (int c = 0; c < 3; c++)
-				keys[3 * i + c] = ((uint64_t)ep.slot_mesh[lf.first + i] << 32) | ep.vertex_index[3 * (size_t)(lf.first + i) + c];
-		size_t fresh = 0;
-		{
-			std::vector<uint64_t> uniq(keys);
-			std::sort(uniq.begin(), uniq.end());
-			uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
-			for (uint64_t k : uniq) if (!group.count(k)) fresh++;
-		}
-		if (group.size() + fresh > 256) {
-			group.clear();
-			group_start = align_up(ep.vertices.size(), 4);    // 64-byte aligned groups (rtk.c:193)
-			ep.vertices.resize(group_start);
-		}
-		lf.group_byte = (uint64_t)group_start * 16u;
-		lf.vix.resize(3 * (size_t)lf.count);
-		std::vector<uint32_t> meshes;
-		for (uint32_t i = 0; i < lf.count; i++) {
-			const DevTri &t = ep.tris[lf.first + i];
-			const float *pv[3] = { t.v0, t.v1, t.v2 };
-			for (int c = 0; c < 3; c++) {
-				const uint64_t k = keys[3 * i + c];
-				auto it = group.find(k);
-				uint32_t idx;
-				if (it == group.end()) {
-					idx = (uint32_t)group.size();
-					group[k] = idx;
-					rtk_vertex v;
-					v.position.x = pv[c][0]; v.position.y = pv[c][1]; v.position.z = pv[c][2];
-					v.index = (uint32_t)k;
-					ep.vertices.push_back(v);
-				} else idx = it->second;
-				lf.vix[3 * i + c] = (uint8_t)idx;
-			}
-			const uint32_t mesh = ep.slot_mesh[lf.first + i];
-			if (std::find(meshes.begin(), meshes.end(), mesh) == meshes.end()) meshes.push_back(mesh);
-		}
-		lf.num_meshes = (uint32_t)meshes.size();
-		lf.offset = leaf_bytes;
-		leaf_bytes += align_up(8 + 8 * (size_t)((lf.count + 3u) & ~3u) + 4 * meshes.size(), 64);
-	}
-	ep.leaf_off = align_up(ep.node_off + ep.nodes.size() * 128, 128);
-	ep.vert_off = align_up(ep.leaf_off + leaf_bytes, 128);
-	ep.total = align_up(ep.vert_off + align_up(ep.vertices.size(), 4) * 16, 128);
-	return true;
-}
-
-void write_blob(const ExportPlan &ep, char *blob)
-{
-	memset(blob, 0, ep.total);
-	rtk_scene *s = (rtk_scene *)blob;
-	static const char magic[8] = { 0, 'R', 'T', 'K', '\r', '\n', 0x1a, '\n' };
-	memcpy(s->magic, magic, 8);
-	s->endian = 0xaabb; s->sizeof_real = 4; s->pad_0 = 0; s->version = 1; s->pad_1 = 0;
-	s->size_in_bytes = ep.total; s->node_offset = ep.node_off; s->leaf_offset = ep.leaf_off; s->vertex_offset = ep.vert_off;
-	for (size_t i = 0; i < ep.nodes.size(); i++) {
-		const DevNode &n = ep.nodes[i];
-		char *dst = blob + ep.node_off + i * 128;
-		memcpy(dst, n.bx, 96);
-		uint64_t ptr[4];
-		for (int k = 0; k < 4; k++) {
-			const uint32_t r = n.child[k];
-			if (r == RTK_REF_NONE) ptr[k] = ep.leaf_off | 1u;                               // null leaf (rtk.c:1619, tagged: B19)
-			else if (r & RTK_REF_LEAF) ptr[k] = (ep.leaf_off + ep.leaves[ep.leaf_of_slot.at(r & 0x7fffffffu)].offset) | 1u;
-			else ptr[k] = ep.node_off + (uint64_t)r * 128u;
-		}
-		memcpy(dst + 96, ptr, 32);
-	}
-	for (const ExportPlan::Leaf &lf : ep.leaves) {
-		char *dst = blob + ep.leaf_off + lf.offset;
-		const uint64_t info = (uint64_t)lf.count | (ep.vert_off + lf.group_byte);
-		memcpy(dst, &info, 8);
-		const size_t n4 = (lf.count + 3u) & ~3u;
-		uint32_t *table = (uint32_t *)(dst + 8 + 8 * n4);
-		uint32_t nm = 0;
-		for (uint32_t i = 0; i < lf.count; i++) {
-			uint8_t *rec = (uint8_t *)dst + 8 + 8 * (size_t)i;
-			rec[0] = lf.vix[3 * i]; rec[1] = lf.vix[3 * i + 1]; rec[2] = lf.vix[3 * i + 2];
-			const uint32_t mesh = ep.slot_mesh[lf.first + i];
-			uint32_t k = 0;
-			for (; k < nm; k++) if (table[k] == mesh) break;
-			if (k == nm) table[nm++] = mesh;
-			rec[3] = (uint8_t)k;
-			memcpy(rec + 4, &ep.slot_tri[lf.first + i], 4);
-		}
-	}
-	if (!ep.vertices.empty()) memcpy(blob + ep.vert_off, ep.vertices.data(), ep.vertices.size() * 16);
-}
-
-// one export plan is cached per scene between export_size and export
-std::mutex g_plans_mutex;
-std::unordered_map<const rtk_dev_scene *, ExportPlan *> g_plans;
-
-ExportPlan *get_plan(const rtk_dev_scene *ds)
-{
-	std::lock_guard<std::mutex> lock(g_plans_mutex);
-	auto it = g_plans.find(ds);
-	if (it != g_plans.end()) return it->second;
-	ExportPlan *ep = new ExportPlan();
-	if (!download(ds, *ep) || !plan(*ep)) { delete ep; return nullptr; }
-	g_plans[ds] = ep;
-	return ep;
-}
-
-void drop_plan(const rtk_dev_scene *ds)
-{
-	std::lock_guard<std::mutex> lock(g_plans_mutex);
-	auto it = g_plans.find(ds);
-	if (it != g_plans.end()) { delete it->second; g_plans.erase(it); }
-}
-
-} // namespace
-
-void rtk_export_forget(const rtk_dev_scene *ds) { drop_plan(ds); }
-
-extern "C" size_t rtk_dev_scene_export_size(const rtk_dev_scene *ds)
-{
-	if (!ds) { rtk_set_error("rtk_dev_scene_export_size: NULL scene"); return 0; }
-	ExportPlan *ep = get_plan(ds);
-	return ep ? (size_t)ep->total : 0;
-}
-
-extern "C" rtk_scene *rtk_dev_scene_export(const rtk_dev_scene *ds, void *buffer, size_t size)
-{
-	if (!ds || !buffer) { rtk_set_error("rtk_dev_scene_export: NULL argument"); return nullptr; }
-	ExportPlan *ep = get_plan(ds);
-	if (!ep) return nullptr;
-	if (size < ep->total) { rtk_set_error("rtk_dev_scene_export: buffer too small (%zu < %llu)", size, (unsigned long long)ep->total); return nullptr; }
-	write_blob(*ep, (char *)buffer);
-	drop_plan(ds);
-	return (rtk_scene *)buffer;
 }
 
 // =====================================================================================
@@ -2876,7 +2506,7 @@ extern "C" rtk_scene *rtk_finish_build(rtk_build *build)
 {
 	if (!build) return nullptr;
 	const size_t need = rtk_get_build_size(build);
-	void *buffer = need ? aligned_alloc(128, align_up(need, 128)) : nullptr;
+	void *buffer = need ? aligned_alloc(128, (need + 127) & ~(size_t)127) : nullptr;
 	if (!buffer) {                                            // rtk.c:1779-1783: free the build, return NULL
 		if (build->scene) rtk_dev_scene_free(build->scene);
 		if (build->cpu) rtk_cpu_build_free(build->cpu);

@@ -63,7 +63,7 @@ extern "C" rtk_dev_scene *rtk_dev_scene_upload_buffer(const void *blob, size_t b
 	return rtk_dev_scene_from_host_bvh(h);
 }
 
-void rtk_export_forget(const rtk_dev_scene *ds);   // rtk_build.hip
+void rtk_export_forget(const rtk_dev_scene *ds);   // rtk_export.hip
 
 extern "C" void rtk_dev_scene_free(rtk_dev_scene *ds)
 {

@@ -254,12 +254,12 @@ struct WorkspaceLoan {
 };
 bool rtk_is_device_ptr(const void *p);         // hipMalloc'ed memory?
 static inline size_t rtk_padded(size_t bytes) { return ((bytes ? bytes : 1) + 255u) & ~(size_t)255u; }   // sizes inside one allocation: 256-byte steps
-void rtk_export_forget(const rtk_dev_scene *ds);   // the scene's cached export plan, if any (rtk_build.hip)
+void rtk_export_forget(const rtk_dev_scene *ds);   // the scene's cached export plan, if any (rtk_export.hip)
 // the two constants of the surface area heuristic, for the builder that splits by them and for rtk_dev_scene_quality that
 // measures by them: 0.5 per node visited, 1.0 per triangle tested, RTK_AMD_SAH_CN / RTK_AMD_SAH_CT override (rtk_build.hip)
 void rtk_sah_costs(float *cost_node, float *cost_tri);
 
-// -- radix sort shared with the builder (rtk_build.hip) --
+// -- radix sort shared with the builder (rtk_sort.hip) --
 size_t rtk_sort_scratch_words(uint32_t n);
 bool rtk_sort_pairs_async(unsigned long long *keys_a, unsigned long long *keys_b, uint32_t *vals_a, uint32_t *vals_b,
 	uint32_t n, uint32_t key_bits, uint32_t *scratch, hipStream_t stream);
