@@ -213,6 +213,54 @@ typedef struct rtk_dev_scene_quality_info {
 } rtk_dev_scene_quality_info;
 int rtk_dev_scene_quality(const rtk_dev_scene *ds, rtk_dev_scene_quality_info *out, void *stream);
 
+/* Big leaves of a scene split in place: every leaf that holds more than max_leaf triangles is replaced by a small subtree of
+ * 4-wide nodes whose leaves hold at most max_leaf. What a scene that arrived as a blob needs before it is traced many times:
+ * the reference's builder, the CPU task builder and every file on disk make leaves of 4 to 63 triangles, the device builder
+ * leaves of at most 3, and the hand-written packet kernels are made for those (a scene with more than 2 % bigger leaves is
+ * kept off some of them and pays for every triangle of a leaf a beam touches). The top of the tree, which a binned-SAH
+ * builder made well, stays as it is. max_leaf == 0: the device builder's own limit (RTK_AMD_MAX_LEAF, default 3); 1 .. 63 are
+ * taken as given.
+ *   - STAYS: primitive ids, the set of triangles, mesh_base, every handle. Every existing node's number and boxes: loose
+ *     boxes of an upload stay loose (a refit makes them exact as before). The slot range of every former leaf: its K
+ *     triangles are permuted inside [first, first + K) and nowhere else, so rtk_dev_scene_primitive_order changes there and
+ *     stays a permutation.
+ *   - CHANGES: a child word that named a split leaf names a new node. New nodes are appended at [old num_nodes, new
+ *     num_nodes): subtree after subtree in the order of their former leaf's first slot, breadth-first inside a subtree, so a
+ *     child always comes after its parent. Every box of a new node is the exact union of the triangles below it. The
+ *     end-of-leaf flags and leaf sizes of the permuted records, and the entries of the four side arrays (vertex indices,
+ *     primitive -> slot, slot -> mesh, slot -> triangle) where the scene has made them, follow the permutation. Compressed
+ *     nodes, child order words and the scene's constants are made again over the whole new tree. num_nodes, node_bytes,
+ *     total_device_bytes, max_depth, stack_entries (3 * max_depth + 1) and the share of big leaves that picks the kernels
+ *     are recomputed; launch scratch grows by itself at the next launch.
+ *   - FORGOTTEN, and made again on next use: the refit schedule, the tables of rtk_dev_scene_refit_meshes, the cached export
+ *     plan. sah_cost_at_build is forgotten too: the next rtk_dev_scene_quality call sets it anew if the scene has never had
+ *     a refit (after a refit it stays 0, as before).
+ *   - DEPTH: the subtree that replaces a leaf of K triangles is at most 2 * ceil(log4(K / max_leaf)) node levels deep (a
+ *     four-way median split needs ceil(log4(K / max_leaf)); the rest is the room the surface-area choice of the cuts gets),
+ *     whatever the triangles are: equal, on a line, not finite. Every set of at most max_leaf triangles is a leaf; every
+ *     new node has two to four children, none of them empty.
+ *   - DETERMINISTIC: the result is a pure function of the scene's bits and max_leaf. Two scenes with equal content_hash
+ *     have equal content_hash afterwards; the replicas of a multi-GPU context agree.
+ *   - The call WRITES the scene and MOVES its node arrays: no trace, refit or measurement of the scene may be in flight on
+ *     another stream or thread. It takes the lock of the refits and is synchronous; work queued earlier on `stream` is
+ *     ordered before it.
+ *   - Nothing to split (a device-built scene, a second call with the same limit, a scene without triangles): success,
+ *     leaves_split == 0, no bit changes, nothing is kept allocated, nothing is forgotten.
+ *   - RTK_AMD_ERR_BAD_ARG: ds NULL, max_leaf > 63, out->struct_size < sizeof(rtk_dev_split_info); decided before any HIP
+ *     call. RTK_AMD_ERR_OOM is decided before the scene is written: everything is allocated first. While the call runs the
+ *     scene needs its new node arrays beside the old ones (192 bytes per node) and 4 bytes per triangle and node.
+ * rtk_mgpu_split_leaves does the same on every GPU of the context; rtk_mgpu_scene handles stay valid. */
+typedef struct rtk_dev_split_info {
+	uint32_t struct_size;        /* sizeof(rtk_dev_split_info), set by the caller */
+	uint32_t max_leaf;           /* the limit that was applied (after resolving 0) */
+	uint64_t leaves_split;       /* leaves that held more than max_leaf triangles */
+	uint64_t nodes_added;        /* num_nodes after - num_nodes before */
+	uint32_t largest_leaf_before, largest_leaf_after;
+	uint32_t max_depth_before, max_depth_after;
+	double split_ms;             /* wall time inside the call */
+} rtk_dev_split_info;
+int rtk_dev_scene_split_leaves(rtk_dev_scene *ds, uint32_t max_leaf, rtk_dev_split_info *out /* may be NULL */, void *stream);
+
 /* Structural check of a device scene, run on the device (the loader/validator the reference lacks,
  * SURVEY.md section 5; blob-level checks happen in rtk_dev_scene_upload). Every child box must contain
  * what is below it, every triangle slot must sit in exactly one leaf, every node but the root must be
@@ -340,6 +388,7 @@ int rtk_mgpu_build(rtk_mgpu *m, const rtk_scene_desc *desc);      /* rtk_dev_sce
 int rtk_mgpu_upload(rtk_mgpu *m, const rtk_scene *scene);         /* rtk_dev_scene_upload on every GPU */
 int rtk_mgpu_refit(rtk_mgpu *m, const rtk_scene_desc *desc);      /* rtk_dev_scene_refit on every GPU of the context (handles stay valid) */
 int rtk_mgpu_refit_meshes(rtk_mgpu *m, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids);   /* rtk_dev_scene_refit_meshes on every GPU */
+int rtk_mgpu_split_leaves(rtk_mgpu *m, uint32_t max_leaf);        /* rtk_dev_scene_split_leaves on every GPU of the context (handles stay valid) */
 /* host rays in, host records out (records[i] belongs to rays[i]) */
 int rtk_mgpu_trace_rays(rtk_mgpu *m, const rtk_ray *rays, size_t n, rtk_hit_record *records, const rtk_trace_opts *opts);
 /* device-resident shards: d_rays[r] / d_records[r] (counts[r] elements) live on GPU r of the context; if d_gathered

@@ -58,6 +58,16 @@ class SceneQuality(C.Structure):
         return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_}
 
 
+class SplitInfo(C.Structure):
+    """rtk_dev_split_info: what rtk_dev_scene_split_leaves did."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_leaf", C.c_uint32), ("leaves_split", C.c_uint64), ("nodes_added", C.c_uint64),
+                ("largest_leaf_before", C.c_uint32), ("largest_leaf_after", C.c_uint32), ("max_depth_before", C.c_uint32),
+                ("max_depth_after", C.c_uint32), ("split_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_}
+
+
 class TraceOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("image_width", C.c_uint32),
                 ("image_height", C.c_uint32), ("refill_min", C.c_uint32), ("blocks_per_cu", C.c_uint32),
@@ -107,7 +117,7 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_mgpu_trace_rays_device_striped", "rtk_mgpu_striped_segment",
                      "rtk_dev_scene_refit", "rtk_dev_scene_last_refit_ms", "rtk_mgpu_refit",
                      "rtk_dev_scene_refit_meshes", "rtk_dev_scene_last_refit_nodes", "rtk_mgpu_refit_meshes",
-                     "rtk_dev_scene_quality"]
+                     "rtk_dev_scene_quality", "rtk_dev_scene_split_leaves", "rtk_mgpu_split_leaves"]
 
 _lib = None
 
@@ -184,6 +194,10 @@ def lib():
     L.rtk_dev_scene_last_refit_nodes.argtypes = [C.c_void_p]
     L.rtk_dev_scene_quality.restype = C.c_int
     L.rtk_dev_scene_quality.argtypes = [C.c_void_p, C.POINTER(SceneQuality), C.c_void_p]
+    L.rtk_dev_scene_split_leaves.restype = C.c_int
+    L.rtk_dev_scene_split_leaves.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(SplitInfo), C.c_void_p]
+    L.rtk_mgpu_split_leaves.restype = C.c_int
+    L.rtk_mgpu_split_leaves.argtypes = [C.c_void_p, C.c_uint32]
     L.rtk_mgpu_refit_meshes.restype = C.c_int
     L.rtk_mgpu_refit_meshes.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_size_t]
     L.rtk_mgpu_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(TraceOpts)]
@@ -337,6 +351,19 @@ class DeviceScene:
         d = q.as_dict()
         d["ratio"] = d["sah_cost"] / d["sah_cost_at_build"] if d["sah_cost_at_build"] != 0.0 else None
         return d
+
+    def split_leaves(self, max_leaf=0):
+        """Every leaf of more than max_leaf triangles becomes a small subtree with leaves of at most max_leaf
+        (rtk_dev_scene_split_leaves), in place, on the current stream; 0 = the device builder's limit (3). What an uploaded
+        blob wants before it is traced many times. Returns the fields of rtk_dev_split_info as a dict. Synchronous; the
+        scene must not be traced from another stream or thread meanwhile."""
+        if not 0 <= int(max_leaf) <= 63:
+            raise RtkError("split_leaves: max_leaf %r (0 = the device builder's limit, else 1 .. 63)" % (max_leaf,))
+        _torch()
+        s = SplitInfo()
+        s.struct_size = C.sizeof(SplitInfo)
+        _check(lib().rtk_dev_scene_split_leaves(self.handle, int(max_leaf), C.byref(s), _stream_ptr()), "rtk_dev_scene_split_leaves")
+        return s.as_dict()
 
     def free(self):
         if self.handle:

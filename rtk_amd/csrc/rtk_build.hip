@@ -1694,6 +1694,19 @@ struct BuildKnobs {
 	bool key_rebuild;        // RTK_AMD_KEY_REBUILD=0: a scene whose narrow keys collide too often is not built again with wide ones
 };
 
+} // namespace
+
+// RTK_AMD_MAX_LEAF, 1 .. 63, default 3: the device builder's leaf limit, and what rtk_dev_scene_split_leaves takes for max_leaf 0
+uint32_t rtk_build_max_leaf()
+{
+	uint32_t max_leaf = (uint32_t)env_float("RTK_AMD_MAX_LEAF", 3.0f);
+	if (max_leaf < 1) max_leaf = 1;
+	if (max_leaf > 63) max_leaf = 63;         // 6-bit count in the blob's leaf header (rtk.c:188)
+	return max_leaf;
+}
+
+namespace {
+
 BuildKnobs read_build_knobs()
 {
 	BuildKnobs k;
@@ -1702,9 +1715,7 @@ BuildKnobs read_build_knobs()
 	// leaves of at most three triangles: a leaf of fewer than four is one partial group for the reference's group-of-four rule
 	// (rtk.c:302-336: double-precision edge functions, no redo), which is all the hand-written packet kernel implements; with
 	// cn = 0.5 the SAH rule made 1.008 triangles per leaf at a limit of 8, so nothing of substance changes
-	k.max_leaf = (uint32_t)env_float("RTK_AMD_MAX_LEAF", 3.0f);
-	if (k.max_leaf < 1) k.max_leaf = 1;
-	if (k.max_leaf > 63) k.max_leaf = 63;     // 6-bit count in the blob's leaf header (rtk.c:188)
+	k.max_leaf = rtk_build_max_leaf();
 	k.sort_packed = env_unless_zero("RTK_AMD_SORT_PACKED");
 	k.key_bits = 0;
 	if (getenv("RTK_AMD_KEY_BITS")) { const int kb = atoi(getenv("RTK_AMD_KEY_BITS")); if (kb >= 8 && kb <= 40 && kb % 8 == 0) k.key_bits = (uint32_t)kb; }
@@ -2254,6 +2265,7 @@ bool finish(Build &b)
 {
 	rtk_dev_scene *ds = b.ds;
 	ds->total_bytes += b.node_cap * (sizeof(DevNode) + sizeof(DevNodeQ));
+	ds->node_cap = b.node_cap;
 	if (hipStreamSynchronize(b.bs) != hipSuccess || (b.side_busy && hipStreamSynchronize(b.ws->side) != hipSuccess)) return b.fail("sync");
 	if (!b.tiles_done) {
 		b.equal_codes = b.results->equal_codes;

@@ -129,6 +129,7 @@ struct RefitSchedule {
 	void *d_meshes = nullptr;                  // [num_meshes] where each mesh's positions are read from (filled per refit)
 	bool max_vertex_ready = false;
 	std::vector<uint32_t> max_vertex;          // [num_meshes] largest vertex index the mesh's triangles use (made when a mesh first arrives in host memory)
+	size_t bytes = 0;                          // what d_order and d_level_start added to total_bytes (rtk_dev_scene_split_leaves drops them)
 };
 
 // What a refit of SOME meshes needs on top of the schedule (rtk_dev_scene_refit_meshes): who is above a node, which node holds
@@ -146,6 +147,7 @@ struct RefitPartial {
 	uint32_t *d_list_start = nullptr;          // [heights + 1] where each height begins in d_list
 	void *d_ranges = nullptr;                  // [num_meshes + 1] runs of listed meshes in d_mesh_slots (filled per call)
 	uint32_t epoch = 0;                        // of the last call (0: none yet; d_dirty starts cleared)
+	size_t bytes = 0;                          // what the tables added to total_bytes
 };
 
 // What rtk_dev_scene_quality keeps per scene (rtk_quality.hip): its partial records and result slot on the device, made by the
@@ -165,6 +167,8 @@ struct rtk_dev_scene {
 	uint32_t max_depth = 0;
 	uint32_t stack_entries = 0;
 	uint32_t first_top = 0;                // device build, tile collapse: nodes [1, first_top) are the tiles', 0 and [first_top, n) the ones above them (0: one run)
+	uint32_t first_split = 0;              // rtk_dev_scene_split_leaves: nodes [first_split, n) were appended by a split, each after its parent (0: none)
+	uint64_t node_cap = 0;                 // nodes the node allocation holds where exact and compressed nodes share one (a device build, a split; 0: an upload's two arrays of num_nodes)
 	uint64_t total_bytes = 0;
 	double build_ms = 0.0;
 	double big_leaf_fraction = 0.0;        // leaves of more than three triangles (uploads; device builds make ~none): the assembly packet kernel hands those tiles back

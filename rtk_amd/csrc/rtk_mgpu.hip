@@ -179,6 +179,18 @@ extern "C" int rtk_mgpu_refit(rtk_mgpu *m, const rtk_scene_desc *desc)
 	});
 }
 
+// big leaves split on every GPU (rtk_dev_scene_split_leaves): the call is a pure function of the scene's bits, so the replicas agree afterwards
+extern "C" int rtk_mgpu_split_leaves(rtk_mgpu *m, uint32_t max_leaf)
+{
+	if (!m) { rtk_set_error("rtk_mgpu_split_leaves: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
+	if (max_leaf > 63u) { rtk_set_error("rtk_mgpu_split_leaves: max_leaf %u (0 = the device builder's limit, else 1 .. 63)", max_leaf); return RTK_AMD_ERR_BAD_ARG; }
+	for (const DeviceSlot &s : m->slots) if (!s.scene) { rtk_set_error("rtk_mgpu_split_leaves: the context holds no scene"); return RTK_AMD_ERR_BAD_ARG; }
+	return for_each_slot_in_parallel(m, [&](size_t j) -> int {
+		DeviceSlot &s = m->slots[j];
+		return rtk_dev_scene_split_leaves(s.scene, max_leaf, nullptr, s.trace_stream);
+	});
+}
+
 // the same for some meshes (rtk_dev_scene_refit_meshes)
 extern "C" int rtk_mgpu_refit_meshes(rtk_mgpu *m, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids)
 {

@@ -495,7 +495,8 @@ int make_schedule(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
 		return rc;
 	}
 	ds->allocs.push_back(d_order); ds->allocs.push_back(d_small);
-	ds->total_bytes += (size_t)n * 4 + level_start.size() * 4 + num_meshes * sizeof(RefitMesh);
+	rs.bytes = (size_t)n * 4 + level_start.size() * 4 + num_meshes * sizeof(RefitMesh);
+	ds->total_bytes += rs.bytes;
 	rs.d_order = (uint32_t *)d_order;
 	rs.d_level_start = (uint32_t *)d_small;
 	rs.level_start.swap(level_start);
@@ -576,7 +577,8 @@ int make_partial_tables(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
 		return RTK_AMD_ERR_HIP;
 	}
 	ds->allocs.push_back(mem);
-	ds->total_bytes += (size_t)n * 12 + (size_t)nt * 8 + ((size_t)nb + 1) * 4 + (heights + 1) * 4 + (num_meshes + 1) * sizeof(RefitRange);
+	rp.bytes = (size_t)n * 12 + (size_t)nt * 8 + ((size_t)nb + 1) * 4 + (heights + 1) * 4 + (num_meshes + 1) * sizeof(RefitRange);
+	ds->total_bytes += rp.bytes;
 	rp.d_parent = d_parent; rp.d_slot_node = d_slot_node; rp.d_mesh_slots = d_mesh_slots;
 	rp.d_dirty = (uint32_t *)(base + o_dirty); rp.d_list = (uint32_t *)(base + o_list); rp.d_block = (uint32_t *)(base + o_block);
 	rp.d_list_start = (uint32_t *)(base + o_list_start); rp.d_ranges = base + o_ranges;

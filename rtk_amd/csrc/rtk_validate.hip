@@ -37,7 +37,7 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long x)
 	return x;
 }
 
-__global__ void k_check_nodes(DevSceneView sc, uint32_t first_top, uint32_t *slot_seen, uint32_t *node_seen, unsigned long long *c)
+__global__ void k_check_nodes(DevSceneView sc, uint32_t first_top, uint32_t first_split, uint32_t *slot_seen, uint32_t *node_seen, unsigned long long *c)
 {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= sc.num_nodes) return;
@@ -93,7 +93,9 @@ __global__ void k_check_nodes(DevSceneView sc, uint32_t first_top, uint32_t *slo
 		} else {
 			// (first_top 0: one run of numbers)
 			const bool tile_node = i != 0u && i < first_top, tile_child = ref != 0u && ref < first_top;
-			const bool order_ok = tile_node ? (ref > i && tile_child) : (ref > i || tile_child);
+			// (a node appended by rtk_dev_scene_split_leaves comes after its parent, whichever run the parent is in)
+			const bool appended = first_split != 0u && ref >= first_split && ref > i;
+			const bool order_ok = appended || (tile_node ? (ref > i && tile_child) : (ref > i || tile_child));
 			if (ref >= sc.num_nodes || !order_ok) { report(c, C_BAD_REF, i); continue; }
 			atomicAdd(&node_seen[ref], 1u);
 			const DevNode ch = sc.nodes[ref];
@@ -165,7 +167,7 @@ extern "C" int rtk_dev_scene_validate(const rtk_dev_scene *ds, rtk_dev_scene_che
 		h[C_FIRST_BAD] = ~0ull;
 		if (hipMemset(d_seen, 0, words * 4) != hipSuccess || hipMemcpy(d_c, h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess) { rc = RTK_AMD_ERR_HIP; break; }
 		uint32_t *slot_seen = d_seen, *node_seen = d_seen + v.num_tris, *prim_seen = node_seen + v.num_nodes;
-		hipLaunchKernelGGL(k_check_nodes, dim3((v.num_nodes + 127u) / 128u), dim3(128), 0, 0, v, ds->first_top, slot_seen, node_seen, d_c);
+		hipLaunchKernelGGL(k_check_nodes, dim3((v.num_nodes + 127u) / 128u), dim3(128), 0, 0, v, ds->first_top, ds->first_split, slot_seen, node_seen, d_c);
 		if (v.num_tris) hipLaunchKernelGGL(k_check_slots, dim3((v.num_tris + 255u) / 256u), dim3(256), 0, 0, v, slot_seen, prim_seen, d_c);
 		const uint32_t m = v.num_nodes > v.num_prims ? v.num_nodes : v.num_prims;
 		// a scene built here holds every primitive of its meshes; an uploaded blob may leave ids unused
