@@ -1790,7 +1790,7 @@ struct Build {
 	DevTri *d_tris = nullptr;
 	EmitSrc emit_src = {};
 	// the collapse
-	void *node_mem = nullptr;         // [DevNode x node_cap | DevNodeQ x node_cap], owned by the scene (the last of its allocs)
+	void *node_mem = nullptr;         // [DevNode x node_cap | DevNodeQ x node_cap], owned by the scene (Build::node_alloc)
 	size_t node_cap = 0;
 	LevelState h_state = {};
 	bool tiles_done = false;
@@ -1830,13 +1830,14 @@ struct Build {
 		return give_up();
 	}
 	// a device allocation the scene owns
-	char *dev_alloc(size_t bytes)
+	char *dev_alloc(size_t bytes) { return (char *)ds->mem.own(bytes ? bytes : 16, bytes); }
+	// the scene's node block for node_cap nodes, instead of the one there is (error paths free it with the scene)
+	bool node_alloc()
 	{
-		void *p = nullptr;
-		if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr;
-		ds->allocs.push_back(p);
-		ds->total_bytes += bytes;
-		return (char *)p;
+		ds->mem.release(node_mem);
+		const size_t bytes = node_cap * (sizeof(DevNode) + sizeof(DevNodeQ));
+		node_mem = ds->mem.own(bytes, bytes);
+		return node_mem != nullptr;
 	}
 };
 
@@ -2115,8 +2116,7 @@ bool refit(Build &b)
 void alloc_node_estimate(Build &b)
 {
 	b.node_cap = b.knobs.est_div > 0 ? (size_t)b.n / (size_t)b.knobs.est_div + 16 : (size_t)b.n / 2 + 4096;
-	if (hipMalloc(&b.node_mem, b.node_cap * (sizeof(DevNode) + sizeof(DevNodeQ))) != hipSuccess) { (void)hipGetLastError(); b.node_mem = nullptr; b.node_cap = 0; }
-	else b.ds->allocs.push_back(b.node_mem);      // owned by the scene from here on (error paths free it with the scene)
+	if (!b.node_alloc()) { (void)hipGetLastError(); b.node_cap = 0; }
 }
 
 // The level-by-level collapse into `target` (room for `cap` nodes; more are counted but not written). False: a launch or the
@@ -2212,10 +2212,8 @@ bool collapse_tiles(Build &b)
 		if (attempt > 0) return b.fail("collapse (internal error: node count changed between two runs)");
 		// the estimate was too small: an exact allocation, and the tiles and the move once more (the nodes above the tiles stay
 		// where they are in the workspace; every pass is deterministic)
-		if (b.node_mem) { b.ds->allocs.pop_back(); (void)hipFree(b.node_mem); b.node_mem = nullptr; }     // it was the last one pushed
 		b.node_cap = b.total_nodes;
-		if (hipMalloc(&b.node_mem, b.node_cap * (sizeof(DevNode) + sizeof(DevNodeQ))) != hipSuccess) { b.node_mem = nullptr; return b.fail("out of device memory"); }
-		b.ds->allocs.push_back(b.node_mem);
+		if (!b.node_alloc()) return b.fail("out of device memory");
 		if (hipMemsetAsync(consts, 0, sizeof(DevSceneConsts), bs) != hipSuccess || hipMemsetAsync(b.d_depth_word, 0, 4, bs) != hipSuccess) return b.fail("memset");
 	}
 	if (b.tiles_done) b.stage("collapse");
@@ -2236,7 +2234,8 @@ bool collapse_levels(Build &b)
 	if (!run_collapse(b, in_place ? (DevNode *)b.node_mem : b.d_nodes_tmp, in_place ? (uint32_t)b.node_cap : b.n, b.n)) return b.fail("collapse");
 	if (in_place && b.h_state.total_nodes > b.node_cap) {
 		// the estimate was too small: once more, into the workspace; then an exact allocation
-		b.ds->allocs.pop_back(); (void)hipFree(b.node_mem); b.node_mem = nullptr;      // it was the last one pushed
+		b.ds->mem.release(b.node_mem);
+		b.node_mem = nullptr;
 		in_place = false;
 		if (!run_collapse(b, b.d_nodes_tmp, b.n, b.n)) return b.fail("collapse");
 	}
@@ -2245,8 +2244,7 @@ bool collapse_levels(Build &b)
 	b.stage("collapse");
 	if (!b.node_mem) {
 		b.node_cap = b.total_nodes ? b.total_nodes : 1;
-		if (hipMalloc(&b.node_mem, b.node_cap * (sizeof(DevNode) + sizeof(DevNodeQ))) != hipSuccess) { b.node_mem = nullptr; return b.fail("out of device memory"); }
-		b.ds->allocs.push_back(b.node_mem);
+		if (!b.node_alloc()) return b.fail("out of device memory");
 	}
 	DevNode *d_nodes_ = (DevNode *)b.node_mem;
 	b.ds->view.nodes = d_nodes_;
@@ -2264,8 +2262,6 @@ bool collapse_levels(Build &b)
 bool finish(Build &b)
 {
 	rtk_dev_scene *ds = b.ds;
-	ds->total_bytes += b.node_cap * (sizeof(DevNode) + sizeof(DevNodeQ));
-	ds->node_cap = b.node_cap;
 	if (hipStreamSynchronize(b.bs) != hipSuccess || (b.side_busy && hipStreamSynchronize(b.ws->side) != hipSuccess)) return b.fail("sync");
 	if (!b.tiles_done) {
 		b.equal_codes = b.results->equal_codes;
@@ -2359,21 +2355,18 @@ int rtk_scene_side_arrays(const rtk_dev_scene *ds_c, hipStream_t stream)
 	if (ds->side_ready) return RTK_AMD_OK;
 	const size_t n = ds->view.num_tris, np = ds->view.num_prims;
 	const size_t o_pslot = rtk_padded(3 * n * 4), o_smesh = o_pslot + rtk_padded(np * 4), o_stri = o_smesh + rtk_padded(n * 4), total = o_stri + rtk_padded(n * 4);
-	void *mem = nullptr;
-	RTK_HIP_CHECK(hipMalloc(&mem, total), RTK_AMD_ERR_OOM);
-	char *base = (char *)mem;
+	char *base = (char *)ds->mem.own(total, total);
+	if (!base) { rtk_set_error("rtk_scene_side_arrays: %s", hipGetErrorString(hipGetLastError())); return RTK_AMD_ERR_OOM; }
 	uint32_t *vertex_index = (uint32_t *)base, *prim_slot = (uint32_t *)(base + o_pslot), *slot_mesh = (uint32_t *)(base + o_smesh), *slot_tri = (uint32_t *)(base + o_stri);
 	if (n) {
 		hipLaunchKernelGGL(k_side_arrays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ds->view.tris, (uint32_t)n, ds->d_mesh_base, ds->d_vidx_in,
 			vertex_index, prim_slot, slot_mesh, slot_tri);
 		if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
 			rtk_set_error("rtk_scene_side_arrays: %s", hipGetErrorString(hipGetLastError()));
-			(void)hipFree(mem);
+			ds->mem.release(base);
 			return RTK_AMD_ERR_HIP;
 		}
 	}
-	ds->allocs.push_back(mem);
-	ds->total_bytes += total;
 	ds->view.vertex_index = vertex_index;
 	ds->view.prim_slot = prim_slot;
 	ds->view.slot_mesh = slot_mesh;

@@ -63,13 +63,23 @@ extern "C" rtk_dev_scene *rtk_dev_scene_upload_buffer(const void *blob, size_t b
 	return rtk_dev_scene_from_host_bvh(h);
 }
 
-void rtk_export_forget(const rtk_dev_scene *ds);   // rtk_export.hip
+void rtk_scene_forget_derived(rtk_dev_scene *ds, unsigned what)
+{
+	rtk_export_forget(ds);
+	if (what & RTK_FORGET_BOXES) ds->quality.refitted = true;
+	if (what & RTK_FORGET_TREE) {
+		ds->refit.reset(ds->mem);
+		ds->partial.reset(ds->mem);
+		ds->quality.baseline_known = false;
+		ds->quality.sah_cost_at_build = 0.0;
+	}
+}
 
 extern "C" void rtk_dev_scene_free(rtk_dev_scene *ds)
 {
 	if (!ds) return;
-	rtk_export_forget(ds);
-	for (void *p : ds->allocs) (void)hipFree(p);
+	rtk_scene_forget_derived(ds, RTK_FORGET_BOXES | RTK_FORGET_TREE);
+	ds->mem.release_all();
 	for (LaunchScratch *s : ds->scratch) rtk_scratch_free(s);
 	delete ds;
 }
@@ -82,7 +92,7 @@ extern "C" int rtk_dev_scene_get_info(const rtk_dev_scene *ds, rtk_dev_scene_inf
 	info->num_nodes = ds->view.num_nodes;
 	info->node_bytes = (uint64_t)ds->view.num_nodes * sizeof(DevNode);
 	info->triangle_bytes = (uint64_t)ds->view.num_tris * sizeof(DevTri);
-	info->total_device_bytes = ds->total_bytes;
+	info->total_device_bytes = ds->mem.counted();
 	info->max_depth = ds->max_depth;
 	info->stack_entries = ds->stack_entries;
 	info->build_ms = ds->build_ms;

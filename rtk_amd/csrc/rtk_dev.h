@@ -16,6 +16,7 @@
 
 #include "rtk.h"
 #include "rtk_amd.h"
+#include "rtk_scene_mem.h"
 
 #define RTK_MAX_DEVICES 64       // per-device tables (workspaces, cached properties)
 #define RTK_REF_NONE 0xffffffffu  // empty child slot / "no node"
@@ -120,7 +121,7 @@ struct LaunchScratch {
 
 // What a refit needs besides the scene (rtk_refit.hip): the node numbers grouped by HEIGHT (0: every child is a leaf or
 // empty; else 1 + the largest height among the inner children), so that one launch per height finds its children's boxes
-// written by an earlier launch. The device arrays are owned through rtk_dev_scene::allocs.
+// written by an earlier launch. The device arrays are entries of rtk_dev_scene::mem.
 struct RefitSchedule {
 	bool ready = false;
 	uint32_t *d_order = nullptr;               // [num_nodes] node numbers, by height, by number inside a height
@@ -129,12 +130,12 @@ struct RefitSchedule {
 	void *d_meshes = nullptr;                  // [num_meshes] where each mesh's positions are read from (filled per refit)
 	bool max_vertex_ready = false;
 	std::vector<uint32_t> max_vertex;          // [num_meshes] largest vertex index the mesh's triangles use (made when a mesh first arrives in host memory)
-	size_t bytes = 0;                          // what d_order and d_level_start added to total_bytes (rtk_dev_scene_split_leaves drops them)
+	void reset(SceneMem &mem);                 // gives the device arrays back (rtk_refit.hip); max_vertex holds for any tree over the same triangles and stays
 };
 
 // What a refit of SOME meshes needs on top of the schedule (rtk_dev_scene_refit_meshes): who is above a node, which node holds
-// a slot's leaf, every mesh's slots, and the memory of the per-call dirty set. Made by the first such call of a scene, owned
-// through rtk_dev_scene::allocs; 12 B per node and 8 B per triangle.
+// a slot's leaf, every mesh's slots, and the memory of the per-call dirty set. Made by the first such call of a scene, one
+// entry of rtk_dev_scene::mem; 12 B per node and 8 B per triangle.
 #define RTK_DIRTY_BLOCK 1024u                  // entries of d_order one workgroup of the compaction counts and scatters
 struct RefitPartial {
 	bool ready = false;
@@ -147,17 +148,20 @@ struct RefitPartial {
 	uint32_t *d_list_start = nullptr;          // [heights + 1] where each height begins in d_list
 	void *d_ranges = nullptr;                  // [num_meshes + 1] runs of listed meshes in d_mesh_slots (filled per call)
 	uint32_t epoch = 0;                        // of the last call (0: none yet; d_dirty starts cleared)
-	size_t bytes = 0;                          // what the tables added to total_bytes
+	void reset(SceneMem &mem);                 // gives the tables back (rtk_refit.hip)
 };
 
 // What rtk_dev_scene_quality keeps per scene (rtk_quality.hip): its partial records and result slot on the device, made by the
-// first measurement and owned through rtk_dev_scene::allocs, and the cost the scene had before any refit.
+// first measurement and an entry of rtk_dev_scene::mem, and the cost the scene had before any refit.
 struct QualityState {
-	void *d_mem = nullptr;
+	void *d_mem = nullptr;                     // QUALITY_BLOCKS records and one result: the size does not follow the tree, so RTK_FORGET_TREE keeps it
 	bool refitted = false;                     // a refit of the scene has succeeded (set by the refit, read by the measurement)
 	bool baseline_known = false;               // a measurement was made before any refit ...
 	double sah_cost_at_build = 0.0;            // ... and gave this cost
 };
+
+static inline void *rtk_dev_malloc(size_t bytes) { void *p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; }
+static inline void rtk_dev_free(void *p) { (void)hipFree(p); }
 
 struct rtk_dev_scene {
 	int device = 0;
@@ -168,15 +172,13 @@ struct rtk_dev_scene {
 	uint32_t stack_entries = 0;
 	uint32_t first_top = 0;                // device build, tile collapse: nodes [1, first_top) are the tiles', 0 and [first_top, n) the ones above them (0: one run)
 	uint32_t first_split = 0;              // rtk_dev_scene_split_leaves: nodes [first_split, n) were appended by a split, each after its parent (0: none)
-	uint64_t node_cap = 0;                 // nodes the node allocation holds where exact and compressed nodes share one (a device build, a split; 0: an upload's two arrays of num_nodes)
-	uint64_t total_bytes = 0;
 	double build_ms = 0.0;
 	double big_leaf_fraction = 0.0;        // leaves of more than three triangles (uploads; device builds make ~none): the assembly packet kernel hands those tiles back
 	DevSceneConsts consts_readback = {};   // filled by the stream that ran k_quantize; read by rtk_quantize_finish after its synchronisation
 	float bound_abs = 0.0f;
 	float bound_raw = 0.0f;
-	// owned device allocations
-	std::vector<void *> allocs;
+	// owned device allocations, and what each adds to total_device_bytes (rtk_scene_mem.h)
+	SceneMem mem{ rtk_dev_malloc, rtk_dev_free };
 	// per-stream launch scratch, created on first use; the mutex covers the list and the enqueue of a launch
 	std::mutex scratch_mutex;
 	std::vector<LaunchScratch *> scratch;
@@ -184,6 +186,8 @@ struct rtk_dev_scene {
 	// Device-built scenes make the four side arrays of the view (vertex_index, prim_slot, slot_mesh, slot_tri: what the expansion of
 	// hit records, the validator and the exporter read -- never a traversal) on first use, not in every build: 52 of the 100
 	// bytes per triangle the build's emit kernel wrote, one of them scattered (rtk_scene_side_arrays, rtk_build.hip).
+	// RTK_FORGET_TREE keeps them: they go by slot and primitive, not by node, and the split kernel moves their entries with the
+	// triangle records it reorders (k_split_leaves<true>, under side_mutex).
 	std::mutex side_mutex;
 	bool side_ready = true;                    // (uploads arrive with the arrays)
 	const uint32_t *d_vidx_in = nullptr;       // [3 * prim + k] original vertex indices in input order; NULL: every mesh has implicit indices
@@ -202,6 +206,11 @@ struct rtk_dev_scene {
 };
 // makes the side arrays if they are not there yet (synchronises `stream` the one time it has to work)
 int rtk_scene_side_arrays(const rtk_dev_scene *ds, hipStream_t stream);
+// What was derived from the scene and no longer holds is dropped here, and only here (rtk_capi.hip); whoever needs a table
+// again makes it again. A new derived table is added to this function and nowhere else.
+#define RTK_FORGET_BOXES 1u       // boxes moved, the topology stayed (a refit): the export plan; a cost measured from now on is not the build's
+#define RTK_FORGET_TREE 2u        // nodes or slots were renumbered (a split): the refit schedule, the partial refit's tables, the export plan, the cost at build
+void rtk_scene_forget_derived(rtk_dev_scene *ds, unsigned what);
 
 // -- error plumbing (rtk_capi.hip) --
 void rtk_set_error(const char *fmt, ...);
@@ -213,6 +222,30 @@ void rtk_set_error(const char *fmt, ...);
 			return ret;                                                                  \
 		}                                                                                \
 	} while (0)
+
+// A pass over a scene that is not a trace (refit, split, measurement) fails like this: OOM is told apart, the rest is HIP's.
+#define RTK_PASS_CHECK(who, expr)                                                                    \
+	do {                                                                                             \
+		hipError_t e_ = (expr);                                                                      \
+		if (e_ != hipSuccess) {                                                                      \
+			rtk_set_error(who ": %s failed: %s (line %d)", #expr, hipGetErrorString(e_), __LINE__);  \
+			return e_ == hipErrorOutOfMemory ? RTK_AMD_ERR_OOM : RTK_AMD_ERR_HIP;                    \
+		}                                                                                            \
+	} while (0)
+// ... and runs with the scene's device current: switched to here, switched back when the scope ends.
+struct SceneDeviceScope {
+	int before = 0, device;
+	hipError_t err;
+	explicit SceneDeviceScope(const rtk_dev_scene *ds) : device(ds->device)
+	{
+		err = hipGetDevice(&before);
+		if (err == hipSuccess && before != device) err = hipSetDevice(device);
+		if (err != hipSuccess) { rtk_set_error("scene on device %d: %s", device, hipGetErrorString(err)); before = device; }
+	}
+	SceneDeviceScope(const SceneDeviceScope &) = delete;
+	~SceneDeviceScope() { if (before != device) (void)hipSetDevice(before); }
+	bool ok() const { return err == hipSuccess; }      // false: rtk_set_error has been called, nothing was switched
+};
 
 // -- upload (rtk_upload.hip) --
 struct HostBvh {

@@ -149,22 +149,10 @@ int make_buffers(rtk_dev_scene *ds)
 {
 	if (ds->quality.d_mem) return RTK_AMD_OK;
 	const size_t bytes = QUALITY_BLOCKS * sizeof(QualityPartial) + sizeof(QualityResult);
-	void *mem = nullptr;
-	if (hipMalloc(&mem, bytes) != hipSuccess) { (void)hipGetLastError(); rtk_set_error("rtk_dev_scene_quality: out of device memory"); return RTK_AMD_ERR_OOM; }
-	ds->allocs.push_back(mem);
-	ds->total_bytes += bytes;
-	ds->quality.d_mem = mem;
+	ds->quality.d_mem = ds->mem.own(bytes, bytes);
+	if (!ds->quality.d_mem) { (void)hipGetLastError(); rtk_set_error("rtk_dev_scene_quality: out of device memory"); return RTK_AMD_ERR_OOM; }
 	return RTK_AMD_OK;
 }
-
-#define QUALITY_CHECK(expr)                                                                                     \
-	do {                                                                                                        \
-		hipError_t e_ = (expr);                                                                                 \
-		if (e_ != hipSuccess) {                                                                                 \
-			rtk_set_error("rtk_dev_scene_quality: %s failed: %s (line %d)", #expr, hipGetErrorString(e_), __LINE__); \
-			return RTK_AMD_ERR_HIP;                                                                             \
-		}                                                                                                       \
-	} while (0)
 
 // the scene's device is current
 int measure_on_device(rtk_dev_scene *ds, hipStream_t stream, QualityResult *res)
@@ -176,9 +164,9 @@ int measure_on_device(rtk_dev_scene *ds, hipStream_t stream, QualityResult *res)
 	QualityResult *d_result = (QualityResult *)(partials + QUALITY_BLOCKS);
 	hipLaunchKernelGGL(k_quality_partials, dim3(QUALITY_BLOCKS), dim3(QUALITY_THREADS), 0, stream, v.nodes, v.num_nodes, v.tris, v.num_tris, partials);
 	hipLaunchKernelGGL(k_quality_finish, dim3(1), dim3(QUALITY_FINISH_THREADS), 0, stream, partials, v.nodes, v.num_nodes, d_result);
-	QUALITY_CHECK(hipGetLastError());
-	QUALITY_CHECK(hipMemcpyAsync(res, d_result, sizeof(QualityResult), hipMemcpyDeviceToHost, stream));
-	QUALITY_CHECK(hipStreamSynchronize(stream));
+	RTK_PASS_CHECK("rtk_dev_scene_quality", hipGetLastError());
+	RTK_PASS_CHECK("rtk_dev_scene_quality", hipMemcpyAsync(res, d_result, sizeof(QualityResult), hipMemcpyDeviceToHost, stream));
+	RTK_PASS_CHECK("rtk_dev_scene_quality", hipStreamSynchronize(stream));
 	return RTK_AMD_OK;
 }
 
@@ -200,13 +188,10 @@ extern "C" int rtk_dev_scene_quality(const rtk_dev_scene *scene, rtk_dev_scene_q
 	out->struct_size = struct_size;
 	QualityResult res = {};
 	if (ds->view.num_tris != 0u && ds->view.num_nodes != 0u) {
-		int before = 0;
-		RTK_HIP_CHECK(hipGetDevice(&before), RTK_AMD_ERR_NO_DEVICE);
-		if (before != ds->device) RTK_HIP_CHECK(hipSetDevice(ds->device), RTK_AMD_ERR_NO_DEVICE);
+		SceneDeviceScope scope(ds);
+		if (!scope.ok()) return RTK_AMD_ERR_NO_DEVICE;
 		const int rc = measure_on_device(ds, (hipStream_t)stream, &res);
-		if (rc != RTK_AMD_OK) (void)hipStreamSynchronize((hipStream_t)stream);
-		if (before != ds->device) (void)hipSetDevice(before);
-		if (rc != RTK_AMD_OK) return rc;
+		if (rc != RTK_AMD_OK) { (void)hipStreamSynchronize((hipStream_t)stream); return rc; }
 	}
 	out->nonfinite_boxes = res.sum.count[2] > 0xffffffffull ? 0xffffffffu : (uint32_t)res.sum.count[2];
 	out->inner_children = res.sum.count[0];

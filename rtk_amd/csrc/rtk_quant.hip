@@ -59,9 +59,8 @@ __global__ void __launch_bounds__(256) k_quantize_list(DevNode *nodes, uint32_t 
 int rtk_scene_consts(rtk_dev_scene *ds, hipStream_t stream)
 {
 	if (!ds->view.consts) {
-		void *c = nullptr;
-		RTK_HIP_CHECK(hipMalloc(&c, sizeof(DevSceneConsts)), RTK_AMD_ERR_OOM);
-		ds->allocs.push_back(c);
+		void *c = ds->mem.own(sizeof(DevSceneConsts), 0);
+		if (!c) { rtk_set_error("scene constants: %s", hipGetErrorString(hipGetLastError())); return RTK_AMD_ERR_OOM; }
 		ds->view.consts = (const DevSceneConsts *)c;
 	}
 	RTK_HIP_CHECK(hipMemsetAsync(const_cast<DevSceneConsts *>(ds->view.consts), 0, sizeof(DevSceneConsts), stream), RTK_AMD_ERR_HIP);   // (bound_abs 0 = no nodes; kernels read it as max(bound, 1))
@@ -75,9 +74,8 @@ int rtk_quantize_nodes(rtk_dev_scene *ds, hipStream_t stream, const DevNode *src
 	if (!keep_consts || !ds->view.consts) { const int rc = rtk_scene_consts(ds, stream); if (rc != RTK_AMD_OK) return rc; }
 	DevSceneConsts *consts = const_cast<DevSceneConsts *>(ds->view.consts);
 	if (!p) {
-		RTK_HIP_CHECK(hipMalloc(&p, (size_t)(ds->view.num_nodes ? ds->view.num_nodes : 1) * sizeof(DevNodeQ)), RTK_AMD_ERR_OOM);
-		ds->allocs.push_back(p);
-		ds->total_bytes += (size_t)ds->view.num_nodes * sizeof(DevNodeQ);
+		p = ds->mem.own((size_t)(ds->view.num_nodes ? ds->view.num_nodes : 1) * sizeof(DevNodeQ), (size_t)ds->view.num_nodes * sizeof(DevNodeQ));
+		if (!p) { rtk_set_error("compressed nodes: %s", hipGetErrorString(hipGetLastError())); return RTK_AMD_ERR_OOM; }
 	}
 	// src: the nodes still sit in a workspace; ds->view.nodes (allocated, not yet filled) receives them in the same pass
 	if (n) hipLaunchKernelGGL(k_quantize, dim3((n + 255u) / 256u), dim3(256), 0, stream, const_cast<DevNode *>(src ? src : ds->view.nodes), n, (DevNodeQ *)p,

@@ -402,15 +402,6 @@ __global__ void __launch_bounds__(REFIT_SMALL_THREADS) k_refit_small(DevNode *no
 
 // ---------------------------------------------------------------------------------- host
 
-#define REFIT_CHECK(expr)                                                                                    \
-	do {                                                                                                     \
-		hipError_t e_ = (expr);                                                                              \
-		if (e_ != hipSuccess) {                                                                              \
-			rtk_set_error("rtk_dev_scene_refit: %s failed: %s (line %d)", #expr, hipGetErrorString(e_), __LINE__); \
-			return RTK_AMD_ERR_HIP;                                                                          \
-		}                                                                                                    \
-	} while (0)
-
 // temporaries of the schedule: heights, the changed word, two key arrays, the sort's scratch, level starts
 struct ScheduleTmp { size_t o_changed, o_ka, o_kb, o_sort, o_ls, bytes; };
 ScheduleTmp schedule_tmp(uint32_t n)
@@ -494,9 +485,8 @@ int make_schedule(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
 		rs.d_meshes = nullptr;
 		return rc;
 	}
-	ds->allocs.push_back(d_order); ds->allocs.push_back(d_small);
-	rs.bytes = (size_t)n * 4 + level_start.size() * 4 + num_meshes * sizeof(RefitMesh);
-	ds->total_bytes += rs.bytes;
+	ds->mem.adopt(d_order, (size_t)n * 4);
+	ds->mem.adopt(d_small, level_start.size() * 4 + num_meshes * sizeof(RefitMesh));
 	rs.d_order = (uint32_t *)d_order;
 	rs.d_level_start = (uint32_t *)d_small;
 	rs.level_start.swap(level_start);
@@ -576,9 +566,7 @@ int make_partial_tables(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
 		(void)hipFree(mem);
 		return RTK_AMD_ERR_HIP;
 	}
-	ds->allocs.push_back(mem);
-	rp.bytes = (size_t)n * 12 + (size_t)nt * 8 + ((size_t)nb + 1) * 4 + (heights + 1) * 4 + (num_meshes + 1) * sizeof(RefitRange);
-	ds->total_bytes += rp.bytes;
+	ds->mem.adopt(mem, (size_t)n * 12 + (size_t)nt * 8 + ((size_t)nb + 1) * 4 + (heights + 1) * 4 + (num_meshes + 1) * sizeof(RefitRange));
 	rp.d_parent = d_parent; rp.d_slot_node = d_slot_node; rp.d_mesh_slots = d_mesh_slots;
 	rp.d_dirty = (uint32_t *)(base + o_dirty); rp.d_list = (uint32_t *)(base + o_list); rp.d_block = (uint32_t *)(base + o_block);
 	rp.d_list_start = (uint32_t *)(base + o_list_start); rp.d_ranges = base + o_ranges;
@@ -646,14 +634,14 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 		size_t off = 0;
 		for (size_t mi = 0; mi < num_meshes; mi++) {
 			if (!upload[mi]) continue;
-			REFIT_CHECK(hipMemcpyAsync(base + off, table[mi].pos, upload[mi], hipMemcpyHostToDevice, stream));
+			RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(base + off, table[mi].pos, upload[mi], hipMemcpyHostToDevice, stream));
 			table[mi].pos = base + off;
 			off += rtk_padded(upload[mi]);
 		}
 	}
 	// a mesh in device memory was written by the caller's own work, possibly still in flight on the NULL stream (as in a build)
-	if (any_device && stream != nullptr) REFIT_CHECK(hipStreamSynchronize(nullptr));
-	if (num_meshes) REFIT_CHECK(hipMemcpyAsync(rs.d_meshes, table.data(), num_meshes * sizeof(RefitMesh), hipMemcpyHostToDevice, stream));
+	if (any_device && stream != nullptr) RTK_PASS_CHECK("rtk_dev_scene_refit", hipStreamSynchronize(nullptr));
+	if (num_meshes) RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(rs.d_meshes, table.data(), num_meshes * sizeof(RefitMesh), hipMemcpyHostToDevice, stream));
 
 	// Until this call has succeeded nobody may take the boxes it leaves alone for exact unions.
 	const bool were_exact = ds->boxes_exact;
@@ -676,9 +664,9 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 			threads += ds->mesh_base[mi + 1] - ds->mesh_base[mi];
 			run_end = ds->mesh_base[mi + 1];
 		}
-		REFIT_CHECK(hipMemcpyAsync(rp.d_ranges, ranges.data(), ranges.size() * sizeof(RefitRange), hipMemcpyHostToDevice, stream));
+		RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(rp.d_ranges, ranges.data(), ranges.size() * sizeof(RefitRange), hipMemcpyHostToDevice, stream));
 		if (++rp.epoch == 0u) {                                  // (every 2^32 calls the flags start over)
-			REFIT_CHECK(hipMemsetAsync(rp.d_dirty, 0, (size_t)v.num_nodes * 4, stream));
+			RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemsetAsync(rp.d_dirty, 0, (size_t)v.num_nodes * 4, stream));
 			rp.epoch = 1u;
 		}
 		const uint32_t total = (uint32_t)threads;
@@ -696,13 +684,13 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 			else hipLaunchKernelGGL((k_refit_tris_listed<0, false>), grid, block, 0, stream, LISTED_ARGS);
 		}
 #undef LISTED_ARGS
-		REFIT_CHECK(hipGetLastError());
+		RTK_PASS_CHECK("rtk_dev_scene_refit", hipGetLastError());
 	} else if (v.num_tris) {
 		const dim3 grid((v.num_tris + 255u) / 256u), block(256);
 		if (any_f64 && any_f32) hipLaunchKernelGGL((k_refit_tris<2>), grid, block, 0, stream, tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, (uint32_t)num_meshes);
 		else if (any_f64) hipLaunchKernelGGL((k_refit_tris<1>), grid, block, 0, stream, tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, (uint32_t)num_meshes);
 		else hipLaunchKernelGGL((k_refit_tris<0>), grid, block, 0, stream, tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, (uint32_t)num_meshes);
-		REFIT_CHECK(hipGetLastError());
+		RTK_PASS_CHECK("rtk_dev_scene_refit", hipGetLastError());
 	}
 
 	const uint32_t heights = (uint32_t)rs.level_start.size() - 1u;
@@ -730,15 +718,15 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 				h = h1;
 			}
 		}
-		REFIT_CHECK(hipGetLastError());
-		REFIT_CHECK(hipMemcpyAsync(&ds->partial_readback, rp.d_block + nb, 4, hipMemcpyDeviceToHost, stream));
+		RTK_PASS_CHECK("rtk_dev_scene_refit", hipGetLastError());
+		RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(&ds->partial_readback, rp.d_block + nb, 4, hipMemcpyDeviceToHost, stream));
 		// ---- compressed nodes and order words of the dirty nodes, the constants from the root (dirty whenever anything moved).
 		// The misfit count is one over ALL nodes: the list form is the whole answer only if the others have none (the scene is on
 		// its compressed nodes now) and none of the dirty ones has one either; else the full pass below.
 		if (v.qnodes && ds->qnodes_mem) {
 			rc = rtk_quantize_node_list(ds, stream, rp.d_list, rp.d_block + nb);
 			if (rc != RTK_AMD_OK) return rc;
-			REFIT_CHECK(hipStreamSynchronize(stream));
+			RTK_PASS_CHECK("rtk_dev_scene_refit", hipStreamSynchronize(stream));
 			full_finish = ds->consts_readback.qnode_misfits != 0u;
 		}
 	} else {
@@ -756,7 +744,7 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 				h = h1;
 			}
 		}
-		REFIT_CHECK(hipGetLastError());
+		RTK_PASS_CHECK("rtk_dev_scene_refit", hipGetLastError());
 	}
 
 	if (full_finish) {
@@ -764,16 +752,15 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 		// lies inside the root's now, so no bound is passed in
 		rc = rtk_quantize_nodes(ds, stream, nullptr, const_cast<DevNodeQ *>(ds->qnodes_mem), 0.0f, 0xffffffffu, false, true);
 		if (rc != RTK_AMD_OK) return rc;
-		REFIT_CHECK(hipStreamSynchronize(stream));
+		RTK_PASS_CHECK("rtk_dev_scene_refit", hipStreamSynchronize(stream));
 	}
 	{
 		// (the trace path reads these host fields under the same mutex when it enqueues a launch)
 		std::lock_guard<std::mutex> lock(ds->scratch_mutex);
 		rtk_quantize_finish(ds);
 	}
-	rtk_export_forget(ds);
+	rtk_scene_forget_derived(ds, RTK_FORGET_BOXES);
 	ds->boxes_exact = true;
-	ds->quality.refitted = true;               // (rtk_dev_scene_quality: a cost measured from now on is no longer the build's)
 	ds->refit_nodes = dirty_set ? ds->partial_readback : v.num_nodes;
 	return RTK_AMD_OK;
 }
@@ -783,15 +770,13 @@ int refit_locked(rtk_dev_scene *ds, const rtk_scene_desc *desc, void *stream, co
 {
 	const auto t_begin = std::chrono::steady_clock::now();
 	std::lock_guard<std::mutex> lock(ds->refit_mutex);
-	int before = 0;
-	RTK_HIP_CHECK(hipGetDevice(&before), RTK_AMD_ERR_NO_DEVICE);
-	if (before != ds->device) RTK_HIP_CHECK(hipSetDevice(ds->device), RTK_AMD_ERR_NO_DEVICE);
+	SceneDeviceScope scope(ds);
+	if (!scope.ok()) return RTK_AMD_ERR_NO_DEVICE;
 	WorkspaceLoan loan;
 	const int rc = refit_on_device(ds, desc, (hipStream_t)stream, loan, listed, listed_tris);
 	// (a failure may leave work enqueued that reads this call's tables or the workspace: it has to be over first)
 	if (rc != RTK_AMD_OK) (void)hipStreamSynchronize((hipStream_t)stream);
 	loan.release();
-	if (before != ds->device) (void)hipSetDevice(before);
 	if (rc == RTK_AMD_OK) ds->refit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
 	return rc;
 }
@@ -829,6 +814,23 @@ int check_desc(const char *who, const rtk_dev_scene *ds, const rtk_scene_desc *d
 }
 
 } // namespace
+
+// (what make_schedule and make_partial_tables made, given back: rtk_scene_forget_derived)
+void RefitSchedule::reset(SceneMem &mem)
+{
+	mem.release(d_order);
+	mem.release(d_level_start);                // (the mesh table lies behind the level starts)
+	ready = false;
+	d_order = d_level_start = nullptr;
+	d_meshes = nullptr;
+	level_start.clear();
+}
+
+void RefitPartial::reset(SceneMem &mem)
+{
+	mem.release(d_parent);                     // (one allocation; the table of parents is its first)
+	*this = RefitPartial();
+}
 
 extern "C" int rtk_dev_scene_refit(rtk_dev_scene *ds, const rtk_scene_desc *desc, void *stream)
 {

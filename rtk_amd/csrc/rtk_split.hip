@@ -308,53 +308,11 @@ __global__ void __launch_bounds__(64 * SPLIT_WAVES) k_split_leaves(SplitArgs a)
 	if (lane == 0u) a.new_nodes[parent >> 2].child[parent & 3u] = base;
 }
 
-#define SPLIT_CHECK(expr)                                                                                          \
-	do {                                                                                                           \
-		hipError_t e_ = (expr);                                                                                    \
-		if (e_ != hipSuccess) {                                                                                    \
-			rtk_set_error("rtk_dev_scene_split_leaves: %s failed: %s (line %d)", #expr, hipGetErrorString(e_), __LINE__); \
-			return e_ == hipErrorOutOfMemory ? RTK_AMD_ERR_OOM : RTK_AMD_ERR_HIP;                                   \
-		}                                                                                                          \
-	} while (0)
-
 // device memory of one call, freed when it returns
 struct Temporaries {
 	void *small = nullptr, *tables = nullptr, *new_nodes = nullptr;
 	~Temporaries() { if (small) (void)hipFree(small); if (tables) (void)hipFree(tables); if (new_nodes) (void)hipFree(new_nodes); }
 };
-
-// an owned allocation of the scene, given back
-bool free_owned(rtk_dev_scene *ds, const void *p)
-{
-	auto it = std::find(ds->allocs.begin(), ds->allocs.end(), const_cast<void *>(p));
-	if (p == nullptr || it == ds->allocs.end()) return false;
-	(void)hipFree(*it);
-	ds->allocs.erase(it);
-	return true;
-}
-
-// what was derived from the old tree: the refit schedule, the tables of the partial refit (both are made again by the next
-// refit that needs them), the cached export plan, the cost the old tree had
-void forget_derived(rtk_dev_scene *ds)
-{
-	RefitSchedule &rs = ds->refit;
-	if (rs.ready) {
-		free_owned(ds, rs.d_order);
-		free_owned(ds, rs.d_level_start);
-		ds->total_bytes -= rs.bytes;
-		rs.ready = false; rs.d_order = nullptr; rs.d_level_start = nullptr; rs.d_meshes = nullptr; rs.bytes = 0;
-		rs.level_start.clear();
-	}
-	RefitPartial &rp = ds->partial;
-	if (rp.ready) {
-		free_owned(ds, rp.d_parent);
-		ds->total_bytes -= rp.bytes;
-		rp = RefitPartial();
-	}
-	rtk_export_forget(ds);
-	ds->quality.baseline_known = false;
-	ds->quality.sah_cost_at_build = 0.0;
-}
 
 // everything behind the argument checks; the scene's device is current, refit_mutex is held
 int split_on_device(rtk_dev_scene *ds, uint32_t limit, hipStream_t stream, rtk_dev_split_info *info)
@@ -364,14 +322,14 @@ int split_on_device(rtk_dev_scene *ds, uint32_t limit, hipStream_t stream, rtk_d
 	if (v.num_tris == 0u || v.num_nodes == 0u) return RTK_AMD_OK;
 	Temporaries tmp;
 	SplitWords h = {};
-	SPLIT_CHECK(hipMalloc(&tmp.small, sizeof(SplitWords)));
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipMalloc(&tmp.small, sizeof(SplitWords)));
 	SplitWords *words = (SplitWords *)tmp.small;
 	const unsigned tri_blocks = (v.num_tris + 255u) / 256u;
-	SPLIT_CHECK(hipMemsetAsync(words, 0, sizeof(SplitWords), stream));
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipMemsetAsync(words, 0, sizeof(SplitWords), stream));
 	hipLaunchKernelGGL(k_split_stats, dim3(tri_blocks), dim3(256), 0, stream, v.tris, v.num_tris, limit, words->before);
-	SPLIT_CHECK(hipGetLastError());
-	SPLIT_CHECK(hipMemcpyAsync(&h, words, sizeof(h), hipMemcpyDeviceToHost, stream));
-	SPLIT_CHECK(hipStreamSynchronize(stream));
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipGetLastError());
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipMemcpyAsync(&h, words, sizeof(h), hipMemcpyDeviceToHost, stream));
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipStreamSynchronize(stream));
 	info->largest_leaf_before = info->largest_leaf_after = h.before[W_LARGEST];
 	const uint32_t num_big = h.before[W_OVER_LIMIT];
 	if (num_big == 0u) return RTK_AMD_OK;      // nothing to split: no bit changes, nothing is dropped
@@ -382,16 +340,16 @@ int split_on_device(rtk_dev_scene *ds, uint32_t limit, hipStream_t stream, rtk_d
 		o_parent = o_first + rtk_padded((size_t)num_big * 4), o_count = o_parent + rtk_padded((size_t)num_big * 4),
 		o_big_totals = o_count + rtk_padded((size_t)num_big * 4), o_level = o_big_totals + rtk_padded(((size_t)big_scan + 1) * 4),
 		tables_bytes = o_level + rtk_padded((size_t)v.num_nodes * 4);
-	SPLIT_CHECK(hipMalloc(&tmp.tables, tables_bytes));
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipMalloc(&tmp.tables, tables_bytes));
 	char *tb = (char *)tmp.tables;
 	uint32_t *leaf_number = (uint32_t *)tb, *tri_totals = (uint32_t *)(tb + o_tri_totals), *leaf_first = (uint32_t *)(tb + o_first),
 		*leaf_parent = (uint32_t *)(tb + o_parent), *node_count = (uint32_t *)(tb + o_count), *big_totals = (uint32_t *)(tb + o_big_totals),
 		*level = (uint32_t *)(tb + o_level);
 	hipLaunchKernelGGL(k_split_mark, dim3(tri_blocks), dim3(256), 0, stream, v.tris, v.num_tris, limit, leaf_number);
 	scan_exclusive(leaf_number, v.num_tris, tri_totals, &words->big_leaves, stream);
-	SPLIT_CHECK(hipMemsetAsync(tb + o_first, 0xff, o_count - o_first, stream));       // (RTK_REF_NONE: a leaf nobody names)
-	SPLIT_CHECK(hipMemsetAsync(tb + o_count, 0, o_big_totals - o_count, stream));
-	SPLIT_CHECK(hipMemsetAsync(level, 0, (size_t)v.num_nodes * 4, stream));
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipMemsetAsync(tb + o_first, 0xff, o_count - o_first, stream));       // (RTK_REF_NONE: a leaf nobody names)
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipMemsetAsync(tb + o_count, 0, o_big_totals - o_count, stream));
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipMemsetAsync(level, 0, (size_t)v.num_nodes * 4, stream));
 	hipLaunchKernelGGL(k_split_list, dim3((unsigned)(((size_t)v.num_nodes * 4 + 255) / 256)), dim3(256), 0, stream, v.nodes, v.num_nodes, v.tris, v.num_tris, limit,
 		leaf_number, num_big, leaf_first, leaf_parent);
 	for (uint32_t k = 0; k < ds->max_depth; k++) hipLaunchKernelGGL(k_split_depth, dim3((v.num_nodes + 255u) / 256u), dim3(256), 0, stream, v.nodes, v.num_nodes, level);
@@ -402,9 +360,9 @@ int split_on_device(rtk_dev_scene *ds, uint32_t limit, hipStream_t stream, rtk_d
 	const unsigned leaf_blocks = (num_big + SPLIT_WAVES - 1u) / SPLIT_WAVES;
 	hipLaunchKernelGGL((k_split_leaves<false>), dim3(leaf_blocks), dim3(64 * SPLIT_WAVES), 0, stream, a);
 	scan_exclusive(node_count, num_big, big_totals, &words->nodes_added, stream);
-	SPLIT_CHECK(hipGetLastError());
-	SPLIT_CHECK(hipMemcpyAsync(&h, words, sizeof(h), hipMemcpyDeviceToHost, stream));
-	SPLIT_CHECK(hipStreamSynchronize(stream));
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipGetLastError());
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipMemcpyAsync(&h, words, sizeof(h), hipMemcpyDeviceToHost, stream));
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipStreamSynchronize(stream));
 	if (h.big_leaves != num_big) { rtk_set_error("rtk_dev_scene_split_leaves: internal error: %u big leaves counted, %u numbered", num_big, h.big_leaves); return RTK_AMD_ERR_HIP; }
 	const uint64_t new_total = (uint64_t)v.num_nodes + h.nodes_added;
 	if (new_total >= 0x7ffffff0ull) { rtk_set_error("rtk_dev_scene_split_leaves: %llu nodes are too many for 31-bit references", (unsigned long long)new_total); return RTK_AMD_ERR_UNSUPPORTED; }
@@ -421,7 +379,7 @@ int split_on_device(rtk_dev_scene *ds, uint32_t limit, hipStream_t stream, rtk_d
 
 	// ---- from here on the scene is written
 	std::lock_guard<std::mutex> side_lock(ds->side_mutex);          // (nobody makes the side arrays while they are permuted)
-	SPLIT_CHECK(hipMemcpyAsync(new_nodes, v.nodes, (size_t)v.num_nodes * sizeof(DevNode), hipMemcpyDeviceToDevice, stream));
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipMemcpyAsync(new_nodes, v.nodes, (size_t)v.num_nodes * sizeof(DevNode), hipMemcpyDeviceToDevice, stream));
 	a.new_nodes = new_nodes;
 	a.new_nodes_total = (uint32_t)new_total;
 	if (ds->side_ready && v.vertex_index && v.prim_slot && v.slot_mesh && v.slot_tri) {
@@ -430,9 +388,9 @@ int split_on_device(rtk_dev_scene *ds, uint32_t limit, hipStream_t stream, rtk_d
 	}
 	hipLaunchKernelGGL((k_split_leaves<true>), dim3(leaf_blocks), dim3(64 * SPLIT_WAVES), 0, stream, a);
 	hipLaunchKernelGGL(k_split_stats, dim3(tri_blocks), dim3(256), 0, stream, v.tris, v.num_tris, limit, words->after);
-	SPLIT_CHECK(hipGetLastError());
-	SPLIT_CHECK(hipMemcpyAsync(&h, words, sizeof(h), hipMemcpyDeviceToHost, stream));
-	SPLIT_CHECK(hipStreamSynchronize(stream));
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipGetLastError());
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipMemcpyAsync(&h, words, sizeof(h), hipMemcpyDeviceToHost, stream));
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipStreamSynchronize(stream));
 
 	// ---- the scene names the new arrays; compressed nodes, order words and constants over the whole new tree. Boxes of a blob
 	// need not nest: the bound is the one the scene had (over every old node for an upload) widened by the new nodes' planes.
@@ -451,7 +409,7 @@ int split_on_device(rtk_dev_scene *ds, uint32_t limit, hipStream_t stream, rtk_d
 		rc = rtk_quantize_nodes(ds, stream, nullptr, new_qnodes, bound_hint, 0xffffffffu, false, true);
 		if (rc == RTK_AMD_OK && hipStreamSynchronize(stream) != hipSuccess) { rtk_set_error("rtk_dev_scene_split_leaves: %s", hipGetErrorString(hipGetLastError())); rc = RTK_AMD_ERR_HIP; }
 		if (rc == RTK_AMD_OK) rtk_quantize_finish(ds);
-		ds->allocs.push_back(tmp.new_nodes);
+		ds->mem.adopt(tmp.new_nodes, (size_t)new_total * (sizeof(DevNode) + sizeof(DevNodeQ)));
 		tmp.new_nodes = nullptr;
 		const uint32_t depth = h.depth > ds->max_depth ? h.depth : ds->max_depth;
 		ds->max_depth = depth;
@@ -461,14 +419,11 @@ int split_on_device(rtk_dev_scene *ds, uint32_t limit, hipStream_t stream, rtk_d
 		// run: the validator is told where the appended ones begin)
 		if (ds->first_split == 0u) ds->first_split = v.num_nodes;
 	}
-	// the old arrays: an upload owns them one by one, a device build as one allocation (the compressed nodes behind the exact ones)
-	const uint64_t old_cap = ds->node_cap ? ds->node_cap : v.num_nodes;
-	free_owned(ds, old_nodes);
-	if (old_qnodes) free_owned(ds, old_qnodes);
-	ds->total_bytes -= old_cap * sizeof(DevNode) + (old_qnodes ? old_cap * sizeof(DevNodeQ) : 0);
-	ds->total_bytes += new_total * (sizeof(DevNode) + sizeof(DevNodeQ));
-	ds->node_cap = new_total;
-	forget_derived(ds);
+	// the old arrays: an upload owns them one by one, a device build as one allocation (the compressed nodes behind the exact
+	// ones: no entry of their own). What was derived from the old tree goes with them.
+	ds->mem.release(old_nodes);
+	ds->mem.release(old_qnodes);
+	rtk_scene_forget_derived(ds, RTK_FORGET_TREE);
 	if (rc != RTK_AMD_OK) return rc;
 	info->leaves_split = num_big;
 	info->nodes_added = h.nodes_added;
@@ -494,14 +449,11 @@ extern "C" int rtk_dev_scene_split_leaves(rtk_dev_scene *ds, uint32_t max_leaf, 
 	info.struct_size = out ? out->struct_size : (uint32_t)sizeof(info);
 	info.max_leaf = limit;
 	std::lock_guard<std::mutex> lock(ds->refit_mutex);             // never beside a refit or a measurement
-	int before = 0;
-	RTK_HIP_CHECK(hipGetDevice(&before), RTK_AMD_ERR_NO_DEVICE);
-	if (before != ds->device) RTK_HIP_CHECK(hipSetDevice(ds->device), RTK_AMD_ERR_NO_DEVICE);
+	SceneDeviceScope scope(ds);
+	if (!scope.ok()) return RTK_AMD_ERR_NO_DEVICE;
 	const int rc = split_on_device(ds, limit, (hipStream_t)stream, &info);
 	// (a failure may have left work enqueued: it is over before the caller goes on)
-	if (rc != RTK_AMD_OK) (void)hipStreamSynchronize((hipStream_t)stream);
-	if (before != ds->device) (void)hipSetDevice(before);
-	if (rc != RTK_AMD_OK) return rc;
+	if (rc != RTK_AMD_OK) { (void)hipStreamSynchronize((hipStream_t)stream); return rc; }
 	info.split_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
 	if (out) *out = info;
 	return RTK_AMD_OK;

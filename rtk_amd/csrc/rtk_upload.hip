@@ -198,10 +198,8 @@ template <typename T>
 static bool upload_vec(rtk_dev_scene *ds, const std::vector<T> &v, const T **dst, size_t min_elems = 1)
 {
 	const size_t n = v.size() > min_elems ? v.size() : min_elems;
-	void *p = nullptr;
-	if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return false;
-	ds->allocs.push_back(p);
-	ds->total_bytes += n * sizeof(T);
+	void *p = ds->mem.own(n * sizeof(T), n * sizeof(T));
+	if (!p) return false;
 	if (!v.empty() && hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return false;
 	*dst = static_cast<const T *>(p);
 	return true;
