@@ -261,6 +261,48 @@ typedef struct rtk_dev_split_info {
 } rtk_dev_split_info;
 int rtk_dev_scene_split_leaves(rtk_dev_scene *ds, uint32_t max_leaf, rtk_dev_split_info *out /* may be NULL */, void *stream);
 
+/* The last step of the loop for animated scenes: when rtk_dev_scene_quality says the tree has degraded (or for a blob, which
+ * has no description to build from), the device builder builds the tree again over the triangles the scene holds NOW, and the
+ * live handle adopts it.
+ *   - RESULT: the scene becomes what rtk_dev_scene_build returns for a description of the same meshes (same num_meshes, the
+ *     same triangles per mesh in the same order) that holds the positions the scene holds now: nodes, triangle records,
+ *     compressed nodes, order words and constants, num_nodes, max_depth, stack_entries, the slot order. content_hash of
+ *     rtk_dev_scene_validate and rtk_dev_scene_primitive_order equal that fresh build's.
+ *   - HOW: the builder runs over the triangles in primitive-id order (the id breaks ties between equal Morton codes, as the
+ *     triangle's number does in a build), with the knobs, the plan and the narrow-key rule of rtk_dev_scene_build: if more
+ *     than an eighth of the sorted neighbours share a code the build runs once more with 40 bits (rebuild_ms covers both).
+ *     The leaf limit is the builder's own (RTK_AMD_MAX_LEAF).
+ *   - STAYS: the handle, mesh_base, primitive ids, every primitive's rtk_vertex.index triple, the positions bit for bit, the
+ *     per-stream launch scratch (it grows by itself at the next launch, as after a split), rtk_dev_scene_info.build_ms.
+ *   - CHANGES: slots (rtk_dev_scene_primitive_order becomes another permutation), node numbers, num_nodes, node_bytes,
+ *     total_device_bytes, max_depth, stack_entries; the share of big leaves that picks the kernels is the new tree's; no
+ *     node counts as appended by a split any more; every box is an exact union again (what a refit of some meshes relies
+ *     on). A scene that arrived as a blob keeps, from its first rebuild on, its vertex indices by primitive (12 bytes per
+ *     triangle, counted in total_device_bytes).
+ *   - FORGOTTEN, and made again on next use: the refit schedule, the tables of rtk_dev_scene_refit_meshes, the cached export
+ *     plan, the four side arrays (they go by slot). The scene counts as NEVER REFITTED again: the next
+ *     rtk_dev_scene_quality call sets sah_cost_at_build anew, so a host's ratio starts from the new tree.
+ *   - ALL OR NOTHING: the new records and nodes are built in fresh allocations beside the old ones; the host swaps them in
+ *     after the build's last wait and then releases the old ones. RTK_AMD_ERR_OOM and RTK_AMD_ERR_HIP release what was
+ *     allocated and leave every bit of the scene as it was. While the call runs the scene needs its new records (48 bytes per
+ *     triangle) and node block (about 96 bytes per triangle) beside the old ones, plus the build workspace.
+ *   - The call WRITES the scene and MOVES its arrays: no trace, refit, measurement or split of the scene may be in flight on
+ *     another stream or thread. It takes the locks the split takes, in the same order, and is synchronous; work queued
+ *     earlier on `stream` is ordered before it.
+ *   - Fewer than two triangles: success, no bit changes, nothing is launched.
+ *   - RTK_AMD_ERR_BAD_ARG: ds NULL, out->struct_size < sizeof(rtk_dev_rebuild_info); decided before any HIP call.
+ *     RTK_AMD_ERR_UNSUPPORTED: the scene does not hold exactly one triangle record per primitive (an uploaded blob may
+ *     name an id twice or never); decided before the scene is written, which stays as it was.
+ * rtk_mgpu_rebuild does the same on every GPU of the context; rtk_mgpu_scene handles stay valid. */
+typedef struct rtk_dev_rebuild_info {
+	uint32_t struct_size;            /* sizeof(rtk_dev_rebuild_info), set by the caller */
+	uint32_t key_bits;               /* width of the Morton code the final build used */
+	uint64_t nodes_before, nodes_after;
+	uint32_t max_depth_before, max_depth_after;
+	double rebuild_ms;               /* wall time inside the call */
+} rtk_dev_rebuild_info;
+int rtk_dev_scene_rebuild(rtk_dev_scene *ds, rtk_dev_rebuild_info *out /* may be NULL */, void *stream);
+
 /* Structural check of a device scene, run on the device (the loader/validator the reference lacks,
  * SURVEY.md section 5; blob-level checks happen in rtk_dev_scene_upload). Every child box must contain
  * what is below it, every triangle slot must sit in exactly one leaf, every node but the root must be
@@ -389,6 +431,7 @@ int rtk_mgpu_upload(rtk_mgpu *m, const rtk_scene *scene);         /* rtk_dev_sce
 int rtk_mgpu_refit(rtk_mgpu *m, const rtk_scene_desc *desc);      /* rtk_dev_scene_refit on every GPU of the context (handles stay valid) */
 int rtk_mgpu_refit_meshes(rtk_mgpu *m, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids);   /* rtk_dev_scene_refit_meshes on every GPU */
 int rtk_mgpu_split_leaves(rtk_mgpu *m, uint32_t max_leaf);        /* rtk_dev_scene_split_leaves on every GPU of the context (handles stay valid) */
+int rtk_mgpu_rebuild(rtk_mgpu *m);   /* on every GPU of the context; rtk_mgpu_scene handles stay valid */
 /* host rays in, host records out (records[i] belongs to rays[i]) */
 int rtk_mgpu_trace_rays(rtk_mgpu *m, const rtk_ray *rays, size_t n, rtk_hit_record *records, const rtk_trace_opts *opts);
 /* device-resident shards: d_rays[r] / d_records[r] (counts[r] elements) live on GPU r of the context; if d_gathered

@@ -68,6 +68,15 @@ class SplitInfo(C.Structure):
         return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_}
 
 
+class RebuildInfo(C.Structure):
+    """rtk_dev_rebuild_info: what rtk_dev_scene_rebuild did."""
+    _fields_ = [("struct_size", C.c_uint32), ("key_bits", C.c_uint32), ("nodes_before", C.c_uint64), ("nodes_after", C.c_uint64),
+                ("max_depth_before", C.c_uint32), ("max_depth_after", C.c_uint32), ("rebuild_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_}
+
+
 class TraceOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("image_width", C.c_uint32),
                 ("image_height", C.c_uint32), ("refill_min", C.c_uint32), ("blocks_per_cu", C.c_uint32),
@@ -117,7 +126,8 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_mgpu_trace_rays_device_striped", "rtk_mgpu_striped_segment",
                      "rtk_dev_scene_refit", "rtk_dev_scene_last_refit_ms", "rtk_mgpu_refit",
                      "rtk_dev_scene_refit_meshes", "rtk_dev_scene_last_refit_nodes", "rtk_mgpu_refit_meshes",
-                     "rtk_dev_scene_quality", "rtk_dev_scene_split_leaves", "rtk_mgpu_split_leaves"]
+                     "rtk_dev_scene_quality", "rtk_dev_scene_split_leaves", "rtk_mgpu_split_leaves",
+                     "rtk_dev_scene_rebuild", "rtk_mgpu_rebuild"]
 
 _lib = None
 
@@ -198,6 +208,10 @@ def lib():
     L.rtk_dev_scene_split_leaves.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(SplitInfo), C.c_void_p]
     L.rtk_mgpu_split_leaves.restype = C.c_int
     L.rtk_mgpu_split_leaves.argtypes = [C.c_void_p, C.c_uint32]
+    L.rtk_dev_scene_rebuild.restype = C.c_int
+    L.rtk_dev_scene_rebuild.argtypes = [C.c_void_p, C.POINTER(RebuildInfo), C.c_void_p]
+    L.rtk_mgpu_rebuild.restype = C.c_int
+    L.rtk_mgpu_rebuild.argtypes = [C.c_void_p]
     L.rtk_mgpu_refit_meshes.restype = C.c_int
     L.rtk_mgpu_refit_meshes.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_size_t]
     L.rtk_mgpu_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(TraceOpts)]
@@ -364,6 +378,17 @@ class DeviceScene:
         s.struct_size = C.sizeof(SplitInfo)
         _check(lib().rtk_dev_scene_split_leaves(self.handle, int(max_leaf), C.byref(s), _stream_ptr()), "rtk_dev_scene_split_leaves")
         return s.as_dict()
+
+    def rebuild(self):
+        """The device builder's tree over the triangles the scene holds now (rtk_dev_scene_rebuild), in place: what build()
+        of the current positions would return, under the same handle. For a scene whose tree has degraded under refits
+        (quality()["ratio"]) and for an uploaded blob, which has no description to build from. Returns the fields of
+        rtk_dev_rebuild_info as a dict. Synchronous; the scene must not be traced from another stream or thread meanwhile."""
+        _torch()
+        r = RebuildInfo()
+        r.struct_size = C.sizeof(RebuildInfo)
+        _check(lib().rtk_dev_scene_rebuild(self.handle, C.byref(r), _stream_ptr()), "rtk_dev_scene_rebuild")
+        return r.as_dict()
 
     def free(self):
         if self.handle:

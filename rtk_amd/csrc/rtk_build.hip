@@ -206,6 +206,71 @@ __global__ void __launch_bounds__(BOUNDS_BLOCK) k_bounds(const InTri *in_tris, u
 	}
 }
 
+// ---------------------------------------------------------------------------------- 1b staging from a scene (rebuild)
+
+// rtk_dev_scene_rebuild's ingest: the triangles come from the finished records of a scene, not from a description. One thread per
+// slot reads its 48-byte record (a wave reads 3 KB in a row) and writes, under the record's primitive id g -- the number k_morton
+// and the sort know the triangle by, so ties between equal codes break as in a build from a description --, the doubled centroid
+// in k_ingest's arithmetic and the slot the record lies in (k_refit_tile's make_tri gathers old_tris[slot_of[g]]). The bounds
+// of the centroids are taken as k_ingest takes them. vidx_out (a scene that arrived as a blob: its vertex indices exist only
+// by slot): the original vertex indices in primitive order, which the scene owns from then on.
+// slot_of starts out as all ones: with as many slots as primitives an id that is met twice leaves another one unmet, so the
+// words k_stage_check still finds at all ones, plus the ids beyond the range counted here, say whether every primitive has
+// exactly one record.
+#define STAGE_BLOCK 1024
+#define STAGE_BAD_WORD 8          // of the sixteen bounds words: records whose primitive id cannot be staged
+__global__ void __launch_bounds__(STAGE_BLOCK) k_stage_scene(const DevTri *old_tris, uint32_t n, const uint32_t *vertex_index, float *cent, uint32_t *slot_of,
+	uint32_t *vidx_out, uint32_t *bounds)
+{
+	__shared__ float s_mn[3][STAGE_BLOCK / 64], s_mx[3][STAGE_BLOCK / 64];
+	float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
+	uint32_t bad = 0;
+	for (uint32_t s = blockIdx.x * STAGE_BLOCK + threadIdx.x; s < n; s += gridDim.x * STAGE_BLOCK) {
+		const float4 *rec = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(old_tris) + (size_t)s * RTK_TRI_STRIDE);
+		const float4 a = rec[0], b = rec[1], c = rec[2];      // v0 prim | v1 flags | v2 spare
+		const uint32_t g = __float_as_uint(a.w);
+		if (g >= n) { bad++; continue; }
+		const float p[9] = { a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z };
+		slot_of[g] = s;
+		if (vidx_out) { vidx_out[3 * (size_t)g + 0] = vertex_index[3 * (size_t)s + 0]; vidx_out[3 * (size_t)g + 1] = vertex_index[3 * (size_t)s + 1]; vidx_out[3 * (size_t)g + 2] = vertex_index[3 * (size_t)s + 2]; }
+#pragma unroll
+		for (int ax = 0; ax < 3; ax++) {
+			const float lo = fminf(fminf(p[ax], p[3 + ax]), p[6 + ax]);
+			const float hi = fmaxf(fmaxf(p[ax], p[3 + ax]), p[6 + ax]);
+			const float c2 = lo + hi;
+			cent[3 * (size_t)g + ax] = c2;
+			mn[ax] = fminf(mn[ax], c2);
+			mx[ax] = fmaxf(mx[ax], c2);
+		}
+	}
+#pragma unroll
+	for (int a = 0; a < 3; a++) {
+		for (int o = 32; o > 0; o >>= 1) {
+			mn[a] = fminf(mn[a], __shfl_xor(mn[a], o));
+			mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o));
+		}
+		if ((threadIdx.x & 63u) == 0) { s_mn[a][threadIdx.x >> 6] = mn[a]; s_mx[a][threadIdx.x >> 6] = mx[a]; }
+	}
+	for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
+	if ((threadIdx.x & 63u) == 0 && bad) atomicAdd(&bounds[STAGE_BAD_WORD], bad);
+	__syncthreads();
+	if (threadIdx.x < 3) {
+		const int a = threadIdx.x;
+		float lo = s_mn[a][0], hi = s_mx[a][0];
+		for (int w = 1; w < STAGE_BLOCK / 64; w++) { lo = fminf(lo, s_mn[a][w]); hi = fmaxf(hi, s_mx[a][w]); }
+		atomicMin(&bounds[a], f2ord(lo));
+		atomicMax(&bounds[3 + a], f2ord(hi));
+	}
+}
+
+// primitives no record names (see above), added to the count of ids out of range
+__global__ void __launch_bounds__(256) k_stage_check(const uint32_t *slot_of, uint32_t n, uint32_t *bounds)
+{
+	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+	const unsigned long long unmet = __ballot(g < n && slot_of[g] == 0xffffffffu);
+	if ((threadIdx.x & 63u) == 0 && unmet) atomicAdd(&bounds[STAGE_BAD_WORD], (uint32_t)__popcll(unmet));
+}
+
 // ---------------------------------------------------------------------------------- 3 morton
 
 __device__ __forceinline__ unsigned long long spread21(uint32_t v)
@@ -258,18 +323,27 @@ struct EmitSrc {
 	const unsigned long long *words;      // packed sort words, the number in their low 24 bits
 	const unsigned long long *mesh_base;
 	uint32_t num_meshes;
+	const DevTri *old_tris;               // a rebuild: the scene's records as they lie (NULL: a build from a description), and ...
+	const uint32_t *slot_of;              // ... [primitive] -> the slot of its record
 };
 
-// the record of sorted triangle s: its positions gathered from the caller's position buffer (implicit float meshes) or the staged records
+// the record of sorted triangle s: its positions gathered from the caller's position buffer (implicit float meshes), the staged records,
+// or the records of the scene that is being rebuilt
 __device__ __forceinline__ DevTri make_tri(const EmitSrc &e, uint32_t s)
 {
 	const uint32_t g = e.vals ? e.vals[s] : (uint32_t)(e.words[s] & 0xffffffull);     // packed sort words carry the index in their low 24 bits
 	// mesh of global primitive g: last m with mesh_base[m] <= g
 	uint32_t lo = 0, hi = e.num_meshes;
 	while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (e.mesh_base[mid] <= g) lo = mid; else hi = mid; }
-	const MeshSrc ms = e.src[lo];
+	const MeshSrc ms = e.old_tris ? MeshSrc{ nullptr, 0ull } : e.src[lo];
 	DevTri t;
-	if (ms.pos) {
+	if (e.old_tris) {
+		const float4 *rec = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(e.old_tris) + (size_t)e.slot_of[g] * RTK_TRI_STRIDE);
+		const float4 a = rec[0], b = rec[1], c = rec[2];      // v0 prim | v1 flags | v2 spare
+		t.v0[0] = a.x; t.v0[1] = a.y; t.v0[2] = a.z;
+		t.v1[0] = b.x; t.v1[1] = b.y; t.v1[2] = b.z;
+		t.v2[0] = c.x; t.v2[1] = c.y; t.v2[2] = c.z;
+	} else if (ms.pos) {
 		const size_t first = 3u * (size_t)(g - (uint32_t)e.mesh_base[lo]);
 		const float *p0 = reinterpret_cast<const float *>(ms.pos + first * ms.stride);
 		const float *p1 = reinterpret_cast<const float *>(ms.pos + (first + 1u) * ms.stride);
@@ -1744,7 +1818,12 @@ static_assert(REFIT_TILE == RTK_BUILD_REFIT_TILE && COLLAPSE_BLOCK == RTK_BUILD_
 
 // ---- one build: what its stages share ----
 struct Build {
+	// where the triangles come from: a description (rtk_dev_scene_build), or the records of a live scene (rtk_dev_scene_rebuild).
+	// Only plan_meshes and the two ingests look at it; from there on a build knows the number of meshes and mesh_base.
 	const rtk_scene_desc *desc = nullptr;
+	const rtk_dev_scene *from = nullptr;
+	size_t num_meshes = 0;
+	int rc = RTK_AMD_ERR_HIP;         // what a failed build reports where a code is wanted (the rebuild): set by whoever returns false
 	uint32_t n = 0;
 	int device = 0, num_cus = 0;
 	BuildKnobs knobs;
@@ -1789,6 +1868,8 @@ struct Build {
 	const uint32_t *vals = nullptr;
 	DevTri *d_tris = nullptr;
 	EmitSrc emit_src = {};
+	const DevTri *old_tris = nullptr; // a rebuild: what make_tri gathers from (ingest_scene)
+	const uint32_t *slot_of = nullptr;
 	// the collapse
 	void *node_mem = nullptr;         // [DevNode x node_cap | DevNodeQ x node_cap], owned by the scene (Build::node_alloc)
 	size_t node_cap = 0;
@@ -1826,7 +1907,9 @@ struct Build {
 	// (the error text is made before the streams are joined: the wait may change the last error)
 	bool fail(const char *what)
 	{
-		rtk_set_error("device build: %s: %s", what, hipGetErrorString(hipGetLastError()));
+		const hipError_t e = hipGetLastError();
+		rc = e == hipErrorOutOfMemory ? RTK_AMD_ERR_OOM : RTK_AMD_ERR_HIP;
+		rtk_set_error("device build: %s: %s", what, hipGetErrorString(e));
 		return give_up();
 	}
 	// a device allocation the scene owns
@@ -1922,11 +2005,12 @@ bool prepare_workspace(Build &b)
 	for (size_t mi = 0; mi < b.plans.size(); mi++) uploads[mi] = BuildUpload{ b.plans[mi].ibytes, b.plans[mi].pbytes };
 	BuildLayout &L = b.L;
 	if (!rtk_build_layout(b.n, uploads, b.packed, b.tile_mode, b.top_cap, rtk_sort_scratch_words(b.n), &L)) { rtk_set_error("device build: workspace too small (internal error)"); return false; }
-	if (!workspace_grow(ws, L.bytes, 8) || L.bytes > ws.cap) { rtk_set_error("device build: out of device memory (%zu bytes of workspace)", L.bytes); return false; }
+	if (!workspace_grow(ws, L.bytes, 8) || L.bytes > ws.cap) { b.rc = RTK_AMD_ERR_OOM; rtk_set_error("device build: out of device memory (%zu bytes of workspace)", L.bytes); return false; }
 	if (!ws.stream && hipStreamCreateWithFlags(&ws.stream, hipStreamNonBlocking) != hipSuccess) { ws.stream = nullptr; rtk_set_error("device build: hipStreamCreate failed"); return false; }
 	if (!ws.h_results && hipHostMalloc(reinterpret_cast<void **>(&ws.h_results), sizeof(BuildResults), hipHostMallocDefault) != hipSuccess) {
 		(void)hipGetLastError();
 		ws.h_results = nullptr;
+		b.rc = RTK_AMD_ERR_OOM;
 		rtk_set_error("device build: no pinned host memory for the build's results");
 		return false;
 	}
@@ -2021,6 +2105,50 @@ bool ingest(Build &b)
 	return true;
 }
 
+// ---- 1b the other ingest: the records of a live scene (rtk_dev_scene_rebuild). The new scene object; centroids, their bounds and
+// [primitive] -> slot from the old records (k_stage_scene); the one refusal that needs the device ----
+bool ingest_scene(Build &b)
+{
+	const rtk_dev_scene *from = b.from;
+	const hipStream_t bs = b.bs;
+	rtk_dev_scene *ds = b.ds = new rtk_dev_scene();
+	ds->device = b.device;
+	ds->num_cus = b.num_cus;
+	ds->mesh_base = b.mesh_base;
+	ds->side_ready = false;
+	// The vertex indices in input order. A scene the device built has them, or needs none (implicit indices everywhere): either
+	// way they are in input order already and stay where they are. A scene that arrived as a blob (no mesh table on the device:
+	// only a build makes one) has them by slot alone, in its side arrays: they are staged by primitive here.
+	const bool from_blob = !from->d_mesh_base && !from->d_vidx_in;
+	uint32_t *vidx_out = nullptr;
+	if (from_blob) {
+		if (!from->view.vertex_index) { b.rc = RTK_AMD_ERR_BAD_SCENE; rtk_set_error("rtk_dev_scene_rebuild: the scene has no vertex indices"); return b.give_up(); }
+		vidx_out = (uint32_t *)b.dev_alloc(3 * (size_t)b.n * 4);
+		if (!vidx_out) { (void)hipGetLastError(); b.rc = RTK_AMD_ERR_OOM; rtk_set_error("device build: out of device memory (vertex indices)"); return b.give_up(); }
+		ds->d_vidx_in = vidx_out;
+	} else ds->d_vidx_in = from->d_vidx_in;        // (an entry of the live scene's ledger, not of this one's: it survives either outcome)
+	b.mesh_src.assign(b.num_meshes + 1, MeshSrc{ nullptr, 0ull });
+	uint32_t *slot_of = reinterpret_cast<uint32_t *>(b.in_tris);      // (nothing is staged as InTri: the region holds [primitive] -> slot)
+	if (hipMemsetAsync(b.d_bounds, 0xff, 12, bs) != hipSuccess || hipMemsetAsync(b.d_bounds + 3, 0, 12, bs) != hipSuccess ||
+		hipMemsetAsync(b.d_bounds + STAGE_BAD_WORD, 0, 4, bs) != hipSuccess || hipMemsetAsync(slot_of, 0xff, (size_t)b.n * 4, bs) != hipSuccess) return b.fail("memset");
+	const unsigned blocks = (unsigned)std::min<size_t>(((size_t)b.n + STAGE_BLOCK - 1) / STAGE_BLOCK, (size_t)b.num_cus);
+	hipLaunchKernelGGL(k_stage_scene, dim3(blocks), dim3(STAGE_BLOCK), 0, bs, from->view.tris, b.n, from->view.vertex_index, b.d_cent, slot_of, vidx_out, b.d_bounds);
+	hipLaunchKernelGGL(k_stage_check, dim3((b.n + 255u) / 256u), dim3(256), 0, bs, slot_of, b.n, b.d_bounds);
+	if (hipGetLastError() != hipSuccess) return b.fail("staging launch");
+	// (the one wait a build from a description does not have: the emit gathers through slot_of, which must be whole before it is trusted)
+	b.results->pad = 0u;
+	if (hipMemcpyAsync(&b.results->pad, b.d_bounds + STAGE_BAD_WORD, 4, hipMemcpyDeviceToHost, bs) != hipSuccess || hipStreamSynchronize(bs) != hipSuccess) return b.fail("staging");
+	if (b.results->pad != 0u) {
+		b.rc = RTK_AMD_ERR_UNSUPPORTED;
+		rtk_set_error("rtk_dev_scene_rebuild: %u of %u primitives do not have exactly one triangle record", b.results->pad, b.n);
+		return b.give_up();
+	}
+	b.old_tris = from->view.tris;
+	b.slot_of = slot_of;
+	b.stage("ingest");
+	return true;
+}
+
 // ---- 2 bounds, 3 morton, 4 sort: no allocation, no host synchronisation ----
 // 63-bit Morton keys resolve 2^-21 of the scene per axis; for < 2^24 triangles the low bits never decide a
 // split that matters (lab: identical visit counts down to 30 bits at 1M triangles), so the top 40 bits are kept
@@ -2060,7 +2188,7 @@ bool emit(Build &b)
 	if (hipMemcpyAsync(b.d_mesh_base, b.mb.data(), b.mb.size() * 8, hipMemcpyHostToDevice, b.bs) != hipSuccess ||
 		hipMemcpyAsync(b.d_mesh_src, b.mesh_src.data(), b.mesh_src.size() * sizeof(MeshSrc), hipMemcpyHostToDevice, b.bs) != hipSuccess) return b.fail("copy");
 	// the triangle records in sorted order are made by k_refit_tile, which needs them next (RTK_AMD_FUSED_EMIT=0: by a pass of their own, A/B)
-	b.emit_src = EmitSrc{ b.in_tris, b.d_mesh_src, b.vals, b.keys, b.d_mesh_base, (uint32_t)b.desc->num_meshes };
+	b.emit_src = EmitSrc{ b.in_tris, b.d_mesh_src, b.vals, b.keys, b.d_mesh_base, (uint32_t)b.num_meshes, b.old_tris, b.slot_of };
 	if (!b.knobs.fused_emit) {
 		hipLaunchKernelGGL(k_emit_tris, dim3((n + 255u) / 256u), dim3(256), 0, b.bs, b.emit_src, n, b.d_tris);
 		if (hipGetLastError() != hipSuccess) return b.fail("emit launch");
@@ -2280,14 +2408,38 @@ bool finish(Build &b)
 	return true;
 }
 
-// force_bits: 0 = key width from the number of triangles; else the width of the Morton code in the packed sort words.
-// *narrow_key: the build was made with fewer than 40 bits and more than an eighth of the sorted neighbours share their code.
+// Everything behind the planning of the source, for either ingest. force_bits: 0 = key width from the number of triangles; else
+// the width of the Morton code in the packed sort words. *narrow_key: the build was made with fewer than 40 bits and more than an
+// eighth of the sorted neighbours share their code. NULL: the build failed (b.rc says how), nothing is left allocated or enqueued.
+rtk_dev_scene *run_stages(Build &b, uint32_t force_bits, bool *narrow_key)
+{
+	plan_build(b, force_bits);
+	b.ws = &g_workspace[b.device];
+	std::lock_guard<std::mutex> ws_lock(b.ws->mutex);      // held to the end: every exit below has waited for what it enqueued (Build::give_up, finish)
+	if (!prepare_workspace(b) || !(b.from ? ingest_scene(b) : ingest(b)) || !keys_and_sort(b) || !emit(b) || !refit(b)) return nullptr;
+	alloc_node_estimate(b);
+	if (b.tile_mode && !collapse_tiles(b)) return nullptr;
+	if (!b.tiles_done && !collapse_levels(b)) return nullptr;
+	if (!finish(b)) return nullptr;
+
+	*narrow_key = b.packed && b.packed_bits < 40u && (uint64_t)b.equal_codes * 8u > (uint64_t)b.n;
+	if (b.knobs.timing) fprintf(stderr, "rtk_amd build: %u key bits, %u of %u sorted neighbours share a code%s\n", b.packed ? b.packed_bits : BUILD_KEY_BITS, b.equal_codes, b.n,
+		*narrow_key ? " -> key too narrow for this scene" : "");
+	if (!b.knobs.keep_workspace) {
+		(void)hipFree(b.ws->base);
+		b.ws->base = nullptr;
+		b.ws->cap = 0;
+	}
+	return b.ds;
+}
+
 rtk_dev_scene *build_impl(const rtk_scene_desc *desc, const BuildKnobs &knobs, uint32_t force_bits, bool *narrow_key)
 {
 	*narrow_key = false;
 	if (!desc || (!desc->meshes && desc->num_meshes)) { rtk_set_error("rtk_dev_scene_build: NULL scene description"); return nullptr; }
 	Build b;
 	b.desc = desc;
+	b.num_meshes = desc->num_meshes;
 	b.knobs = knobs;
 	b.mesh_base.assign(desc->num_meshes + 1, 0);
 	for (size_t m = 0; m < desc->num_meshes; m++) b.mesh_base[m + 1] = b.mesh_base[m] + desc->meshes[m].num_triangles;
@@ -2301,25 +2453,28 @@ rtk_dev_scene *build_impl(const rtk_scene_desc *desc, const BuildKnobs &knobs, u
 	b.num_cus = cached_cu_count(b.device);
 	if (!plan_meshes(b)) return nullptr;
 	if (b.n < 2) return build_tiny(desc, b.mesh_base);
-	plan_build(b, force_bits);
+	return run_stages(b, force_bits, narrow_key);
+}
 
-	b.ws = &g_workspace[b.device];
-	std::lock_guard<std::mutex> ws_lock(b.ws->mutex);      // held to the end: every exit below has waited for what it enqueued (Build::give_up, finish)
-	if (!prepare_workspace(b) || !ingest(b) || !keys_and_sort(b) || !emit(b) || !refit(b)) return nullptr;
-	alloc_node_estimate(b);
-	if (b.tile_mode && !collapse_tiles(b)) return nullptr;
-	if (!b.tiles_done && !collapse_levels(b)) return nullptr;
-	if (!finish(b)) return nullptr;
-
-	*narrow_key = b.packed && b.packed_bits < 40u && (uint64_t)b.equal_codes * 8u > (uint64_t)b.n;
-	if (knobs.timing) fprintf(stderr, "rtk_amd build: %u key bits, %u of %u sorted neighbours share a code%s\n", b.packed ? b.packed_bits : BUILD_KEY_BITS, b.equal_codes, b.n,
-		*narrow_key ? " -> key too narrow for this scene" : "");
-	if (!knobs.keep_workspace) {
-		(void)hipFree(b.ws->base);
-		b.ws->base = nullptr;
-		b.ws->cap = 0;
-	}
-	return b.ds;
+// One build over the records of `from` (at least two, one per primitive as far as the host can tell), into a scene object of its
+// own: `from` is read and not written. *key_bits: the width of the Morton code it sorted by.
+rtk_dev_scene *rebuild_impl(const rtk_dev_scene *from, const BuildKnobs &knobs, uint32_t force_bits, bool *narrow_key, uint32_t *key_bits, int *rc)
+{
+	*narrow_key = false;
+	Build b;
+	b.from = from;
+	b.num_meshes = from->mesh_base.empty() ? 0 : from->mesh_base.size() - 1;
+	b.knobs = knobs;
+	b.mesh_base = from->mesh_base;
+	b.plans.assign(b.num_meshes, MeshPlan());              // (nothing is uploaded: the layout is asked with all-zero uploads)
+	b.n = from->view.num_tris;
+	b.t_begin = b.t_last = std::chrono::steady_clock::now();
+	b.device = from->device;
+	b.num_cus = cached_cu_count(b.device);
+	rtk_dev_scene *ds = run_stages(b, force_bits, narrow_key);
+	*key_bits = b.packed ? b.packed_bits : BUILD_KEY_BITS;
+	*rc = ds ? RTK_AMD_OK : b.rc;
+	return ds;
 }
 
 } // namespace
@@ -2342,6 +2497,84 @@ extern "C" rtk_dev_scene *rtk_dev_scene_build(const rtk_scene_desc *desc)
 	ds = build_impl(desc, knobs, 40u, &narrow);
 	if (ds) { ds->build_ms += first_ms; ds->boxes_exact = true; }
 	return ds;
+}
+
+// rtk_dev_scene_rebuild: the device builder's tree over the triangles a scene holds now, adopted by the live handle
+// (rtk_amd.h has the contract, DESIGN.md 3.4d the reasons). The build runs as rtk_dev_scene_build runs it -- same knobs, same
+// plan, same narrow-key rule -- from the scene's own records (ingest_scene) into a scene object of its own; the live scene is
+// read until the build's last wait is over and written only by the swap below, which cannot fail.
+extern "C" int rtk_dev_scene_rebuild(rtk_dev_scene *ds, rtk_dev_rebuild_info *out, void *stream)
+{
+	// ---- refused before HIP is touched
+	if (!ds) { rtk_set_error("rtk_dev_scene_rebuild: NULL scene"); return RTK_AMD_ERR_BAD_ARG; }
+	if (out && out->struct_size < sizeof(rtk_dev_rebuild_info)) {
+		rtk_set_error("rtk_dev_scene_rebuild: struct_size %u, rtk_dev_rebuild_info has %zu bytes", out->struct_size, sizeof(rtk_dev_rebuild_info));
+		return RTK_AMD_ERR_BAD_ARG;
+	}
+	const auto t_begin = std::chrono::steady_clock::now();
+	std::lock_guard<std::mutex> lock(ds->refit_mutex);             // never beside a refit, a measurement or a split
+	rtk_dev_rebuild_info info = {};
+	info.struct_size = out ? out->struct_size : (uint32_t)sizeof(info);
+	info.nodes_before = info.nodes_after = ds->view.num_nodes;
+	info.max_depth_before = info.max_depth_after = ds->max_depth;
+	if (ds->view.num_tris != ds->view.num_prims) {
+		rtk_set_error("rtk_dev_scene_rebuild: %u triangle records for %u primitives", ds->view.num_tris, ds->view.num_prims);
+		return RTK_AMD_ERR_UNSUPPORTED;
+	}
+	if (ds->view.num_tris >= 0x3ffffff0u) { rtk_set_error("rtk_dev_scene_rebuild: more than 2^30 triangles"); return RTK_AMD_ERR_UNSUPPORTED; }
+	if (ds->view.num_tris < 2u) { if (out) *out = info; return RTK_AMD_OK; }      // (a tree of one node: there is nothing to build better)
+	SceneDeviceScope scope(ds);
+	if (!scope.ok()) return RTK_AMD_ERR_NO_DEVICE;
+	// the build runs on a stream of its own: what the caller queued on `stream` (a refit's kernels, say) is over first
+	RTK_PASS_CHECK("rtk_dev_scene_rebuild", hipStreamSynchronize((hipStream_t)stream));
+	const BuildKnobs knobs = read_build_knobs();
+	bool narrow = false;
+	int rc = RTK_AMD_OK;
+	const auto t_build = std::chrono::steady_clock::now();
+	rtk_dev_scene *ns = rebuild_impl(ds, knobs, 0u, &narrow, &info.key_bits, &rc);
+	if (ns && narrow && knobs.key_rebuild) {
+		rtk_dev_scene_free(ns);
+		ns = rebuild_impl(ds, knobs, 40u, &narrow, &info.key_bits, &rc);
+	}
+	if (!ns) return rc;
+	const auto t_swap = std::chrono::steady_clock::now();
+
+	// ---- the swap: host work only, after the build's last wait. The old arrays go, the new scene's allocations change ledgers.
+	{
+		std::lock_guard<std::mutex> side_lock(ds->side_mutex);
+		std::lock_guard<std::mutex> scratch_lock(ds->scratch_mutex);      // (the trace path reads these fields under it)
+		rtk_scene_forget_derived(ds, RTK_FORGET_TREE | RTK_FORGET_SLOTS);
+		ds->mem.release(ds->view.nodes);               // (an upload owns its arrays one by one, a device build its compressed nodes
+		ds->mem.release(ds->qnodes_mem);               // behind the exact ones and its mesh table behind the records: no entries of their own)
+		ds->mem.release(ds->view.tris);
+		ds->mem.release(ds->view.consts);
+		ds->mem.adopt_all(ns->mem);
+		ds->view = ns->view;
+		ds->max_depth = ns->max_depth;
+		ds->stack_entries = ns->stack_entries;
+		ds->first_top = ns->first_top;
+		ds->first_split = 0u;
+		ds->big_leaf_fraction = ns->big_leaf_fraction;
+		ds->consts_readback = ns->consts_readback;
+		ds->bound_abs = ns->bound_abs;
+		ds->bound_raw = ns->bound_raw;
+		ds->qnodes_mem = ns->qnodes_mem;
+		ds->d_vidx_in = ns->d_vidx_in;
+		ds->d_mesh_base = ns->d_mesh_base;
+		ds->side_ready = false;
+		ds->boxes_exact = true;
+		ds->quality.refitted = false;                  // a new tree, never refitted: the next measurement is its cost at build
+	}
+	rtk_dev_scene_free(ns);                            // (the shell: its ledger is empty, it never had launch scratch)
+	info.nodes_after = ds->view.num_nodes;
+	info.max_depth_after = ds->max_depth;
+	const auto t_end = std::chrono::steady_clock::now();
+	info.rebuild_ms = std::chrono::duration<double, std::milli>(t_end - t_begin).count();
+	if (knobs.timing) fprintf(stderr, "rtk_amd rebuild: wait for the stream %.3f ms, build %.3f ms, swap (the old arrays released) %.3f ms\n",
+		std::chrono::duration<double, std::milli>(t_build - t_begin).count(), std::chrono::duration<double, std::milli>(t_swap - t_build).count(),
+		std::chrono::duration<double, std::milli>(t_end - t_swap).count());
+	if (out) *out = info;
+	return RTK_AMD_OK;
 }
 
 // The four side arrays of a device-built scene, made when something first needs them (the expansion of hit records into rtk_hit,

@@ -73,6 +73,15 @@ void rtk_scene_forget_derived(rtk_dev_scene *ds, unsigned what)
 		ds->quality.baseline_known = false;
 		ds->quality.sah_cost_at_build = 0.0;
 	}
+	if (what & RTK_FORGET_SLOTS) {
+		// (a device build made the four as one allocation that begins with the vertex indices, an upload one by one)
+		ds->mem.release(ds->view.vertex_index);
+		ds->mem.release(ds->view.prim_slot);
+		ds->mem.release(ds->view.slot_mesh);
+		ds->mem.release(ds->view.slot_tri);
+		ds->view.vertex_index = ds->view.prim_slot = ds->view.slot_mesh = ds->view.slot_tri = nullptr;
+		ds->side_ready = false;
+	}
 }
 
 extern "C" void rtk_dev_scene_free(rtk_dev_scene *ds)

@@ -187,11 +187,11 @@ struct rtk_dev_scene {
 	// hit records, the validator and the exporter read -- never a traversal) on first use, not in every build: 52 of the 100
 	// bytes per triangle the build's emit kernel wrote, one of them scattered (rtk_scene_side_arrays, rtk_build.hip).
 	// RTK_FORGET_TREE keeps them: they go by slot and primitive, not by node, and the split kernel moves their entries with the
-	// triangle records it reorders (k_split_leaves<true>, under side_mutex).
+	// triangle records it reorders (k_split_leaves<true>, under side_mutex). RTK_FORGET_SLOTS drops them (a rebuild: every slot changes).
 	std::mutex side_mutex;
 	bool side_ready = true;                    // (uploads arrive with the arrays)
 	const uint32_t *d_vidx_in = nullptr;       // [3 * prim + k] original vertex indices in input order; NULL: every mesh has implicit indices
-	const unsigned long long *d_mesh_base = nullptr;   // num_meshes + 1, on the device
+	const unsigned long long *d_mesh_base = nullptr;   // num_meshes + 1, on the device (made by a build or a rebuild; NULL: a blob as it was uploaded)
 	// Refits (rtk_refit.hip). The schedule is made by the first one and kept, like the side arrays; none of it is in the view
 	// the traversals copy.
 	const DevNodeQ *qnodes_mem = nullptr;      // the compressed array, also while view.qnodes is NULL (a misfit): the next refit fills it again
@@ -210,6 +210,7 @@ int rtk_scene_side_arrays(const rtk_dev_scene *ds, hipStream_t stream);
 // again makes it again. A new derived table is added to this function and nowhere else.
 #define RTK_FORGET_BOXES 1u       // boxes moved, the topology stayed (a refit): the export plan; a cost measured from now on is not the build's
 #define RTK_FORGET_TREE 2u        // nodes or slots were renumbered (a split): the refit schedule, the partial refit's tables, the export plan, the cost at build
+#define RTK_FORGET_SLOTS 4u       // every record changed its slot (a rebuild): the four side arrays, made again on first use. The caller holds side_mutex.
 void rtk_scene_forget_derived(rtk_dev_scene *ds, unsigned what);
 
 // -- error plumbing (rtk_capi.hip) --

@@ -191,6 +191,17 @@ extern "C" int rtk_mgpu_split_leaves(rtk_mgpu *m, uint32_t max_leaf)
 	});
 }
 
+// the device builder's tree on every GPU (rtk_dev_scene_rebuild): the build is deterministic, so replicas that agreed agree afterwards
+extern "C" int rtk_mgpu_rebuild(rtk_mgpu *m)
+{
+	if (!m) { rtk_set_error("rtk_mgpu_rebuild: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
+	for (const DeviceSlot &s : m->slots) if (!s.scene) { rtk_set_error("rtk_mgpu_rebuild: the context holds no scene"); return RTK_AMD_ERR_BAD_ARG; }
+	return for_each_slot_in_parallel(m, [&](size_t j) -> int {
+		DeviceSlot &s = m->slots[j];
+		return rtk_dev_scene_rebuild(s.scene, nullptr, s.trace_stream);
+	});
+}
+
 // the same for some meshes (rtk_dev_scene_refit_meshes)
 extern "C" int rtk_mgpu_refit_meshes(rtk_mgpu *m, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids)
 {

@@ -16,6 +16,9 @@
 //   make_partial_tables (rtk_refit.hip)         eight tables on 256-byte steps        the tables' unpadded sum
 //   make_buffers (rtk_quality.hip)              records + result slot                 the same
 //   rtk_dev_scene_split_leaves, node block      new nodes * (128 + 64)                the same
+//   rtk_dev_scene_rebuild                       a build's entries (Build::dev_alloc,  the same: they change ledgers as they are
+//                                               the node block, the constants)        (adopt_all), the old ones are released
+//   rtk_dev_scene_rebuild of a blob, d_vidx_in  num_tris * 12, by Build::dev_alloc    the same
 //
 // The allocator and its free are the owner's (hipMalloc / hipFree for a scene, malloc / free for tests/scene_mem_driver.cpp).
 // One lock of its own: the side arrays arrive under another mutex of the scene than the tables of a refit or a measurement.
@@ -45,6 +48,17 @@ public:
 	{
 		std::lock_guard<std::mutex> lock(mutex_);
 		entries_.push_back(Entry{ p, counted_bytes });
+	}
+	// every entry of `from` (same allocator) becomes an entry of this ledger, counted as it was; `from` is left empty
+	void adopt_all(SceneMem &from)
+	{
+		std::vector<Entry> moved;
+		{
+			std::lock_guard<std::mutex> lock(from.mutex_);
+			moved.swap(from.entries_);
+		}
+		std::lock_guard<std::mutex> lock(mutex_);
+		entries_.insert(entries_.end(), moved.begin(), moved.end());
 	}
 	// frees and forgets one entry; false (and nothing freed) for NULL or a pointer that is not an entry's
 	bool release(const void *p)
