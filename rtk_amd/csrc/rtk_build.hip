@@ -1613,7 +1613,9 @@ rtk_dev_scene *build_tiny(const rtk_scene_desc *desc, const std::vector<uint64_t
 		root.child[0] = RTK_REF_LEAF | 0u;
 	}
 	h.nodes.push_back(root);
-	return rtk_dev_scene_from_host_bvh(h);
+	rtk_dev_scene *ds = rtk_dev_scene_from_host_bvh(h);
+	if (ds) ds->tree.boxes_exact = true;       // (as finish() says of every device build)
+	return ds;
 }
 
 } // namespace
@@ -2052,7 +2054,7 @@ bool ingest(Build &b)
 	if (any_indexed) {
 		b.d_vidx_in = (uint32_t *)b.dev_alloc(3 * (size_t)b.n * 4);
 		if (!b.d_vidx_in) { (void)hipGetLastError(); rtk_set_error("device build: out of device memory (vertex indices)"); return b.give_up(); }
-		ds->d_vidx_in = b.d_vidx_in;
+		ds->tree.d_vidx_in = b.d_vidx_in;
 	}
 	b.mesh_src.assign(desc->num_meshes + 1, MeshSrc{ nullptr, 0ull });
 	// centroid bounds: min words start at all ones, max words at zero (ordered-uint encoding): two fills, nothing the host
@@ -2119,14 +2121,14 @@ bool ingest_scene(Build &b)
 	// The vertex indices in input order. A scene the device built has them, or needs none (implicit indices everywhere): either
 	// way they are in input order already and stay where they are. A scene that arrived as a blob (no mesh table on the device:
 	// only a build makes one) has them by slot alone, in its side arrays: they are staged by primitive here.
-	const bool from_blob = !from->d_mesh_base && !from->d_vidx_in;
+	const bool from_blob = !from->tree.d_mesh_base && !from->tree.d_vidx_in;
 	uint32_t *vidx_out = nullptr;
 	if (from_blob) {
 		if (!from->view.vertex_index) { b.rc = RTK_AMD_ERR_BAD_SCENE; rtk_set_error("rtk_dev_scene_rebuild: the scene has no vertex indices"); return b.give_up(); }
 		vidx_out = (uint32_t *)b.dev_alloc(3 * (size_t)b.n * 4);
 		if (!vidx_out) { (void)hipGetLastError(); b.rc = RTK_AMD_ERR_OOM; rtk_set_error("device build: out of device memory (vertex indices)"); return b.give_up(); }
-		ds->d_vidx_in = vidx_out;
-	} else ds->d_vidx_in = from->d_vidx_in;        // (an entry of the live scene's ledger, not of this one's: it survives either outcome)
+		ds->tree.d_vidx_in = vidx_out;
+	} else ds->tree.d_vidx_in = from->tree.d_vidx_in;        // (an entry of the live scene's ledger, not of this one's: it survives either outcome)
 	b.mesh_src.assign(b.num_meshes + 1, MeshSrc{ nullptr, 0ull });
 	uint32_t *slot_of = reinterpret_cast<uint32_t *>(b.in_tris);      // (nothing is staged as InTri: the region holds [primitive] -> slot)
 	if (hipMemsetAsync(b.d_bounds, 0xff, 12, bs) != hipSuccess || hipMemsetAsync(b.d_bounds + 3, 0, 12, bs) != hipSuccess ||
@@ -2179,12 +2181,13 @@ bool emit(Build &b)
 	const uint32_t n = b.n;
 	b.mb.assign(b.mesh_base.begin(), b.mesh_base.end());
 	// the triangle records; the mesh table (a few words the scene keeps: rtk_scene_side_arrays reads it)
-	const size_t o_mb = rtk_padded((size_t)n * sizeof(DevTri)), tri_block = o_mb + rtk_padded(b.mb.size() * 8);
-	char *tri_mem = b.dev_alloc(tri_block);
+	Carve c;
+	const size_t o_tris = c.take((size_t)n * sizeof(DevTri)), o_mb = c.take(b.mb.size() * 8);
+	char *tri_mem = b.dev_alloc(c.bytes);
 	if (!tri_mem) return b.fail("out of device memory");
-	b.d_tris = (DevTri *)tri_mem;
+	b.d_tris = (DevTri *)(tri_mem + o_tris);
 	b.d_mesh_base = (unsigned long long *)(tri_mem + o_mb);
-	b.ds->d_mesh_base = b.d_mesh_base;
+	b.ds->tree.d_mesh_base = b.d_mesh_base;
 	if (hipMemcpyAsync(b.d_mesh_base, b.mb.data(), b.mb.size() * 8, hipMemcpyHostToDevice, b.bs) != hipSuccess ||
 		hipMemcpyAsync(b.d_mesh_src, b.mesh_src.data(), b.mesh_src.size() * sizeof(MeshSrc), hipMemcpyHostToDevice, b.bs) != hipSuccess) return b.fail("copy");
 	// the triangle records in sorted order are made by k_refit_tile, which needs them next (RTK_AMD_FUSED_EMIT=0: by a pass of their own, A/B)
@@ -2310,7 +2313,7 @@ bool collapse_tiles(Build &b)
 		const uint32_t tile_nodes = results->tiles_total;      // wide nodes of all tiles
 		b.depth = results->depth;
 		b.equal_codes = results->equal_codes;
-		b.ds->consts_readback = results->consts;
+		b.ds->tree.consts_readback = results->consts;
 #ifdef RTK_TILE_PHASES
 		{
 			unsigned long long h[8] = {}, z[8] = {};
@@ -2333,7 +2336,7 @@ bool collapse_tiles(Build &b)
 			b.ds->view.nodes = d_nodes_;
 			b.ds->view.qnodes = d_qnodes_;
 			b.ds->view.num_nodes = b.total_nodes;
-			b.ds->first_top = 1u + tile_nodes;
+			b.ds->tree.first_top = 1u + tile_nodes;
 			b.tiles_done = true;
 			break;
 		}
@@ -2393,7 +2396,7 @@ bool finish(Build &b)
 	if (hipStreamSynchronize(b.bs) != hipSuccess || (b.side_busy && hipStreamSynchronize(b.ws->side) != hipSuccess)) return b.fail("sync");
 	if (!b.tiles_done) {
 		b.equal_codes = b.results->equal_codes;
-		ds->consts_readback = b.results->consts;
+		ds->tree.consts_readback = b.results->consts;
 	}
 	rtk_quantize_finish(ds);
 	ds->view.tris = b.d_tris;
@@ -2401,8 +2404,8 @@ bool finish(Build &b)
 	ds->view.num_nodes = b.total_nodes;
 	ds->view.num_tris = b.n;
 	ds->view.num_prims = b.n;
-	ds->max_depth = b.depth;
-	ds->stack_entries = 3u * b.depth + 1u;
+	ds->tree.max_depth = b.depth;
+	ds->tree.boxes_exact = true;               // (every box the union of what is below it: what a refit of some meshes relies on)
 	b.stage("finish");
 	ds->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - b.t_begin).count();
 	return true;
@@ -2490,12 +2493,11 @@ extern "C" rtk_dev_scene *rtk_dev_scene_build(const rtk_scene_desc *desc)
 	const BuildKnobs knobs = read_build_knobs();
 	bool narrow = false;
 	rtk_dev_scene *ds = build_impl(desc, knobs, 0u, &narrow);
-	if (ds) ds->boxes_exact = true;            // (every box the union of what is below it: what a refit of some meshes relies on)
 	if (!ds || !narrow || !knobs.key_rebuild) return ds;
 	const double first_ms = ds->build_ms;
 	rtk_dev_scene_free(ds);
 	ds = build_impl(desc, knobs, 40u, &narrow);
-	if (ds) { ds->build_ms += first_ms; ds->boxes_exact = true; }
+	if (ds) ds->build_ms += first_ms;
 	return ds;
 }
 
@@ -2511,22 +2513,20 @@ extern "C" int rtk_dev_scene_rebuild(rtk_dev_scene *ds, rtk_dev_rebuild_info *ou
 		rtk_set_error("rtk_dev_scene_rebuild: struct_size %u, rtk_dev_rebuild_info has %zu bytes", out->struct_size, sizeof(rtk_dev_rebuild_info));
 		return RTK_AMD_ERR_BAD_ARG;
 	}
-	const auto t_begin = std::chrono::steady_clock::now();
-	std::lock_guard<std::mutex> lock(ds->refit_mutex);             // never beside a refit, a measurement or a split
+	ScenePass pass(ds, stream);                                    // never beside a refit, a measurement or a split
 	rtk_dev_rebuild_info info = {};
 	info.struct_size = out ? out->struct_size : (uint32_t)sizeof(info);
 	info.nodes_before = info.nodes_after = ds->view.num_nodes;
-	info.max_depth_before = info.max_depth_after = ds->max_depth;
+	info.max_depth_before = info.max_depth_after = ds->tree.max_depth;
 	if (ds->view.num_tris != ds->view.num_prims) {
 		rtk_set_error("rtk_dev_scene_rebuild: %u triangle records for %u primitives", ds->view.num_tris, ds->view.num_prims);
 		return RTK_AMD_ERR_UNSUPPORTED;
 	}
 	if (ds->view.num_tris >= 0x3ffffff0u) { rtk_set_error("rtk_dev_scene_rebuild: more than 2^30 triangles"); return RTK_AMD_ERR_UNSUPPORTED; }
 	if (ds->view.num_tris < 2u) { if (out) *out = info; return RTK_AMD_OK; }      // (a tree of one node: there is nothing to build better)
-	SceneDeviceScope scope(ds);
-	if (!scope.ok()) return RTK_AMD_ERR_NO_DEVICE;
+	if (!pass.on_device()) return RTK_AMD_ERR_NO_DEVICE;
 	// the build runs on a stream of its own: what the caller queued on `stream` (a refit's kernels, say) is over first
-	RTK_PASS_CHECK("rtk_dev_scene_rebuild", hipStreamSynchronize((hipStream_t)stream));
+	RTK_PASS_CHECK("rtk_dev_scene_rebuild", hipStreamSynchronize(pass.stream));
 	const BuildKnobs knobs = read_build_knobs();
 	bool narrow = false;
 	int rc = RTK_AMD_OK;
@@ -2536,7 +2536,7 @@ extern "C" int rtk_dev_scene_rebuild(rtk_dev_scene *ds, rtk_dev_rebuild_info *ou
 		rtk_dev_scene_free(ns);
 		ns = rebuild_impl(ds, knobs, 40u, &narrow, &info.key_bits, &rc);
 	}
-	if (!ns) return rc;
+	if (!ns) return pass.end(rc);
 	const auto t_swap = std::chrono::steady_clock::now();
 
 	// ---- the swap: host work only, after the build's last wait. The old arrays go, the new scene's allocations change ledgers.
@@ -2545,34 +2545,23 @@ extern "C" int rtk_dev_scene_rebuild(rtk_dev_scene *ds, rtk_dev_rebuild_info *ou
 		std::lock_guard<std::mutex> scratch_lock(ds->scratch_mutex);      // (the trace path reads these fields under it)
 		rtk_scene_forget_derived(ds, RTK_FORGET_TREE | RTK_FORGET_SLOTS);
 		ds->mem.release(ds->view.nodes);               // (an upload owns its arrays one by one, a device build its compressed nodes
-		ds->mem.release(ds->qnodes_mem);               // behind the exact ones and its mesh table behind the records: no entries of their own)
+		ds->mem.release(ds->tree.qnodes_mem);          // behind the exact ones and its mesh table behind the records: no entries of their own)
 		ds->mem.release(ds->view.tris);
 		ds->mem.release(ds->view.consts);
 		ds->mem.adopt_all(ns->mem);
+		// view and record as wholes (SceneTree's rule, rtk_dev.h): a fresh build's first_split is 0, its boxes are exact, its side
+		// arrays are not made -- as RTK_FORGET_SLOTS has just left this scene's
 		ds->view = ns->view;
-		ds->max_depth = ns->max_depth;
-		ds->stack_entries = ns->stack_entries;
-		ds->first_top = ns->first_top;
-		ds->first_split = 0u;
-		ds->big_leaf_fraction = ns->big_leaf_fraction;
-		ds->consts_readback = ns->consts_readback;
-		ds->bound_abs = ns->bound_abs;
-		ds->bound_raw = ns->bound_raw;
-		ds->qnodes_mem = ns->qnodes_mem;
-		ds->d_vidx_in = ns->d_vidx_in;
-		ds->d_mesh_base = ns->d_mesh_base;
-		ds->side_ready = false;
-		ds->boxes_exact = true;
-		ds->quality.refitted = false;                  // a new tree, never refitted: the next measurement is its cost at build
+		ds->tree = ns->tree;
+		ds->quality.refitted = false;                  // the one deviation: a new tree, never refitted, so the next measurement is its cost at build
 	}
 	rtk_dev_scene_free(ns);                            // (the shell: its ledger is empty, it never had launch scratch)
 	info.nodes_after = ds->view.num_nodes;
-	info.max_depth_after = ds->max_depth;
-	const auto t_end = std::chrono::steady_clock::now();
-	info.rebuild_ms = std::chrono::duration<double, std::milli>(t_end - t_begin).count();
+	info.max_depth_after = ds->tree.max_depth;
+	info.rebuild_ms = pass.ms();
 	if (knobs.timing) fprintf(stderr, "rtk_amd rebuild: wait for the stream %.3f ms, build %.3f ms, swap (the old arrays released) %.3f ms\n",
-		std::chrono::duration<double, std::milli>(t_build - t_begin).count(), std::chrono::duration<double, std::milli>(t_swap - t_build).count(),
-		std::chrono::duration<double, std::milli>(t_end - t_swap).count());
+		std::chrono::duration<double, std::milli>(t_build - pass.t_begin).count(), std::chrono::duration<double, std::milli>(t_swap - t_build).count(),
+		std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_swap).count());
 	if (out) *out = info;
 	return RTK_AMD_OK;
 }
@@ -2587,12 +2576,13 @@ int rtk_scene_side_arrays(const rtk_dev_scene *ds_c, hipStream_t stream)
 	std::lock_guard<std::mutex> lock(ds->side_mutex);
 	if (ds->side_ready) return RTK_AMD_OK;
 	const size_t n = ds->view.num_tris, np = ds->view.num_prims;
-	const size_t o_pslot = rtk_padded(3 * n * 4), o_smesh = o_pslot + rtk_padded(np * 4), o_stri = o_smesh + rtk_padded(n * 4), total = o_stri + rtk_padded(n * 4);
-	char *base = (char *)ds->mem.own(total, total);
+	Carve c;
+	const size_t o_vidx = c.take(3 * n * 4), o_pslot = c.take(np * 4), o_smesh = c.take(n * 4), o_stri = c.take(n * 4);
+	char *base = (char *)ds->mem.own(c.bytes, c.bytes);
 	if (!base) { rtk_set_error("rtk_scene_side_arrays: %s", hipGetErrorString(hipGetLastError())); return RTK_AMD_ERR_OOM; }
-	uint32_t *vertex_index = (uint32_t *)base, *prim_slot = (uint32_t *)(base + o_pslot), *slot_mesh = (uint32_t *)(base + o_smesh), *slot_tri = (uint32_t *)(base + o_stri);
+	uint32_t *vertex_index = (uint32_t *)(base + o_vidx), *prim_slot = (uint32_t *)(base + o_pslot), *slot_mesh = (uint32_t *)(base + o_smesh), *slot_tri = (uint32_t *)(base + o_stri);
 	if (n) {
-		hipLaunchKernelGGL(k_side_arrays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ds->view.tris, (uint32_t)n, ds->d_mesh_base, ds->d_vidx_in,
+		hipLaunchKernelGGL(k_side_arrays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ds->view.tris, (uint32_t)n, ds->tree.d_mesh_base, ds->tree.d_vidx_in,
 			vertex_index, prim_slot, slot_mesh, slot_tri);
 		if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
 			rtk_set_error("rtk_scene_side_arrays: %s", hipGetErrorString(hipGetLastError()));

@@ -102,8 +102,8 @@ extern "C" int rtk_dev_scene_get_info(const rtk_dev_scene *ds, rtk_dev_scene_inf
 	info->node_bytes = (uint64_t)ds->view.num_nodes * sizeof(DevNode);
 	info->triangle_bytes = (uint64_t)ds->view.num_tris * sizeof(DevTri);
 	info->total_device_bytes = ds->mem.counted();
-	info->max_depth = ds->max_depth;
-	info->stack_entries = ds->stack_entries;
+	info->max_depth = ds->tree.max_depth;
+	info->stack_entries = ds->tree.stack_entries();
 	info->build_ms = ds->build_ms;
 	return RTK_AMD_OK;
 }

@@ -11,11 +11,14 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <chrono>
 #include <mutex>
+#include <optional>
 #include <vector>
 
 #include "rtk.h"
 #include "rtk_amd.h"
+#include "rtk_carve.h"
 #include "rtk_scene_mem.h"
 
 #define RTK_MAX_DEVICES 64       // per-device tables (workspaces, cached properties)
@@ -163,20 +166,31 @@ struct QualityState {
 static inline void *rtk_dev_malloc(size_t bytes) { void *p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; }
 static inline void rtk_dev_free(void *p) { (void)hipFree(p); }
 
+// The tree a scene holds now, as far as the host describes it besides the view. THE RULE: a host field that a rebuild must replace
+// is a member of SceneTree, and nowhere else. A build, an upload and a split fill the record; rtk_dev_scene_rebuild replaces view
+// and tree as wholes, so a member added here cannot be forgotten there. Whoever writes a member the trace path reads (bound_abs,
+// bound_raw, big_leaf_fraction, max_depth, qnodes_mem) does so under scratch_mutex, like the view.
+struct SceneTree {
+	uint32_t max_depth = 0;
+	uint32_t first_top = 0;                // device build, tile collapse: nodes [1, first_top) are the tiles', 0 and [first_top, n) the ones above them (0: one run)
+	uint32_t first_split = 0;              // rtk_dev_scene_split_leaves: nodes [first_split, n) were appended by a split, each after its parent (0: none)
+	double big_leaf_fraction = 0.0;        // leaves of more than three triangles (uploads; device builds make ~none): the assembly packet kernel hands those tiles back
+	DevSceneConsts consts_readback = {};   // filled by the stream that ran k_quantize; read by rtk_quantize_finish after its synchronisation
+	float bound_abs = 0.0f, bound_raw = 0.0f;
+	const DevNodeQ *qnodes_mem = nullptr;      // the compressed array, also while view.qnodes is NULL (a misfit): the next refit fills it again
+	bool boxes_exact = false;                  // every box is known to be the exact union of what is below it (a device build, a full refit; not an upload)
+	const uint32_t *d_vidx_in = nullptr;       // [3 * prim + k] original vertex indices in input order; NULL: every mesh has implicit indices
+	const unsigned long long *d_mesh_base = nullptr;   // num_meshes + 1, on the device (made by a build or a rebuild; NULL: a blob as it was uploaded)
+	uint32_t stack_entries() const { return 3u * max_depth + 1u; }   // traversal stack entries a ray can need: at most three pushes per level of descent
+};
+
 struct rtk_dev_scene {
 	int device = 0;
 	DevSceneView view = {};
-	// host copies kept for export / info
+	SceneTree tree;
+	// what describes calls, the input or derived tables, not the tree
 	std::vector<uint64_t> mesh_base;  // num_meshes + 1
-	uint32_t max_depth = 0;
-	uint32_t stack_entries = 0;
-	uint32_t first_top = 0;                // device build, tile collapse: nodes [1, first_top) are the tiles', 0 and [first_top, n) the ones above them (0: one run)
-	uint32_t first_split = 0;              // rtk_dev_scene_split_leaves: nodes [first_split, n) were appended by a split, each after its parent (0: none)
 	double build_ms = 0.0;
-	double big_leaf_fraction = 0.0;        // leaves of more than three triangles (uploads; device builds make ~none): the assembly packet kernel hands those tiles back
-	DevSceneConsts consts_readback = {};   // filled by the stream that ran k_quantize; read by rtk_quantize_finish after its synchronisation
-	float bound_abs = 0.0f;
-	float bound_raw = 0.0f;
 	// owned device allocations, and what each adds to total_device_bytes (rtk_scene_mem.h)
 	SceneMem mem{ rtk_dev_malloc, rtk_dev_free };
 	// per-stream launch scratch, created on first use; the mutex covers the list and the enqueue of a launch
@@ -190,16 +204,12 @@ struct rtk_dev_scene {
 	// triangle records it reorders (k_split_leaves<true>, under side_mutex). RTK_FORGET_SLOTS drops them (a rebuild: every slot changes).
 	std::mutex side_mutex;
 	bool side_ready = true;                    // (uploads arrive with the arrays)
-	const uint32_t *d_vidx_in = nullptr;       // [3 * prim + k] original vertex indices in input order; NULL: every mesh has implicit indices
-	const unsigned long long *d_mesh_base = nullptr;   // num_meshes + 1, on the device (made by a build or a rebuild; NULL: a blob as it was uploaded)
 	// Refits (rtk_refit.hip). The schedule is made by the first one and kept, like the side arrays; none of it is in the view
 	// the traversals copy.
-	const DevNodeQ *qnodes_mem = nullptr;      // the compressed array, also while view.qnodes is NULL (a misfit): the next refit fills it again
-	std::mutex refit_mutex;                    // one refit of a scene at a time; covers the schedule
+	std::mutex refit_mutex;                    // one pass over a scene at a time (ScenePass); covers the schedule
 	RefitSchedule refit;
 	double refit_ms = 0.0;                     // wall time inside the last rtk_dev_scene_refit / rtk_dev_scene_refit_meshes
 	RefitPartial partial;
-	bool boxes_exact = false;                  // every box is known to be the exact union of what is below it (a device build, a full refit; not an upload)
 	uint64_t refit_nodes = 0;                  // nodes whose boxes the last successful refit remade
 	uint32_t partial_readback = 0;             // the dirty count of a partial refit, brought home with the constants
 	QualityState quality;                      // under refit_mutex, like the schedule
@@ -235,8 +245,7 @@ void rtk_set_error(const char *fmt, ...);
 	} while (0)
 // ... and runs with the scene's device current: switched to here, switched back when the scope ends.
 struct SceneDeviceScope {
-	int before = 0, device;
-	hipError_t err;
+	int before = 0, device; hipError_t err;
 	explicit SceneDeviceScope(const rtk_dev_scene *ds) : device(ds->device)
 	{
 		err = hipGetDevice(&before);
@@ -246,6 +255,20 @@ struct SceneDeviceScope {
 	SceneDeviceScope(const SceneDeviceScope &) = delete;
 	~SceneDeviceScope() { if (before != device) (void)hipSetDevice(before); }
 	bool ok() const { return err == hipSuccess; }      // false: rtk_set_error has been called, nothing was switched
+};
+// The frame of such a pass: from its construction the clock runs and refit_mutex is held, to the end of the scope. The scene's
+// device becomes current when the entry point asks for it (on_device), not with the lock: what a call refuses or answers from
+// the host fields alone touches no HIP. end() is the way out once work may be enqueued: a failed pass leaves nothing running on
+// the caller's stream, which may still read the call's tables.
+struct ScenePass {
+	const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+	std::lock_guard<std::mutex> lock;
+	rtk_dev_scene *const ds; const hipStream_t stream;       // (the caller's)
+	std::optional<SceneDeviceScope> scope;
+	ScenePass(rtk_dev_scene *ds, void *stream) : lock(ds->refit_mutex), ds(ds), stream((hipStream_t)stream) {}
+	bool on_device() { scope.emplace(ds); return scope->ok(); }      // false: the call returns RTK_AMD_ERR_NO_DEVICE
+	int end(int rc) { if (rc != RTK_AMD_OK && scope && scope->ok()) (void)hipStreamSynchronize(stream); return rc; }
+	double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); }
 };
 
 // -- upload (rtk_upload.hip) --
@@ -272,7 +295,7 @@ int rtk_quantize_nodes(rtk_dev_scene *ds, hipStream_t stream, const DevNode *src
 int rtk_scene_consts(rtk_dev_scene *ds, hipStream_t stream);
 // The same finish for the nodes list[0 .. *d_count) only (a refit of some meshes): compressed node and order words of each, the
 // constants' bounds if the root is among them, misfits among them counted. The constants block is cleared first; the copy of
-// the constants to the host is enqueued. The compressed array is ds->qnodes_mem.
+// the constants to the host is enqueued. The compressed array is ds->tree.qnodes_mem.
 int rtk_quantize_node_list(rtk_dev_scene *ds, hipStream_t stream, const uint32_t *list, const uint32_t *d_count);
 void rtk_quantize_finish(rtk_dev_scene *ds);   // after that stream has been synchronised
 
@@ -291,7 +314,6 @@ struct WorkspaceLoan {
 	void release();
 };
 bool rtk_is_device_ptr(const void *p);         // hipMalloc'ed memory?
-static inline size_t rtk_padded(size_t bytes) { return ((bytes ? bytes : 1) + 255u) & ~(size_t)255u; }   // sizes inside one allocation: 256-byte steps
 void rtk_export_forget(const rtk_dev_scene *ds);   // the scene's cached export plan, if any (rtk_export.hip)
 // the two constants of the surface area heuristic, for the builder that splits by them and for rtk_dev_scene_quality that
 // measures by them: 0.5 per node visited, 1.0 per triangle tested, RTK_AMD_SAH_CN / RTK_AMD_SAH_CT override (rtk_build.hip)

@@ -168,50 +168,42 @@ extern "C" int rtk_mgpu_upload(rtk_mgpu *m, const rtk_scene *scene)
 	return replicate(m, nullptr, scene);
 }
 
+// One in-place call on the replica of every GPU: call(scene, the slot's trace stream), a host thread per device. The refusals of
+// a context that is NULL or holds no scene are here; `who` is the public function the error texts name.
+template <typename F>
+static int on_every_replica(rtk_mgpu *m, const char *who, F call)
+{
+	if (!m) { rtk_set_error("%s: NULL argument", who); return RTK_AMD_ERR_BAD_ARG; }
+	for (const DeviceSlot &s : m->slots) if (!s.scene) { rtk_set_error("%s: the context holds no scene", who); return RTK_AMD_ERR_BAD_ARG; }
+	return for_each_slot_in_parallel(m, [&](size_t j) -> int { return call(m->slots[j].scene, m->slots[j].trace_stream); });
+}
+
 // new vertex positions for the replica on every GPU, in place (rtk_dev_scene_refit), each on its slot's trace stream
 extern "C" int rtk_mgpu_refit(rtk_mgpu *m, const rtk_scene_desc *desc)
 {
-	if (!m || !desc) { rtk_set_error("rtk_mgpu_refit: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
-	for (const DeviceSlot &s : m->slots) if (!s.scene) { rtk_set_error("rtk_mgpu_refit: the context holds no scene"); return RTK_AMD_ERR_BAD_ARG; }
-	return for_each_slot_in_parallel(m, [&](size_t j) -> int {
-		DeviceSlot &s = m->slots[j];
-		return rtk_dev_scene_refit(s.scene, desc, s.trace_stream);
-	});
+	if (!desc) { rtk_set_error("rtk_mgpu_refit: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
+	return on_every_replica(m, "rtk_mgpu_refit", [&](rtk_dev_scene *ds, hipStream_t st) { return rtk_dev_scene_refit(ds, desc, st); });
 }
 
 // big leaves split on every GPU (rtk_dev_scene_split_leaves): the call is a pure function of the scene's bits, so the replicas agree afterwards
 extern "C" int rtk_mgpu_split_leaves(rtk_mgpu *m, uint32_t max_leaf)
 {
-	if (!m) { rtk_set_error("rtk_mgpu_split_leaves: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
-	if (max_leaf > 63u) { rtk_set_error("rtk_mgpu_split_leaves: max_leaf %u (0 = the device builder's limit, else 1 .. 63)", max_leaf); return RTK_AMD_ERR_BAD_ARG; }
-	for (const DeviceSlot &s : m->slots) if (!s.scene) { rtk_set_error("rtk_mgpu_split_leaves: the context holds no scene"); return RTK_AMD_ERR_BAD_ARG; }
-	return for_each_slot_in_parallel(m, [&](size_t j) -> int {
-		DeviceSlot &s = m->slots[j];
-		return rtk_dev_scene_split_leaves(s.scene, max_leaf, nullptr, s.trace_stream);
-	});
+	if (m && max_leaf > 63u) { rtk_set_error("rtk_mgpu_split_leaves: max_leaf %u (0 = the device builder's limit, else 1 .. 63)", max_leaf); return RTK_AMD_ERR_BAD_ARG; }
+	return on_every_replica(m, "rtk_mgpu_split_leaves", [&](rtk_dev_scene *ds, hipStream_t st) { return rtk_dev_scene_split_leaves(ds, max_leaf, nullptr, st); });
 }
 
 // the device builder's tree on every GPU (rtk_dev_scene_rebuild): the build is deterministic, so replicas that agreed agree afterwards
 extern "C" int rtk_mgpu_rebuild(rtk_mgpu *m)
 {
-	if (!m) { rtk_set_error("rtk_mgpu_rebuild: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
-	for (const DeviceSlot &s : m->slots) if (!s.scene) { rtk_set_error("rtk_mgpu_rebuild: the context holds no scene"); return RTK_AMD_ERR_BAD_ARG; }
-	return for_each_slot_in_parallel(m, [&](size_t j) -> int {
-		DeviceSlot &s = m->slots[j];
-		return rtk_dev_scene_rebuild(s.scene, nullptr, s.trace_stream);
-	});
+	return on_every_replica(m, "rtk_mgpu_rebuild", [&](rtk_dev_scene *ds, hipStream_t st) { return rtk_dev_scene_rebuild(ds, nullptr, st); });
 }
 
 // the same for some meshes (rtk_dev_scene_refit_meshes)
 extern "C" int rtk_mgpu_refit_meshes(rtk_mgpu *m, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids)
 {
-	if (!m || !desc) { rtk_set_error("rtk_mgpu_refit_meshes: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
-	if (!mesh_ids && num_ids) { rtk_set_error("rtk_mgpu_refit_meshes: NULL mesh_ids with %zu ids", num_ids); return RTK_AMD_ERR_BAD_ARG; }
-	for (const DeviceSlot &s : m->slots) if (!s.scene) { rtk_set_error("rtk_mgpu_refit_meshes: the context holds no scene"); return RTK_AMD_ERR_BAD_ARG; }
-	return for_each_slot_in_parallel(m, [&](size_t j) -> int {
-		DeviceSlot &s = m->slots[j];
-		return rtk_dev_scene_refit_meshes(s.scene, desc, mesh_ids, num_ids, s.trace_stream);
-	});
+	if (!desc) { rtk_set_error("rtk_mgpu_refit_meshes: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
+	if (m && !mesh_ids && num_ids) { rtk_set_error("rtk_mgpu_refit_meshes: NULL mesh_ids with %zu ids", num_ids); return RTK_AMD_ERR_BAD_ARG; }
+	return on_every_replica(m, "rtk_mgpu_refit_meshes", [&](rtk_dev_scene *ds, hipStream_t st) { return rtk_dev_scene_refit_meshes(ds, desc, mesh_ids, num_ids, st); });
 }
 
 // Where stripe `stripe` of shard `shard` lies: records [*first, *first + *count) of the buffer of GPU `stripe` (stripes of a

@@ -22,7 +22,6 @@
 #include <math.h>
 #include <string.h>
 
-#include <chrono>
 
 namespace {
 
@@ -180,18 +179,16 @@ extern "C" int rtk_dev_scene_quality(const rtk_dev_scene *scene, rtk_dev_scene_q
 		rtk_set_error("rtk_dev_scene_quality: struct_size %u, rtk_dev_scene_quality_info has %zu bytes", out->struct_size, sizeof(rtk_dev_scene_quality_info));
 		return RTK_AMD_ERR_BAD_ARG;
 	}
-	const auto t_begin = std::chrono::steady_clock::now();
 	rtk_dev_scene *ds = const_cast<rtk_dev_scene *>(scene);      // (the buffers and the remembered cost are the scene's; no bit a trace reads changes)
-	std::lock_guard<std::mutex> lock(ds->refit_mutex);           // never beside a refit; one measurement of a scene at a time (they share the records)
+	ScenePass pass(ds, stream);                                  // never beside a refit; one measurement of a scene at a time (they share the records)
 	const uint32_t struct_size = out->struct_size;
 	memset(out, 0, sizeof(*out));
 	out->struct_size = struct_size;
 	QualityResult res = {};
 	if (ds->view.num_tris != 0u && ds->view.num_nodes != 0u) {
-		SceneDeviceScope scope(ds);
-		if (!scope.ok()) return RTK_AMD_ERR_NO_DEVICE;
-		const int rc = measure_on_device(ds, (hipStream_t)stream, &res);
-		if (rc != RTK_AMD_OK) { (void)hipStreamSynchronize((hipStream_t)stream); return rc; }
+		if (!pass.on_device()) return RTK_AMD_ERR_NO_DEVICE;
+		const int rc = pass.end(measure_on_device(ds, pass.stream, &res));
+		if (rc != RTK_AMD_OK) return rc;
 	}
 	out->nonfinite_boxes = res.sum.count[2] > 0xffffffffull ? 0xffffffffu : (uint32_t)res.sum.count[2];
 	out->inner_children = res.sum.count[0];
@@ -213,6 +210,6 @@ extern "C" int rtk_dev_scene_quality(const rtk_dev_scene *scene, rtk_dev_scene_q
 		ds->quality.sah_cost_at_build = out->sah_cost;
 	}
 	out->sah_cost_at_build = ds->quality.baseline_known ? ds->quality.sah_cost_at_build : 0.0;
-	out->measure_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	out->measure_ms = pass.ms();
 	return RTK_AMD_OK;
 }

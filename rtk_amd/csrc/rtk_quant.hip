@@ -83,24 +83,24 @@ int rtk_quantize_nodes(rtk_dev_scene *ds, hipStream_t stream, const DevNode *src
 	RTK_HIP_CHECK(hipGetLastError(), RTK_AMD_ERR_HIP);
 	ds->view.qnodes = (const DevNodeQ *)p;
 	// the misfit count comes back with the caller's own synchronisation of `stream` (rtk_quantize_finish)
-	if (readback) RTK_HIP_CHECK(hipMemcpyAsync(&ds->consts_readback, consts, sizeof(DevSceneConsts), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
+	if (readback) RTK_HIP_CHECK(hipMemcpyAsync(&ds->tree.consts_readback, consts, sizeof(DevSceneConsts), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
 	return RTK_AMD_OK;
 }
 
 int rtk_quantize_node_list(rtk_dev_scene *ds, hipStream_t stream, const uint32_t *list, const uint32_t *d_count)
 {
 	const uint32_t n = ds->view.num_nodes;
-	if (!ds->qnodes_mem || !ds->view.consts) { rtk_set_error("rtk_quantize_node_list: the scene has no compressed nodes"); return RTK_AMD_ERR_BAD_SCENE; }
+	if (!ds->tree.qnodes_mem || !ds->view.consts) { rtk_set_error("rtk_quantize_node_list: the scene has no compressed nodes"); return RTK_AMD_ERR_BAD_SCENE; }
 	const int rc = rtk_scene_consts(ds, stream);
 	if (rc != RTK_AMD_OK) return rc;
 	DevSceneConsts *consts = const_cast<DevSceneConsts *>(ds->view.consts);
 	unsigned blocks = (n + 255u) / 256u;
 	if (blocks > 2048u) blocks = 2048u;
 	if (n) hipLaunchKernelGGL(k_quantize_list, dim3(blocks), dim3(256), 0, stream, const_cast<DevNode *>(ds->view.nodes), n, list, d_count,
-		const_cast<DevNodeQ *>(ds->qnodes_mem), consts);
+		const_cast<DevNodeQ *>(ds->tree.qnodes_mem), consts);
 	RTK_HIP_CHECK(hipGetLastError(), RTK_AMD_ERR_HIP);
-	ds->view.qnodes = ds->qnodes_mem;
-	RTK_HIP_CHECK(hipMemcpyAsync(&ds->consts_readback, consts, sizeof(DevSceneConsts), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
+	ds->view.qnodes = ds->tree.qnodes_mem;
+	RTK_HIP_CHECK(hipMemcpyAsync(&ds->tree.consts_readback, consts, sizeof(DevSceneConsts), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
 	return RTK_AMD_OK;
 }
 
@@ -108,8 +108,8 @@ int rtk_quantize_node_list(rtk_dev_scene *ds, hipStream_t stream, const uint32_t
 // (non-finite child extents) is traced with its exact nodes only.
 void rtk_quantize_finish(rtk_dev_scene *ds)
 {
-	ds->bound_abs = ds->consts_readback.bound_abs;
-	ds->bound_raw = ds->consts_readback.bound_raw;
-	if (ds->view.qnodes) ds->qnodes_mem = ds->view.qnodes;   // (a refit fills the array again and decides anew)
-	if (ds->consts_readback.qnode_misfits != 0u) ds->view.qnodes = nullptr;
+	ds->tree.bound_abs = ds->tree.consts_readback.bound_abs;
+	ds->tree.bound_raw = ds->tree.consts_readback.bound_raw;
+	if (ds->view.qnodes) ds->tree.qnodes_mem = ds->view.qnodes;   // (a refit fills the array again and decides anew)
+	if (ds->tree.consts_readback.qnode_misfits != 0u) ds->view.qnodes = nullptr;
 }

@@ -25,7 +25,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <chrono>
 #include <vector>
 
 namespace {
@@ -403,17 +402,11 @@ __global__ void __launch_bounds__(REFIT_SMALL_THREADS) k_refit_small(DevNode *no
 // ---------------------------------------------------------------------------------- host
 
 // temporaries of the schedule: heights, the changed word, two key arrays, the sort's scratch, level starts
-struct ScheduleTmp { size_t o_changed, o_ka, o_kb, o_sort, o_ls, bytes; };
+struct ScheduleTmp { size_t o_height, o_changed, o_ka, o_kb, o_sort, o_ls, bytes; };
 ScheduleTmp schedule_tmp(uint32_t n)
 {
-	ScheduleTmp t;
-	t.o_changed = rtk_padded((size_t)n * 4);
-	t.o_ka = t.o_changed + rtk_padded(4);
-	t.o_kb = t.o_ka + rtk_padded((size_t)n * 8);
-	t.o_sort = t.o_kb + rtk_padded((size_t)n * 8);
-	t.o_ls = t.o_sort + rtk_padded(rtk_sort_scratch_words(n) * 4);
-	t.bytes = t.o_ls + rtk_padded(((size_t)n + 2) * 4);
-	return t;
+	Carve c;       // (a braced list is evaluated left to right: the pieces in the order of the members, then their sum)
+	return ScheduleTmp{ c.take((size_t)n * 4), c.take(4), c.take((size_t)n * 8), c.take((size_t)n * 8), c.take(rtk_sort_scratch_words(n) * 4), c.take(((size_t)n + 2) * 4), c.bytes };
 }
 
 // heights, node numbers grouped by height, the mesh table's memory: once per scene. tmp: schedule_tmp(num_nodes).bytes of
@@ -425,11 +418,12 @@ int make_schedule(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
 	const uint32_t n = ds->view.num_nodes;
 	const size_t num_meshes = ds->mesh_base.empty() ? 0 : ds->mesh_base.size() - 1;
 	const ScheduleTmp T = schedule_tmp(n);
-	uint32_t *d_height = (uint32_t *)tmp, *d_changed = (uint32_t *)(tmp + T.o_changed), *d_ls = (uint32_t *)(tmp + T.o_ls);
+	uint32_t *d_height = (uint32_t *)(tmp + T.o_height), *d_changed = (uint32_t *)(tmp + T.o_changed), *d_ls = (uint32_t *)(tmp + T.o_ls);
 	unsigned long long *keys_a = (unsigned long long *)(tmp + T.o_ka), *keys_b = (unsigned long long *)(tmp + T.o_kb);
 	void *d_order = nullptr, *d_small = nullptr;
 	int rc = RTK_AMD_OK;
 	std::vector<uint32_t> level_start;
+	Carve small;
 	do {
 #define SCHED_CHECK(expr) if ((expr) != hipSuccess) { rtk_set_error("rtk_dev_scene_refit: schedule: %s failed: %s", #expr, hipGetErrorString(hipGetLastError())); rc = RTK_AMD_ERR_HIP; break; }
 		const unsigned blocks = (n + 255u) / 256u;
@@ -437,7 +431,7 @@ int make_schedule(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
 		// A tree has no cycle and its heights are below max_depth, so max_depth sweeps settle them; one more, which must change
 		// nothing, is the proof, and the one wait of the host. (Should a scene's max_depth be too small the rounds go on, eight
 		// sweeps at a time.)
-		uint32_t sweeps = 0, round = ds->max_depth < 4096u ? ds->max_depth + 1u : 4096u;
+		uint32_t sweeps = 0, round = ds->tree.max_depth < 4096u ? ds->tree.max_depth + 1u : 4096u;
 		bool converged = false;
 		while (!converged && rc == RTK_AMD_OK) {
 			uint32_t h_changed = 0;
@@ -472,11 +466,12 @@ int make_schedule(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
 		bool sane = level_start.front() == 0u && level_start.back() == n;
 		for (size_t h = 0; h + 1 < level_start.size(); h++) sane = sane && level_start[h] < level_start[h + 1];
 		if (!sane) { rtk_set_error("rtk_dev_scene_refit: schedule: heights are not contiguous"); rc = RTK_AMD_ERR_BAD_SCENE; break; }
-		// the level starts and the mesh table share one small allocation
-		const size_t o_meshes = rtk_padded(level_start.size() * 4);
-		SCHED_CHECK(hipMalloc(&d_small, o_meshes + (num_meshes ? num_meshes : 1) * sizeof(RefitMesh)));
+		// the level starts and the mesh table share one small allocation. The table lies behind the carve: the last piece, not
+		// padded, with room for one record even where there is no mesh, which the ledger does not count
+		small.take(level_start.size() * 4);
+		SCHED_CHECK(hipMalloc(&d_small, small.bytes + (num_meshes ? num_meshes : 1) * sizeof(RefitMesh)));
 		SCHED_CHECK(hipMemcpy(d_small, level_start.data(), level_start.size() * 4, hipMemcpyHostToDevice));
-		rs.d_meshes = (char *)d_small + o_meshes;
+		rs.d_meshes = (char *)d_small + small.bytes;
 #undef SCHED_CHECK
 	} while (0);
 	if (rc != RTK_AMD_OK) {
@@ -486,7 +481,7 @@ int make_schedule(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
 		return rc;
 	}
 	ds->mem.adopt(d_order, (size_t)n * 4);
-	ds->mem.adopt(d_small, level_start.size() * 4 + num_meshes * sizeof(RefitMesh));
+	ds->mem.adopt(d_small, small.counted + num_meshes * sizeof(RefitMesh));
 	rs.d_order = (uint32_t *)d_order;
 	rs.d_level_start = (uint32_t *)d_small;
 	rs.level_start.swap(level_start);
@@ -517,14 +512,11 @@ int make_max_vertex(rtk_dev_scene *ds, hipStream_t stream)
 }
 
 // temporaries of the per-mesh tables: two key arrays over the slots and the sort's scratch
-struct TablesTmp { size_t o_kb, o_sort, bytes; };
+struct TablesTmp { size_t o_ka, o_kb, o_sort, bytes; };
 TablesTmp tables_tmp(uint32_t num_tris)
 {
-	TablesTmp t;
-	t.o_kb = rtk_padded((size_t)num_tris * 8);
-	t.o_sort = t.o_kb + rtk_padded((size_t)num_tris * 8);
-	t.bytes = t.o_sort + rtk_padded(rtk_sort_scratch_words(num_tris) * 4);
-	return t;
+	Carve c;
+	return TablesTmp{ c.take((size_t)num_tris * 8), c.take((size_t)num_tris * 8), c.take(rtk_sort_scratch_words(num_tris) * 4), c.bytes };
 }
 
 // parent[], the node of every slot's leaf, the slots grouped by mesh, and the memory of the dirty set: once per scene, after
@@ -538,15 +530,15 @@ int make_partial_tables(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
 	const size_t num_meshes = ds->mesh_base.size() - 1;
 	const uint32_t nb = (n + RTK_DIRTY_BLOCK - 1u) / RTK_DIRTY_BLOCK;
 	const size_t heights = ds->refit.level_start.size() - 1;
-	const size_t o_slot_node = rtk_padded((size_t)n * 4), o_mesh_slots = o_slot_node + rtk_padded((size_t)nt * 4), o_dirty = o_mesh_slots + rtk_padded((size_t)nt * 4),
-		o_list = o_dirty + rtk_padded((size_t)n * 4), o_block = o_list + rtk_padded((size_t)n * 4), o_list_start = o_block + rtk_padded(((size_t)nb + 1) * 4),
-		o_ranges = o_list_start + rtk_padded((heights + 1) * 4), total = o_ranges + rtk_padded((num_meshes + 1) * sizeof(RefitRange));
+	Carve c;
+	const size_t o_parent = c.take((size_t)n * 4), o_slot_node = c.take((size_t)nt * 4), o_mesh_slots = c.take((size_t)nt * 4), o_dirty = c.take((size_t)n * 4),
+		o_list = c.take((size_t)n * 4), o_block = c.take(((size_t)nb + 1) * 4), o_list_start = c.take((heights + 1) * 4), o_ranges = c.take((num_meshes + 1) * sizeof(RefitRange));
 	void *mem = nullptr;
-	if (hipMalloc(&mem, total) != hipSuccess) { (void)hipGetLastError(); rtk_set_error("rtk_dev_scene_refit_meshes: out of device memory"); return RTK_AMD_ERR_OOM; }
+	if (hipMalloc(&mem, c.bytes) != hipSuccess) { (void)hipGetLastError(); rtk_set_error("rtk_dev_scene_refit_meshes: out of device memory"); return RTK_AMD_ERR_OOM; }
 	char *base = (char *)mem;
-	uint32_t *d_parent = (uint32_t *)base, *d_slot_node = (uint32_t *)(base + o_slot_node), *d_mesh_slots = (uint32_t *)(base + o_mesh_slots);
+	uint32_t *d_parent = (uint32_t *)(base + o_parent), *d_slot_node = (uint32_t *)(base + o_slot_node), *d_mesh_slots = (uint32_t *)(base + o_mesh_slots);
 	const TablesTmp T = tables_tmp(nt);
-	unsigned long long *keys_a = (unsigned long long *)tmp, *keys_b = (unsigned long long *)(tmp + T.o_kb);
+	unsigned long long *keys_a = (unsigned long long *)(tmp + T.o_ka), *keys_b = (unsigned long long *)(tmp + T.o_kb);
 	// (RTK_REF_NONE everywhere first: the root has no parent, and a slot no leaf names stays without a node)
 	bool ok = hipMemsetAsync(base, 0xff, o_mesh_slots, stream) == hipSuccess && hipMemsetAsync(base + o_dirty, 0, o_list - o_dirty, stream) == hipSuccess;
 	if (ok) {
@@ -566,7 +558,7 @@ int make_partial_tables(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
 		(void)hipFree(mem);
 		return RTK_AMD_ERR_HIP;
 	}
-	ds->mem.adopt(mem, (size_t)n * 12 + (size_t)nt * 8 + ((size_t)nb + 1) * 4 + (heights + 1) * 4 + (num_meshes + 1) * sizeof(RefitRange));
+	ds->mem.adopt(mem, c.counted);
 	rp.d_parent = d_parent; rp.d_slot_node = d_slot_node; rp.d_mesh_slots = d_mesh_slots;
 	rp.d_dirty = (uint32_t *)(base + o_dirty); rp.d_list = (uint32_t *)(base + o_list); rp.d_block = (uint32_t *)(base + o_block);
 	rp.d_list_start = (uint32_t *)(base + o_list_start); rp.d_ranges = base + o_ranges;
@@ -644,8 +636,8 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 	if (num_meshes) RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(rs.d_meshes, table.data(), num_meshes * sizeof(RefitMesh), hipMemcpyHostToDevice, stream));
 
 	// Until this call has succeeded nobody may take the boxes it leaves alone for exact unions.
-	const bool were_exact = ds->boxes_exact;
-	ds->boxes_exact = false;
+	const bool were_exact = ds->tree.boxes_exact;
+	ds->tree.boxes_exact = false;
 	// the dirty set pays while the listed meshes are a small part of the scene and the other boxes can be trusted
 	const bool dirty_set = listed && were_exact && (double)listed_tris <= partial_max_share() * (double)v.num_tris;
 
@@ -723,11 +715,11 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 		// ---- compressed nodes and order words of the dirty nodes, the constants from the root (dirty whenever anything moved).
 		// The misfit count is one over ALL nodes: the list form is the whole answer only if the others have none (the scene is on
 		// its compressed nodes now) and none of the dirty ones has one either; else the full pass below.
-		if (v.qnodes && ds->qnodes_mem) {
+		if (v.qnodes && ds->tree.qnodes_mem) {
 			rc = rtk_quantize_node_list(ds, stream, rp.d_list, rp.d_block + nb);
 			if (rc != RTK_AMD_OK) return rc;
 			RTK_PASS_CHECK("rtk_dev_scene_refit", hipStreamSynchronize(stream));
-			full_finish = ds->consts_readback.qnode_misfits != 0u;
+			full_finish = ds->tree.consts_readback.qnode_misfits != 0u;
 		}
 	} else {
 		// ---- boxes, height by height; runs of small heights share one launch of one workgroup
@@ -750,7 +742,7 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 	if (full_finish) {
 		// ---- compressed nodes, order words, constants (the block is cleared first: the misfit count starts at zero); every box
 		// lies inside the root's now, so no bound is passed in
-		rc = rtk_quantize_nodes(ds, stream, nullptr, const_cast<DevNodeQ *>(ds->qnodes_mem), 0.0f, 0xffffffffu, false, true);
+		rc = rtk_quantize_nodes(ds, stream, nullptr, const_cast<DevNodeQ *>(ds->tree.qnodes_mem), 0.0f, 0xffffffffu, false, true);
 		if (rc != RTK_AMD_OK) return rc;
 		RTK_PASS_CHECK("rtk_dev_scene_refit", hipStreamSynchronize(stream));
 	}
@@ -760,24 +752,20 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 		rtk_quantize_finish(ds);
 	}
 	rtk_scene_forget_derived(ds, RTK_FORGET_BOXES);
-	ds->boxes_exact = true;
+	ds->tree.boxes_exact = true;
 	ds->refit_nodes = dirty_set ? ds->partial_readback : v.num_nodes;
 	return RTK_AMD_OK;
 }
 
 // what both entry points do once nothing can be refused any more
-int refit_locked(rtk_dev_scene *ds, const rtk_scene_desc *desc, void *stream, const uint8_t *listed, uint64_t listed_tris)
+int refit_in_pass(ScenePass &pass, const rtk_scene_desc *desc, const uint8_t *listed, uint64_t listed_tris)
 {
-	const auto t_begin = std::chrono::steady_clock::now();
-	std::lock_guard<std::mutex> lock(ds->refit_mutex);
-	SceneDeviceScope scope(ds);
-	if (!scope.ok()) return RTK_AMD_ERR_NO_DEVICE;
+	if (!pass.on_device()) return RTK_AMD_ERR_NO_DEVICE;
 	WorkspaceLoan loan;
-	const int rc = refit_on_device(ds, desc, (hipStream_t)stream, loan, listed, listed_tris);
-	// (a failure may leave work enqueued that reads this call's tables or the workspace: it has to be over first)
-	if (rc != RTK_AMD_OK) (void)hipStreamSynchronize((hipStream_t)stream);
+	// (a failed pass has waited for whatever reads the workspace before the loan ends; the time is taken after it has)
+	const int rc = pass.end(refit_on_device(pass.ds, desc, pass.stream, loan, listed, listed_tris));
 	loan.release();
-	if (rc == RTK_AMD_OK) ds->refit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	if (rc == RTK_AMD_OK) pass.ds->refit_ms = pass.ms();
 	return rc;
 }
 
@@ -842,7 +830,8 @@ extern "C" int rtk_dev_scene_refit(rtk_dev_scene *ds, const rtk_scene_desc *desc
 		rc = check_mesh_positions("rtk_dev_scene_refit", &desc->meshes[mi], mi);
 		if (rc != RTK_AMD_OK) return rc;
 	}
-	return refit_locked(ds, desc, stream, nullptr, 0);
+	ScenePass pass(ds, stream);
+	return refit_in_pass(pass, desc, nullptr, 0);
 }
 
 extern "C" int rtk_dev_scene_refit_meshes(rtk_dev_scene *ds, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids, void *stream)
@@ -865,16 +854,15 @@ extern "C" int rtk_dev_scene_refit_meshes(rtk_dev_scene *ds, const rtk_scene_des
 		if (rc != RTK_AMD_OK) return rc;
 		listed_tris += desc->meshes[mi].num_triangles;
 	}
+	ScenePass pass(ds, stream);
 	if (listed_tris == 0) {
 		// nothing moves: no bit changes, nothing is launched
-		std::lock_guard<std::mutex> lock(ds->refit_mutex);
 		ds->refit_nodes = 0;
 		ds->refit_ms = 0.0;
 		return RTK_AMD_OK;
 	}
 	// every mesh that has a triangle is listed: that IS the full refit (no mesh it would read is one this call may not read)
-	if (listed_tris == ds->mesh_base.back()) return refit_locked(ds, desc, stream, nullptr, 0);
-	return refit_locked(ds, desc, stream, listed.data(), listed_tris);
+	return refit_in_pass(pass, desc, listed_tris == ds->mesh_base.back() ? nullptr : listed.data(), listed_tris);
 }
 
 extern "C" double rtk_dev_scene_last_refit_ms(const rtk_dev_scene *ds)

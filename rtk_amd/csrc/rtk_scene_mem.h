@@ -10,10 +10,10 @@
 //   rtk_quantize_nodes, an upload's qnodes      max(num_nodes, 1) * 64                num_nodes * 64
 //   Build::dev_alloc (rtk_build.hip)            bytes, 16 if that is 0                bytes
 //   the build's node block                      node_cap * (128 + 64)                 the same (the capacity, not num_nodes)
-//   rtk_scene_side_arrays (rtk_build.hip)       four arrays, each on a 256-byte step  the same (padded)
+//   rtk_scene_side_arrays (rtk_build.hip)       four arrays, one Carve                the same (Carve::bytes: padded)
 //   make_schedule (rtk_refit.hip), d_order      num_nodes * 4                         the same
 //   make_schedule, level starts + mesh table    padded starts + max(meshes, 1) * 24   starts * 4 + meshes * 24 (unpadded)
-//   make_partial_tables (rtk_refit.hip)         eight tables on 256-byte steps        the tables' unpadded sum
+//   make_partial_tables (rtk_refit.hip)         eight tables, one Carve               Carve::counted: the tables' unpadded sum
 //   make_buffers (rtk_quality.hip)              records + result slot                 the same
 //   rtk_dev_scene_split_leaves, node block      new nodes * (128 + 64)                the same
 //   rtk_dev_scene_rebuild                       a build's entries (Build::dev_alloc,  the same: they change ledgers as they are

@@ -29,7 +29,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
 
 uint32_t rtk_build_max_leaf();                 // RTK_AMD_MAX_LEAF as the device builder reads it (rtk_build.hip)
 
@@ -314,11 +313,11 @@ struct Temporaries {
 	~Temporaries() { if (small) (void)hipFree(small); if (tables) (void)hipFree(tables); if (new_nodes) (void)hipFree(new_nodes); }
 };
 
-// everything behind the argument checks; the scene's device is current, refit_mutex is held
+// everything behind the argument checks, inside a ScenePass on the scene's device
 int split_on_device(rtk_dev_scene *ds, uint32_t limit, hipStream_t stream, rtk_dev_split_info *info)
 {
 	const DevSceneView v = ds->view;
-	info->max_depth_before = info->max_depth_after = ds->max_depth;
+	info->max_depth_before = info->max_depth_after = ds->tree.max_depth;
 	if (v.num_tris == 0u || v.num_nodes == 0u) return RTK_AMD_OK;
 	Temporaries tmp;
 	SplitWords h = {};
@@ -336,13 +335,13 @@ int split_on_device(rtk_dev_scene *ds, uint32_t limit, hipStream_t stream, rtk_d
 
 	// ---- the big leaves in slot order, who names them, how many nodes each becomes, how deep that reaches
 	const uint32_t tri_scan = scan_blocks(v.num_tris), big_scan = scan_blocks(num_big);
-	const size_t o_tri_totals = rtk_padded((size_t)v.num_tris * 4), o_first = o_tri_totals + rtk_padded(((size_t)tri_scan + 1) * 4),
-		o_parent = o_first + rtk_padded((size_t)num_big * 4), o_count = o_parent + rtk_padded((size_t)num_big * 4),
-		o_big_totals = o_count + rtk_padded((size_t)num_big * 4), o_level = o_big_totals + rtk_padded(((size_t)big_scan + 1) * 4),
-		tables_bytes = o_level + rtk_padded((size_t)v.num_nodes * 4);
-	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipMalloc(&tmp.tables, tables_bytes));
+	Carve c;
+	const size_t o_number = c.take((size_t)v.num_tris * 4), o_tri_totals = c.take(((size_t)tri_scan + 1) * 4), o_first = c.take((size_t)num_big * 4),
+		o_parent = c.take((size_t)num_big * 4), o_count = c.take((size_t)num_big * 4), o_big_totals = c.take(((size_t)big_scan + 1) * 4),
+		o_level = c.take((size_t)v.num_nodes * 4);
+	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipMalloc(&tmp.tables, c.bytes));
 	char *tb = (char *)tmp.tables;
-	uint32_t *leaf_number = (uint32_t *)tb, *tri_totals = (uint32_t *)(tb + o_tri_totals), *leaf_first = (uint32_t *)(tb + o_first),
+	uint32_t *leaf_number = (uint32_t *)(tb + o_number), *tri_totals = (uint32_t *)(tb + o_tri_totals), *leaf_first = (uint32_t *)(tb + o_first),
 		*leaf_parent = (uint32_t *)(tb + o_parent), *node_count = (uint32_t *)(tb + o_count), *big_totals = (uint32_t *)(tb + o_big_totals),
 		*level = (uint32_t *)(tb + o_level);
 	hipLaunchKernelGGL(k_split_mark, dim3(tri_blocks), dim3(256), 0, stream, v.tris, v.num_tris, limit, leaf_number);
@@ -352,7 +351,7 @@ int split_on_device(rtk_dev_scene *ds, uint32_t limit, hipStream_t stream, rtk_d
 	RTK_PASS_CHECK("rtk_dev_scene_split_leaves", hipMemsetAsync(level, 0, (size_t)v.num_nodes * 4, stream));
 	hipLaunchKernelGGL(k_split_list, dim3((unsigned)(((size_t)v.num_nodes * 4 + 255) / 256)), dim3(256), 0, stream, v.nodes, v.num_nodes, v.tris, v.num_tris, limit,
 		leaf_number, num_big, leaf_first, leaf_parent);
-	for (uint32_t k = 0; k < ds->max_depth; k++) hipLaunchKernelGGL(k_split_depth, dim3((v.num_nodes + 255u) / 256u), dim3(256), 0, stream, v.nodes, v.num_nodes, level);
+	for (uint32_t k = 0; k < ds->tree.max_depth; k++) hipLaunchKernelGGL(k_split_depth, dim3((v.num_nodes + 255u) / 256u), dim3(256), 0, stream, v.nodes, v.num_nodes, level);
 	SplitArgs a = {};
 	a.tris = const_cast<DevTri *>(v.tris);
 	a.leaf_first = leaf_first; a.leaf_parent = leaf_parent; a.level = level; a.node_count = node_count; a.words = words;
@@ -395,29 +394,28 @@ int split_on_device(rtk_dev_scene *ds, uint32_t limit, hipStream_t stream, rtk_d
 	// ---- the scene names the new arrays; compressed nodes, order words and constants over the whole new tree. Boxes of a blob
 	// need not nest: the bound is the one the scene had (over every old node for an upload) widened by the new nodes' planes.
 	const DevNode *old_nodes = v.nodes;
-	const DevNodeQ *old_qnodes = ds->qnodes_mem;
+	const DevNodeQ *old_qnodes = ds->tree.qnodes_mem;
 	float new_bound;
 	memcpy(&new_bound, &h.bound_bits, 4);
-	const float bound_hint = fmaxf(ds->bound_raw, new_bound);      // (either may be INFINITY: the scene keeps to its exact nodes then)
+	const float bound_hint = fmaxf(ds->tree.bound_raw, new_bound);      // (either may be INFINITY: the scene keeps to its exact nodes then)
 	int rc;
 	{
 		std::lock_guard<std::mutex> lock(ds->scratch_mutex);      // (the trace path reads these fields under it)
 		ds->view.nodes = new_nodes;
 		ds->view.num_nodes = (uint32_t)new_total;
 		ds->view.qnodes = new_qnodes;
-		ds->qnodes_mem = new_qnodes;
+		ds->tree.qnodes_mem = new_qnodes;
 		rc = rtk_quantize_nodes(ds, stream, nullptr, new_qnodes, bound_hint, 0xffffffffu, false, true);
 		if (rc == RTK_AMD_OK && hipStreamSynchronize(stream) != hipSuccess) { rtk_set_error("rtk_dev_scene_split_leaves: %s", hipGetErrorString(hipGetLastError())); rc = RTK_AMD_ERR_HIP; }
 		if (rc == RTK_AMD_OK) rtk_quantize_finish(ds);
 		ds->mem.adopt(tmp.new_nodes, (size_t)new_total * (sizeof(DevNode) + sizeof(DevNodeQ)));
 		tmp.new_nodes = nullptr;
-		const uint32_t depth = h.depth > ds->max_depth ? h.depth : ds->max_depth;
-		ds->max_depth = depth;
-		ds->stack_entries = 3u * depth + 1u;
-		ds->big_leaf_fraction = h.after[W_LEAVES] ? (double)h.after[W_OVER3] / (double)h.after[W_LEAVES] : 0.0;
+		const uint32_t depth = h.depth > ds->tree.max_depth ? h.depth : ds->tree.max_depth;
+		ds->tree.max_depth = depth;
+		ds->tree.big_leaf_fraction = h.after[W_LEAVES] ? (double)h.after[W_OVER3] / (double)h.after[W_LEAVES] : 0.0;
 		// (appended nodes follow their parents in number, but a tile's node of a device-built tree may now name one outside its
 		// run: the validator is told where the appended ones begin)
-		if (ds->first_split == 0u) ds->first_split = v.num_nodes;
+		if (ds->tree.first_split == 0u) ds->tree.first_split = v.num_nodes;
 	}
 	// the old arrays: an upload owns them one by one, a device build as one allocation (the compressed nodes behind the exact
 	// ones: no entry of their own). What was derived from the old tree goes with them.
@@ -428,7 +426,7 @@ int split_on_device(rtk_dev_scene *ds, uint32_t limit, hipStream_t stream, rtk_d
 	info->leaves_split = num_big;
 	info->nodes_added = h.nodes_added;
 	info->largest_leaf_after = h.after[W_LARGEST];
-	info->max_depth_after = ds->max_depth;
+	info->max_depth_after = ds->tree.max_depth;
 	return RTK_AMD_OK;
 }
 
@@ -443,18 +441,15 @@ extern "C" int rtk_dev_scene_split_leaves(rtk_dev_scene *ds, uint32_t max_leaf, 
 		rtk_set_error("rtk_dev_scene_split_leaves: struct_size %u, rtk_dev_split_info has %zu bytes", out->struct_size, sizeof(rtk_dev_split_info));
 		return RTK_AMD_ERR_BAD_ARG;
 	}
-	const auto t_begin = std::chrono::steady_clock::now();
 	const uint32_t limit = max_leaf ? max_leaf : rtk_build_max_leaf();
 	rtk_dev_split_info info = {};
 	info.struct_size = out ? out->struct_size : (uint32_t)sizeof(info);
 	info.max_leaf = limit;
-	std::lock_guard<std::mutex> lock(ds->refit_mutex);             // never beside a refit or a measurement
-	SceneDeviceScope scope(ds);
-	if (!scope.ok()) return RTK_AMD_ERR_NO_DEVICE;
-	const int rc = split_on_device(ds, limit, (hipStream_t)stream, &info);
-	// (a failure may have left work enqueued: it is over before the caller goes on)
-	if (rc != RTK_AMD_OK) { (void)hipStreamSynchronize((hipStream_t)stream); return rc; }
-	info.split_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	ScenePass pass(ds, stream);                                    // never beside a refit or a measurement
+	if (!pass.on_device()) return RTK_AMD_ERR_NO_DEVICE;
+	const int rc = pass.end(split_on_device(ds, limit, pass.stream, &info));
+	if (rc != RTK_AMD_OK) return rc;
+	info.split_ms = pass.ms();
 	if (out) *out = info;
 	return RTK_AMD_OK;
 }

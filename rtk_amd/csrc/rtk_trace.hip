@@ -1183,7 +1183,7 @@ int enqueue_packet_hot(const rtk_dev_scene *ds, LaunchScratch *sc, TraceParams &
 	hp.image_w = p.image_w;
 	hp.blocks_per_row = p.image_w >> 6;
 	hp.bpr_magic = (uint32_t)((0x100000000ull + hp.blocks_per_row - 1u) / hp.blocks_per_row);
-	hp.bound_abs = ds->bound_abs > 1.0f ? ds->bound_abs : 1.0f;
+	hp.bound_abs = ds->tree.bound_abs > 1.0f ? ds->tree.bound_abs : 1.0f;
 	hp.entries = p.entries;
 	const int rc = rtk_packet_module().launch(ds->device, (int)plan.kernel, &hp, sizeof(hp), (unsigned)plan.hot_grid, stream);
 	if (rc != RTK_AMD_OK) return rc;
@@ -1208,7 +1208,7 @@ int enqueue_lane_hot(const rtk_dev_scene *ds, LaunchScratch *sc, const TracePara
 	// (re-swept for these kernels: refill at 16 idle lanes instead of 8 is +1 % / +2 %, profiles/r04_lane_sweep.log)
 	hp.refill_min = refill_given ? p.refill_min : 16u;
 	hp.node_exit = p.node_exit;
-	hp.bound_abs = ds->bound_raw;             // (no floor of 1: these kernels test child words, not inverted boxes)
+	hp.bound_abs = ds->tree.bound_raw;             // (no floor of 1: these kernels test child words, not inverted boxes)
 	hp.spill = p.spill;
 	hp.spill_stride = p.spill_stride;
 	hp.spill_cap = p.spill_cap;
@@ -1303,7 +1303,7 @@ int rtk_launch_trace(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, size_t n,
 	rq.filtered = p.mesh_mask || p.ignore_prim || p.after; rq.has_filter = filter != nullptr;
 	SceneFacts facts;
 	facts.num_nodes = ds->view.num_nodes; facts.num_tris = ds->view.num_tris; facts.has_qnodes = ds->view.qnodes != nullptr;
-	facts.stack_entries = ds->stack_entries; facts.bound_abs = ds->bound_abs; facts.big_leaf_fraction = ds->big_leaf_fraction;
+	facts.stack_entries = ds->tree.stack_entries(); facts.bound_abs = ds->tree.bound_abs; facts.big_leaf_fraction = ds->tree.big_leaf_fraction;
 	facts.num_cus = ds->num_cus; facts.tri_stride = RTK_TRI_STRIDE;
 	uint32_t look_w = 0, look_h = 0;
 	if (wants_image_look(rq, o, facts, knobs)) {
@@ -1338,7 +1338,7 @@ int rtk_launch_trace(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, size_t n,
 	// kernel clears them itself: a 4.6 us fill kernel and its launch gap less per frame.)
 	if ((plan.dynamic || plan.packet || counted) && !plan.entries) RTK_HIP_CHECK(hipMemsetAsync(sc->d_counter, 0, RTK_COUNTER_WORDS * sizeof(unsigned long long), stream), RTK_AMD_ERR_HIP);
 	if (plan.entries) {
-		rtk_packet_entries_launch(p, (PkBlockEntries *)sc->d_entries, ds->bound_abs > 1.0f ? ds->bound_abs : 1.0f, knobs.entry_target, knobs.entry_levels, stream);
+		rtk_packet_entries_launch(p, (PkBlockEntries *)sc->d_entries, ds->tree.bound_abs > 1.0f ? ds->tree.bound_abs : 1.0f, knobs.entry_target, knobs.entry_levels, stream);
 		p.entries = (const PkBlockEntries *)sc->d_entries;
 	}
 	if (plan.hot) rc = enqueue_packet_hot(ds, sc, p, plan, any_hit, pk_counted != nullptr, stream);

@@ -216,8 +216,7 @@ rtk_dev_scene *rtk_dev_scene_from_host_bvh(const HostBvh &h)
 	}
 	ds->num_cus = prop.multiProcessorCount;
 	ds->mesh_base = h.mesh_base;
-	ds->max_depth = h.max_depth;
-	ds->stack_entries = 3u * h.max_depth + 1u;   // at most three pushes per level of descent
+	ds->tree.max_depth = h.max_depth;
 
 	std::vector<uint32_t> prim_slot(h.mesh_base.empty() ? 0 : (size_t)h.mesh_base.back(), 0xffffffffu);
 	for (size_t s = 0; s < h.tris.size(); s++) if (h.tris[s].prim < prim_slot.size()) prim_slot[h.tris[s].prim] = (uint32_t)s;
@@ -248,7 +247,7 @@ rtk_dev_scene *rtk_dev_scene_from_host_bvh(const HostBvh &h)
 	// leaves of more than three triangles (the assembly packet kernel hands tiles that meet one to the C++ kernel)
 	size_t leaves = 0, big = 0;
 	for (const DevTri &t : h.tris) if (t.spare != 0u) { leaves++; if (t.spare > 3u) big++; }
-	ds->big_leaf_fraction = leaves ? (double)big / (double)leaves : 0.0;
+	ds->tree.big_leaf_fraction = leaves ? (double)big / (double)leaves : 0.0;
 	if (rtk_quantize_nodes(ds, 0, nullptr, nullptr, bound) != RTK_AMD_OK || hipStreamSynchronize(0) != hipSuccess) {
 		rtk_dev_scene_free(ds);
 		return nullptr;

@@ -167,7 +167,7 @@ extern "C" int rtk_dev_scene_validate(const rtk_dev_scene *ds, rtk_dev_scene_che
 		h[C_FIRST_BAD] = ~0ull;
 		if (hipMemset(d_seen, 0, words * 4) != hipSuccess || hipMemcpy(d_c, h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess) { rc = RTK_AMD_ERR_HIP; break; }
 		uint32_t *slot_seen = d_seen, *node_seen = d_seen + v.num_tris, *prim_seen = node_seen + v.num_nodes;
-		hipLaunchKernelGGL(k_check_nodes, dim3((v.num_nodes + 127u) / 128u), dim3(128), 0, 0, v, ds->first_top, ds->first_split, slot_seen, node_seen, d_c);
+		hipLaunchKernelGGL(k_check_nodes, dim3((v.num_nodes + 127u) / 128u), dim3(128), 0, 0, v, ds->tree.first_top, ds->tree.first_split, slot_seen, node_seen, d_c);
 		if (v.num_tris) hipLaunchKernelGGL(k_check_slots, dim3((v.num_tris + 255u) / 256u), dim3(256), 0, 0, v, slot_seen, prim_seen, d_c);
 		const uint32_t m = v.num_nodes > v.num_prims ? v.num_nodes : v.num_prims;
 		// a scene built here holds every primitive of its meshes; an uploaded blob may leave ids unused
