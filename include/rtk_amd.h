@@ -172,6 +172,42 @@ double rtk_dev_scene_last_refit_ms(const rtk_dev_scene *ds);
 int rtk_dev_scene_refit_meshes(rtk_dev_scene *ds, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids, void *stream);
 uint64_t rtk_dev_scene_last_refit_nodes(const rtk_dev_scene *ds);
 
+/* PLACED meshes: the description holds every mesh in its rest pose, and a 3 x 4 matrix per mesh says where it stands. What a
+ * host of rigid bodies has (one vertex buffer per mesh, one matrix per mesh and frame), and what an instance is: two meshes
+ * may name the same position and index buffers with different placements. rtk_mesh has the reference's 96 bytes and no room
+ * for a matrix, so the placements come in beside the description: host memory, desc->num_meshes entries, indexed by mesh
+ * number; rtk_dev_scene_refit_meshes_placed reads only the listed entries.
+ *   - THE RULE: m[0..11] row by row; the vertex is made float as an unplaced call makes it ((float) of a double), then
+ *         x' = ((m0*x + m1*y) + m2*z) + m3,  y' = ((m4*x + m5*y) + m6*z) + m7,  z' = ((m8*x + m9*y) + m10*z) + m11
+ *     with every product and every sum rounded to float on its own, in this order, never fused: numpy float32 arithmetic.
+ *     Denormals are kept. The identity is not a bit-for-bit no-op (-0 becomes +0, 0 * inf is NaN); of a NaN result only
+ *     that it is one is promised. rtk_amd/csrc/rtk_place_rule.h is the rule, for the host and the device.
+ *   - RESULT: each call leaves the scene bit for bit as its unplaced sibling (rtk_dev_scene_build, _refit, _refit_meshes)
+ *     would, given a twin description in which every mesh has tightly packed F32 positions equal to the rule applied to
+ *     every vertex of that mesh, with the same index buffers and triangle counts: content_hash,
+ *     rtk_dev_scene_primitive_order, the exported blob, every field of rtk_dev_scene_info except build_ms (so
+ *     total_device_bytes too), last_refit_nodes, the choice between exact and compressed nodes and the narrow-key rule of
+ *     the build are the twin's.
+ *   - INPUTS: whatever the sibling accepts for positions and indices: F32 / F64 / REAL / DEFAULT positions, strides, host
+ *     or device memory, u16 / u32 / implicit indices, index_cb where the build accepts it. Host-resident positions are
+ *     staged as they are and placed on the device.
+ *   - rtk_hit.mesh_index, triangle_index and vertex[].index are those of the mesh ENTRY (of the instance, not of whoever
+ *     else shares its buffers); vertex[].position is the placed position the scene holds.
+ *   - NOTHING IS REMEMBERED: the scene keeps no placement. A later rtk_dev_scene_refit takes its positions as given;
+ *     rtk_dev_scene_rebuild, _export, _quality, _split_leaves and _validate work on the records as always. The unplaced
+ *     calls allocate and count what they always did.
+ *   - RTK_AMD_ERR_BAD_ARG (the build: NULL) for placements == NULL and for everything the sibling refuses;
+ *     RTK_AMD_ERR_UNSUPPORTED (the build: NULL) for a mesh that is read and has position_cb set: a callback produces world
+ *     positions already. Every refusal is decided before anything is launched and leaves the scene alone.
+ *   - rtk_dev_scene_refit_meshes_placed keeps the quarter crossover, the rule for an uploaded blob's first refit and the
+ *     num_ids == 0 no-op of rtk_dev_scene_refit_meshes. Locks, synchrony, rtk_dev_scene_last_refit_ms and
+ *     rtk_dev_scene_last_refit_nodes are the siblings'. */
+typedef struct rtk_placement { float m[12]; } rtk_placement;
+rtk_dev_scene *rtk_dev_scene_build_placed(const rtk_scene_desc *desc, const rtk_placement *placements);
+int rtk_dev_scene_refit_placed(rtk_dev_scene *ds, const rtk_scene_desc *desc, const rtk_placement *placements, void *stream);
+int rtk_dev_scene_refit_meshes_placed(rtk_dev_scene *ds, const rtk_scene_desc *desc, const rtk_placement *placements,
+                                      const uint32_t *mesh_ids, size_t num_ids, void *stream);
+
 /* How good the tree is NOW: the surface-area-heuristic cost of the scene's exact child boxes, measured on the device. What
  * a host that refits every frame asks to learn that a rebuild pays: measure once after rtk_dev_scene_build (or an upload),
  * refit, measure again every frame or every few, and rebuild when sah_cost has grown past a ratio of the host's choosing.
@@ -430,6 +466,11 @@ int rtk_mgpu_build(rtk_mgpu *m, const rtk_scene_desc *desc);      /* rtk_dev_sce
 int rtk_mgpu_upload(rtk_mgpu *m, const rtk_scene *scene);         /* rtk_dev_scene_upload on every GPU */
 int rtk_mgpu_refit(rtk_mgpu *m, const rtk_scene_desc *desc);      /* rtk_dev_scene_refit on every GPU of the context (handles stay valid) */
 int rtk_mgpu_refit_meshes(rtk_mgpu *m, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids);   /* rtk_dev_scene_refit_meshes on every GPU */
+/* the placed forms (rtk_placement above) on every GPU: the same placements for every replica, which agree afterwards */
+int rtk_mgpu_build_placed(rtk_mgpu *m, const rtk_scene_desc *desc, const rtk_placement *placements);
+int rtk_mgpu_refit_placed(rtk_mgpu *m, const rtk_scene_desc *desc, const rtk_placement *placements);
+int rtk_mgpu_refit_meshes_placed(rtk_mgpu *m, const rtk_scene_desc *desc, const rtk_placement *placements,
+                                 const uint32_t *mesh_ids, size_t num_ids);
 int rtk_mgpu_split_leaves(rtk_mgpu *m, uint32_t max_leaf);        /* rtk_dev_scene_split_leaves on every GPU of the context (handles stay valid) */
 int rtk_mgpu_rebuild(rtk_mgpu *m);   /* on every GPU of the context; rtk_mgpu_scene handles stay valid */
 /* host rays in, host records out (records[i] belongs to rays[i]) */

@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from .types import (HIT_DTYPE, HIT_RECORD_DTYPE, RAY_DTYPE, MeshSet, SceneDesc, SceneHeader)
+from .types import (HIT_DTYPE, HIT_RECORD_DTYPE, RAY_DTYPE, MeshSet, Placement, SceneDesc, SceneHeader, placement_array)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RTK_AMD_LIB") or os.path.join(HERE, "librtk_amd.so")   # RTK_AMD_LIB: kernel A/B builds only
@@ -127,7 +127,9 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_dev_scene_refit", "rtk_dev_scene_last_refit_ms", "rtk_mgpu_refit",
                      "rtk_dev_scene_refit_meshes", "rtk_dev_scene_last_refit_nodes", "rtk_mgpu_refit_meshes",
                      "rtk_dev_scene_quality", "rtk_dev_scene_split_leaves", "rtk_mgpu_split_leaves",
-                     "rtk_dev_scene_rebuild", "rtk_mgpu_rebuild"]
+                     "rtk_dev_scene_rebuild", "rtk_mgpu_rebuild",
+                     "rtk_dev_scene_build_placed", "rtk_dev_scene_refit_placed", "rtk_dev_scene_refit_meshes_placed",
+                     "rtk_mgpu_build_placed", "rtk_mgpu_refit_placed", "rtk_mgpu_refit_meshes_placed"]
 
 _lib = None
 
@@ -214,6 +216,18 @@ def lib():
     L.rtk_mgpu_rebuild.argtypes = [C.c_void_p]
     L.rtk_mgpu_refit_meshes.restype = C.c_int
     L.rtk_mgpu_refit_meshes.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(C.c_uint32), C.c_size_t]
+    L.rtk_dev_scene_build_placed.restype = C.c_void_p
+    L.rtk_dev_scene_build_placed.argtypes = [C.POINTER(SceneDesc), C.POINTER(Placement)]
+    L.rtk_dev_scene_refit_placed.restype = C.c_int
+    L.rtk_dev_scene_refit_placed.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(Placement), C.c_void_p]
+    L.rtk_dev_scene_refit_meshes_placed.restype = C.c_int
+    L.rtk_dev_scene_refit_meshes_placed.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(Placement), C.POINTER(C.c_uint32), C.c_size_t, C.c_void_p]
+    L.rtk_mgpu_build_placed.restype = C.c_int
+    L.rtk_mgpu_build_placed.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(Placement)]
+    L.rtk_mgpu_refit_placed.restype = C.c_int
+    L.rtk_mgpu_refit_placed.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(Placement)]
+    L.rtk_mgpu_refit_meshes_placed.restype = C.c_int
+    L.rtk_mgpu_refit_meshes_placed.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(Placement), C.POINTER(C.c_uint32), C.c_size_t]
     L.rtk_mgpu_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(TraceOpts)]
     L.rtk_mgpu_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(TraceOpts)]
     L.rtk_mgpu_trace_rays_device_striped.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TraceOpts)]
@@ -306,6 +320,12 @@ def mesh_set_of_some(meshes, mesh_base):
     return ms
 
 
+def placement_ptr(placements, num_meshes):
+    """(rtk_placement pointer, the array it points into) for array-like placements of shape (num_meshes, 3, 4) or (num_meshes, 12)."""
+    a = placement_array(placements, num_meshes)
+    return a.ctypes.data_as(C.POINTER(Placement)), a
+
+
 class DeviceScene:
     """A device-resident scene (rtk_dev_scene*)."""
 
@@ -326,26 +346,42 @@ class DeviceScene:
         return cls(lib().rtk_dev_scene_upload_buffer(C.c_void_p(arr.ctypes.data), arr.size), arr)
 
     @classmethod
-    def build(cls, meshes):
-        """Device LBVH build from mesh dicts (see rtk_amd.types.MeshSet)."""
+    def build(cls, meshes, placements=None):
+        """Device LBVH build from mesh dicts (see rtk_amd.types.MeshSet). placements: one 3 x 4 matrix per mesh, array-like
+        (num_meshes, 3, 4) or (num_meshes, 12) float32 -- the meshes are in their rest pose and every vertex is moved by
+        its mesh's matrix as it is read (rtk_dev_scene_build_placed); two meshes may share buffers (instances)."""
         _torch()
         ms = meshes if isinstance(meshes, MeshSet) else MeshSet(meshes)
-        return cls(lib().rtk_dev_scene_build(C.byref(ms.desc)), ms)
+        if placements is None:
+            return cls(lib().rtk_dev_scene_build(C.byref(ms.desc)), ms)
+        ptr, _keep = placement_ptr(placements, int(ms.desc.num_meshes))
+        return cls(lib().rtk_dev_scene_build_placed(C.byref(ms.desc), ptr), ms)
 
-    def refit(self, meshes, only=None):
+    def refit(self, meshes, only=None, placements=None):
         """New vertex positions for the same triangles, in place (rtk_dev_scene_refit): meshes as for build(); only the
         positions are read. Synchronous; the scene must not be traced from another stream or thread meanwhile.
         only: a list of mesh indices (rtk_dev_scene_refit_meshes) -- just those meshes are read and moved, at a cost that
-        follows them; the entries of `meshes` that are not listed may be None."""
+        follows them; the entries of `meshes` that are not listed may be None.
+        placements: as for build() (rtk_dev_scene_refit_placed / rtk_dev_scene_refit_meshes_placed): one matrix per mesh of
+        the scene, of which only those of the meshes that are read count."""
         _torch()
         if only is None:
             ms = meshes if isinstance(meshes, MeshSet) else MeshSet(meshes)
-            _check(lib().rtk_dev_scene_refit(self.handle, C.byref(ms.desc), _stream_ptr()), "rtk_dev_scene_refit")
+            if placements is None:
+                _check(lib().rtk_dev_scene_refit(self.handle, C.byref(ms.desc), _stream_ptr()), "rtk_dev_scene_refit")
+                return
+            ptr, _keep = placement_ptr(placements, int(ms.desc.num_meshes))
+            _check(lib().rtk_dev_scene_refit_placed(self.handle, C.byref(ms.desc), ptr, _stream_ptr()), "rtk_dev_scene_refit_placed")
             return
         ms = meshes if isinstance(meshes, MeshSet) else mesh_set_of_some(meshes, self.mesh_base())
         ids = np.ascontiguousarray(only, np.uint32).reshape(-1)
-        _check(lib().rtk_dev_scene_refit_meshes(self.handle, C.byref(ms.desc), ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids.size else None,
-                                                ids.size, _stream_ptr()), "rtk_dev_scene_refit_meshes")
+        id_ptr = ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids.size else None
+        if placements is None:
+            _check(lib().rtk_dev_scene_refit_meshes(self.handle, C.byref(ms.desc), id_ptr, ids.size, _stream_ptr()), "rtk_dev_scene_refit_meshes")
+            return
+        ptr, _keep = placement_ptr(placements, int(ms.desc.num_meshes))
+        _check(lib().rtk_dev_scene_refit_meshes_placed(self.handle, C.byref(ms.desc), ptr, id_ptr, ids.size, _stream_ptr()),
+               "rtk_dev_scene_refit_meshes_placed")
 
     def last_refit_ms(self):
         return float(lib().rtk_dev_scene_last_refit_ms(self.handle))

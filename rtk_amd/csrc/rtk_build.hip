@@ -20,6 +20,7 @@
 #include "rtk_dev.h"
 #include "rtk_build_layout.h"
 #include "rtk_node_finish.h"
+#include "rtk_place_rule.h"
 
 #include <limits.h>
 #include <math.h>
@@ -86,10 +87,14 @@ __device__ __forceinline__ float ord2f(uint32_t u)
 // straight from the caller's (or the uploaded) position buffer. Every form writes the doubled centroid (12 B: all k_morton
 // needs; it used to read the whole 48-byte staged record for it) and, if the scene keeps them (vidx_in: some mesh is indexed),
 // the original vertex indices in input order.
-template <int IDX, bool F64, bool DIRECT>
+// PLACED (rtk_dev_scene_build_placed): every vertex goes through the mesh's placement (rtk_place_rule.h) as soon as it is a
+// float, so the staged record, the centroid and the bounds are those of the placed mesh. Never together with DIRECT: the emit
+// would have to place the vertices a second time, so a placed mesh is always staged.
+template <int IDX, bool F64, bool DIRECT, bool PLACED>
 __global__ void __launch_bounds__(INGEST_BLOCK) k_ingest(const char *pos, unsigned long long pos_stride, const char *idx,
-	unsigned long long idx_stride, uint32_t ntris, uint32_t base, InTri *in_tris, float *cent, uint32_t *vidx_in, uint32_t *bounds)
+	unsigned long long idx_stride, uint32_t ntris, uint32_t base, InTri *in_tris, float *cent, uint32_t *vidx_in, uint32_t *bounds, rtk_placement place)
 {
+	static_assert(!(DIRECT && PLACED), "a placed mesh is staged");
 	__shared__ float s_mn[3][INGEST_BLOCK / 64], s_mx[3][INGEST_BLOCK / 64];
 	float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
 	for (uint32_t i = blockIdx.x * INGEST_BLOCK + threadIdx.x; i < ntris; i += gridDim.x * INGEST_BLOCK) {
@@ -116,6 +121,7 @@ __global__ void __launch_bounds__(INGEST_BLOCK) k_ingest(const char *pos, unsign
 				const float *p = reinterpret_cast<const float *>(pos + (size_t)vi[c] * pos_stride);
 				x = p[0]; y = p[1]; z = p[2];
 			}
+			if (PLACED) rtk_place_vertex(place.m, x, y, z);
 			rec.p[3 * c + 0] = x;
 			rec.p[3 * c + 1] = y;
 			rec.p[3 * c + 2] = z;
@@ -155,13 +161,19 @@ __global__ void __launch_bounds__(INGEST_BLOCK) k_ingest(const char *pos, unsign
 	}
 }
 
+// place: the mesh's placement, or NULL (never with `direct`)
 template <int IDX>
-void launch_ingest(bool f64, bool direct, unsigned blocks, const char *pos, unsigned long long pstride, const char *idx,
+void launch_ingest(bool f64, bool direct, const rtk_placement *place, unsigned blocks, const char *pos, unsigned long long pstride, const char *idx,
 	unsigned long long istride, uint32_t nt, uint32_t base, InTri *in_tris, float *cent, uint32_t *vidx_in, uint32_t *bounds, hipStream_t stream)
 {
-	if (direct) hipLaunchKernelGGL((k_ingest<0, false, true>), dim3(blocks), dim3(INGEST_BLOCK), 0, stream, pos, pstride, idx, istride, nt, base, in_tris, cent, vidx_in, bounds);
-	else if (f64) hipLaunchKernelGGL((k_ingest<IDX, true, false>), dim3(blocks), dim3(INGEST_BLOCK), 0, stream, pos, pstride, idx, istride, nt, base, in_tris, cent, vidx_in, bounds);
-	else hipLaunchKernelGGL((k_ingest<IDX, false, false>), dim3(blocks), dim3(INGEST_BLOCK), 0, stream, pos, pstride, idx, istride, nt, base, in_tris, cent, vidx_in, bounds);
+	const rtk_placement pl = place ? *place : rtk_placement{};
+#define INGEST_LAUNCH(...) hipLaunchKernelGGL((k_ingest<__VA_ARGS__>), dim3(blocks), dim3(INGEST_BLOCK), 0, stream, pos, pstride, idx, istride, nt, base, in_tris, cent, vidx_in, bounds, pl)
+	if (place && f64) INGEST_LAUNCH(IDX, true, false, true);
+	else if (place) INGEST_LAUNCH(IDX, false, false, true);
+	else if (direct) INGEST_LAUNCH(0, false, true, false);
+	else if (f64) INGEST_LAUNCH(IDX, true, false, false);
+	else INGEST_LAUNCH(IDX, false, false, false);
+#undef INGEST_LAUNCH
 }
 
 // ---------------------------------------------------------------------------------- 2 bounds
@@ -1569,8 +1581,14 @@ hipError_t upload_staged(void *dst, const void *src, size_t bytes, hipStream_t s
 	return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream);
 }
 
+// the decoded corners of a mesh (pos9: 9 floats per triangle) under its placement: the host's side of rtk_place_rule.h
+void place_on_host(const rtk_placement &pl, float *pos9, size_t num_triangles)
+{
+	for (size_t v = 0; v < 3 * num_triangles; v++) rtk_place_vertex(pl.m, pos9[3 * v], pos9[3 * v + 1], pos9[3 * v + 2]);
+}
+
 // ---- fewer than two triangles: no radix tree to build, no workspace; one root node, at most one leaf ----
-rtk_dev_scene *build_tiny(const rtk_scene_desc *desc, const std::vector<uint64_t> &mesh_base)
+rtk_dev_scene *build_tiny(const rtk_scene_desc *desc, const std::vector<uint64_t> &mesh_base, const rtk_placement *placements)
 {
 	std::vector<float> pos;
 	std::vector<uint32_t> vidx;
@@ -1580,6 +1598,7 @@ rtk_dev_scene *build_tiny(const rtk_scene_desc *desc, const std::vector<uint64_t
 		pos.resize(9 * m->num_triangles);
 		vidx.resize(3 * m->num_triangles);
 		decode_mesh_on_host(m, pos.data(), vidx.data());
+		if (placements) place_on_host(placements[mi], pos.data(), m->num_triangles);
 	}
 	HostBvh h;
 	h.mesh_base = mesh_base;
@@ -1823,6 +1842,7 @@ struct Build {
 	// where the triangles come from: a description (rtk_dev_scene_build), or the records of a live scene (rtk_dev_scene_rebuild).
 	// Only plan_meshes and the two ingests look at it; from there on a build knows the number of meshes and mesh_base.
 	const rtk_scene_desc *desc = nullptr;
+	const rtk_placement *placements = nullptr;   // rtk_dev_scene_build_placed: one per mesh of desc (host memory), else NULL
 	const rtk_dev_scene *from = nullptr;
 	size_t num_meshes = 0;
 	int rc = RTK_AMD_ERR_HIP;         // what a failed build reports where a code is wanted (the rebuild): set by whoever returns false
@@ -1941,6 +1961,7 @@ bool plan_meshes(Build &b)
 		// RTK_TYPE_DEFAULT on an index buffer means 32-bit indices (the reference's default index type, rtk.c:1049-1059)
 		if (!m->index_cb && m->index.data && m->index.type != RTK_TYPE_DEFAULT && m->index.type != RTK_TYPE_U16 && m->index.type != RTK_TYPE_U32) {
 			rtk_set_error("rtk_dev_scene_build: mesh %zu: bad index type %d", mi, (int)m->index.type); return false; }
+		if (b.placements && m->position_cb) { b.rc = RTK_AMD_ERR_UNSUPPORTED; rtk_set_error("rtk_dev_scene_build_placed: mesh %zu: a position callback gives world positions, it takes no placement", mi); return false; }
 		if (m->position_cb || m->index_cb || b.n < 2) { pl.on_host_decode = true; continue; }
 		if (!m->position.data) { rtk_set_error("rtk_dev_scene_build: mesh %zu has no positions", mi); return false; }
 		pl.f64 = m->position.type == RTK_TYPE_F64;
@@ -2070,6 +2091,7 @@ bool ingest(Build &b)
 			std::vector<float> pos9(9 * nt);
 			std::vector<uint32_t> vidx3(3 * nt);
 			decode_mesh_on_host(m, pos9.data(), vidx3.data());
+			if (b.placements) place_on_host(b.placements[mi], pos9.data(), nt);
 			std::vector<InTri> recs(nt);
 			for (size_t t = 0; t < nt; t++) {
 				for (int c = 0; c < 9; c++) recs[t].p[c] = pos9[9 * t + c];
@@ -2095,12 +2117,14 @@ bool ingest(Build &b)
 			pos_ptr = d;
 		}
 		// implicit indices and float positions whose three components can be read as floats in place: gathered in place by k_emit_tris
-		const bool direct = b.knobs.direct && pl.idx_kind == 0 && !pl.f64 && (pl.pstride % 4u) == 0u && ((uintptr_t)pos_ptr % 4u) == 0u;
+		// (not a placed mesh: its vertices are placed once, here, and staged)
+		const rtk_placement *place = b.placements ? &b.placements[mi] : nullptr;
+		const bool direct = !place && b.knobs.direct && pl.idx_kind == 0 && !pl.f64 && (pl.pstride % 4u) == 0u && ((uintptr_t)pos_ptr % 4u) == 0u;
 		if (direct) b.mesh_src[mi] = MeshSrc{ pos_ptr, (unsigned long long)pl.pstride };
 		const unsigned iblocks = (unsigned)std::min<size_t>((nt + INGEST_BLOCK - 1) / INGEST_BLOCK, (size_t)b.num_cus);
-		if (pl.idx_kind == 0) launch_ingest<0>(pl.f64, direct, iblocks, pos_ptr, pl.pstride, idx_ptr, pl.istride, (uint32_t)nt, base, b.in_tris, b.d_cent, b.d_vidx_in, b.d_bounds, bs);
-		else if (pl.idx_kind == 1) launch_ingest<1>(pl.f64, false, iblocks, pos_ptr, pl.pstride, idx_ptr, pl.istride, (uint32_t)nt, base, b.in_tris, b.d_cent, b.d_vidx_in, b.d_bounds, bs);
-		else launch_ingest<2>(pl.f64, false, iblocks, pos_ptr, pl.pstride, idx_ptr, pl.istride, (uint32_t)nt, base, b.in_tris, b.d_cent, b.d_vidx_in, b.d_bounds, bs);
+		if (pl.idx_kind == 0) launch_ingest<0>(pl.f64, direct, place, iblocks, pos_ptr, pl.pstride, idx_ptr, pl.istride, (uint32_t)nt, base, b.in_tris, b.d_cent, b.d_vidx_in, b.d_bounds, bs);
+		else if (pl.idx_kind == 1) launch_ingest<1>(pl.f64, false, place, iblocks, pos_ptr, pl.pstride, idx_ptr, pl.istride, (uint32_t)nt, base, b.in_tris, b.d_cent, b.d_vidx_in, b.d_bounds, bs);
+		else launch_ingest<2>(pl.f64, false, place, iblocks, pos_ptr, pl.pstride, idx_ptr, pl.istride, (uint32_t)nt, base, b.in_tris, b.d_cent, b.d_vidx_in, b.d_bounds, bs);
 		if (hipGetLastError() != hipSuccess) return b.fail("ingest launch");
 	}
 	b.stage("ingest");
@@ -2436,12 +2460,13 @@ rtk_dev_scene *run_stages(Build &b, uint32_t force_bits, bool *narrow_key)
 	return b.ds;
 }
 
-rtk_dev_scene *build_impl(const rtk_scene_desc *desc, const BuildKnobs &knobs, uint32_t force_bits, bool *narrow_key)
+rtk_dev_scene *build_impl(const rtk_scene_desc *desc, const rtk_placement *placements, const BuildKnobs &knobs, uint32_t force_bits, bool *narrow_key)
 {
 	*narrow_key = false;
 	if (!desc || (!desc->meshes && desc->num_meshes)) { rtk_set_error("rtk_dev_scene_build: NULL scene description"); return nullptr; }
 	Build b;
 	b.desc = desc;
+	b.placements = placements;
 	b.num_meshes = desc->num_meshes;
 	b.knobs = knobs;
 	b.mesh_base.assign(desc->num_meshes + 1, 0);
@@ -2455,7 +2480,7 @@ rtk_dev_scene *build_impl(const rtk_scene_desc *desc, const BuildKnobs &knobs, u
 	if (b.device < 0 || b.device >= RTK_MAX_DEVICES) { rtk_set_error("rtk_dev_scene_build: device %d out of range", b.device); return nullptr; }
 	b.num_cus = cached_cu_count(b.device);
 	if (!plan_meshes(b)) return nullptr;
-	if (b.n < 2) return build_tiny(desc, b.mesh_base);
+	if (b.n < 2) return build_tiny(desc, b.mesh_base, placements);
 	return run_stages(b, force_bits, narrow_key);
 }
 
@@ -2488,17 +2513,32 @@ rtk_dev_scene *rebuild_impl(const rtk_dev_scene *from, const BuildKnobs &knobs, 
 // cannot repair that topology. k_refit_tile counts the sorted neighbours with equal codes while it builds the
 // tree; if more than an eighth of them are equal the scene is built once more with the full 40 bits: twice the time for such a
 // scene, the same tree quality as before the narrow keys, nothing for scenes that do not need it.
-extern "C" rtk_dev_scene *rtk_dev_scene_build(const rtk_scene_desc *desc)
+// placements: NULL (rtk_dev_scene_build), or one per mesh (rtk_dev_scene_build_placed)
+static rtk_dev_scene *build_with_key_rule(const rtk_scene_desc *desc, const rtk_placement *placements)
 {
 	const BuildKnobs knobs = read_build_knobs();
 	bool narrow = false;
-	rtk_dev_scene *ds = build_impl(desc, knobs, 0u, &narrow);
+	rtk_dev_scene *ds = build_impl(desc, placements, knobs, 0u, &narrow);
 	if (!ds || !narrow || !knobs.key_rebuild) return ds;
 	const double first_ms = ds->build_ms;
 	rtk_dev_scene_free(ds);
-	ds = build_impl(desc, knobs, 40u, &narrow);
+	ds = build_impl(desc, placements, knobs, 40u, &narrow);
 	if (ds) ds->build_ms += first_ms;
 	return ds;
+}
+
+extern "C" rtk_dev_scene *rtk_dev_scene_build(const rtk_scene_desc *desc)
+{
+	return build_with_key_rule(desc, nullptr);
+}
+
+// The same build over placed meshes (rtk_amd.h has the contract, DESIGN.md 3.4e the reasons): the placement is applied where a
+// vertex is first read -- k_ingest, or the host's decode of an index_cb mesh and of a scene of fewer than two triangles -- and
+// nothing behind the ingest knows of it.
+extern "C" rtk_dev_scene *rtk_dev_scene_build_placed(const rtk_scene_desc *desc, const rtk_placement *placements)
+{
+	if (!placements) { rtk_set_error("rtk_dev_scene_build_placed: NULL placements"); return nullptr; }
+	return build_with_key_rule(desc, placements);
 }
 
 // rtk_dev_scene_rebuild: the device builder's tree over the triangles a scene holds now, adopted by the live handle

@@ -145,13 +145,13 @@ static int for_each_slot_in_parallel(rtk_mgpu *m, F work)
 
 // the scene on every GPU of the context: each device builds (or uploads) its own replica on a host thread of its own, so
 // eight replicas take the time of one
-static int replicate(rtk_mgpu *m, const rtk_scene_desc *desc, const rtk_scene *blob)
+static int replicate(rtk_mgpu *m, const rtk_scene_desc *desc, const rtk_scene *blob, const rtk_placement *placements = nullptr)
 {
 	if (!m) { rtk_set_error("rtk_mgpu: NULL context"); return RTK_AMD_ERR_BAD_ARG; }
 	return for_each_slot_in_parallel(m, [&](size_t j) -> int {
 		DeviceSlot &s = m->slots[j];
 		if (s.scene) rtk_dev_scene_free(s.scene);
-		s.scene = desc ? rtk_dev_scene_build(desc) : rtk_dev_scene_upload(blob);
+		s.scene = !desc ? rtk_dev_scene_upload(blob) : placements ? rtk_dev_scene_build_placed(desc, placements) : rtk_dev_scene_build(desc);
 		return s.scene ? RTK_AMD_OK : RTK_AMD_ERR_HIP;
 	});
 }
@@ -160,6 +160,16 @@ extern "C" int rtk_mgpu_build(rtk_mgpu *m, const rtk_scene_desc *desc)
 {
 	if (!desc) { rtk_set_error("rtk_mgpu_build: NULL description"); return RTK_AMD_ERR_BAD_ARG; }
 	return replicate(m, desc, nullptr);
+}
+
+// rtk_dev_scene_build_placed on every GPU. The two refusals that have a code of their own are made here (a build returns a
+// scene or none); whatever else is wrong with the description every replica's build refuses.
+extern "C" int rtk_mgpu_build_placed(rtk_mgpu *m, const rtk_scene_desc *desc, const rtk_placement *placements)
+{
+	if (!desc || !placements) { rtk_set_error("rtk_mgpu_build_placed: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
+	for (size_t mi = 0; desc->meshes && mi < desc->num_meshes; mi++)
+		if (desc->meshes[mi].position_cb) { rtk_set_error("rtk_mgpu_build_placed: mesh %zu: a position callback gives world positions, it takes no placement", mi); return RTK_AMD_ERR_UNSUPPORTED; }
+	return replicate(m, desc, nullptr, placements);
 }
 
 extern "C" int rtk_mgpu_upload(rtk_mgpu *m, const rtk_scene *scene)
@@ -204,6 +214,20 @@ extern "C" int rtk_mgpu_refit_meshes(rtk_mgpu *m, const rtk_scene_desc *desc, co
 	if (!desc) { rtk_set_error("rtk_mgpu_refit_meshes: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
 	if (m && !mesh_ids && num_ids) { rtk_set_error("rtk_mgpu_refit_meshes: NULL mesh_ids with %zu ids", num_ids); return RTK_AMD_ERR_BAD_ARG; }
 	return on_every_replica(m, "rtk_mgpu_refit_meshes", [&](rtk_dev_scene *ds, hipStream_t st) { return rtk_dev_scene_refit_meshes(ds, desc, mesh_ids, num_ids, st); });
+}
+
+// the placed forms of both refits (rtk_dev_scene_refit_placed, rtk_dev_scene_refit_meshes_placed)
+extern "C" int rtk_mgpu_refit_placed(rtk_mgpu *m, const rtk_scene_desc *desc, const rtk_placement *placements)
+{
+	if (!desc || !placements) { rtk_set_error("rtk_mgpu_refit_placed: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
+	return on_every_replica(m, "rtk_mgpu_refit_placed", [&](rtk_dev_scene *ds, hipStream_t st) { return rtk_dev_scene_refit_placed(ds, desc, placements, st); });
+}
+
+extern "C" int rtk_mgpu_refit_meshes_placed(rtk_mgpu *m, const rtk_scene_desc *desc, const rtk_placement *placements, const uint32_t *mesh_ids, size_t num_ids)
+{
+	if (!desc || !placements) { rtk_set_error("rtk_mgpu_refit_meshes_placed: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
+	if (m && !mesh_ids && num_ids) { rtk_set_error("rtk_mgpu_refit_meshes_placed: NULL mesh_ids with %zu ids", num_ids); return RTK_AMD_ERR_BAD_ARG; }
+	return on_every_replica(m, "rtk_mgpu_refit_meshes_placed", [&](rtk_dev_scene *ds, hipStream_t st) { return rtk_dev_scene_refit_meshes_placed(ds, desc, placements, mesh_ids, num_ids, st); });
 }
 
 // Where stripe `stripe` of shard `shard` lies: records [*first, *first + *count) of the buffer of GPU `stripe` (stripes of a

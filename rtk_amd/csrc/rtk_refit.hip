@@ -20,6 +20,7 @@
 // A box is made by the validator's rule (rtk_validate.hip: fminf / fmaxf over the vertices of a leaf, over the non-empty
 // slots of an inner child), so after a refit every box is the exact union of what is below it.
 #include "rtk_dev.h"
+#include "rtk_place_rule.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -103,9 +104,14 @@ __global__ void k_refit_max_vertex(const uint32_t *vertex_index, const uint32_t 
 
 // MODE 0: every mesh has float positions, 1: every mesh doubles, 2: per mesh (RefitMesh::f64, a flag the host derived from
 // validated type codes). Doubles are converted as k_ingest converts them.
-template <int MODE>
-__device__ __forceinline__ void refit_tri(DevTri *tris, uint32_t s, const uint32_t *vertex_index, const RefitMesh &ms)
+// PLACED (the _placed entry points): place = the mesh's entry of a table beside `meshes`, applied to every vertex as soon as it
+// is a float (rtk_place_rule.h, as k_ingest does in a placed build). The table lives in the borrowed workspace for the length of
+// the call: the scene keeps no placement and allocates nothing for one.
+template <int MODE, bool PLACED>
+__device__ __forceinline__ void refit_tri(DevTri *tris, uint32_t s, const uint32_t *vertex_index, const RefitMesh &ms, const rtk_placement *place)
 {
+	rtk_placement pl;
+	if (PLACED) pl = *place;
 	const uint32_t vi[3] = { vertex_index[3 * (size_t)s], vertex_index[3 * (size_t)s + 1], vertex_index[3 * (size_t)s + 2] };
 	float p[3][3];
 	const bool f64 = MODE == 1 || (MODE == 2 && ms.f64 != 0u);
@@ -118,6 +124,7 @@ __device__ __forceinline__ void refit_tri(DevTri *tris, uint32_t s, const uint32
 			const float *q = reinterpret_cast<const float *>(ms.pos + (size_t)vi[c] * ms.stride);
 			p[c][0] = q[0]; p[c][1] = q[1]; p[c][2] = q[2];
 		}
+		if (PLACED) rtk_place_vertex(pl.m, p[c][0], p[c][1], p[c][2]);
 	}
 	// (the w lanes -- prim, flags, spare -- stay; a record is RTK_TRI_STRIDE bytes apart, 48 of them payload)
 	float4 *rec = reinterpret_cast<float4 *>(tris + s);
@@ -128,16 +135,16 @@ __device__ __forceinline__ void refit_tri(DevTri *tris, uint32_t s, const uint32
 	rec[0] = r0; rec[1] = r1; rec[2] = r2;
 }
 
-template <int MODE>
+template <int MODE, bool PLACED>
 __global__ void __launch_bounds__(256) k_refit_tris(DevTri *tris, uint32_t n, const uint32_t *vertex_index, const uint32_t *slot_mesh,
-	const RefitMesh *meshes, uint32_t num_meshes)
+	const RefitMesh *meshes, uint32_t num_meshes, const rtk_placement *places)
 {
 	const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
 	if (s >= n) return;
 	const uint32_t mesh = slot_mesh[s];
 	if (mesh >= num_meshes) return;
 	const RefitMesh ms = meshes[mesh];
-	refit_tri<MODE>(tris, s, vertex_index, ms);
+	refit_tri<MODE, PLACED>(tris, s, vertex_index, ms, PLACED ? places + mesh : nullptr);
 }
 
 // A run of listed meshes that are neighbours in mesh_slots: its entries from entry_begin on belong to the threads from
@@ -150,10 +157,10 @@ struct RefitRange { uint32_t entry_begin, thread_begin; };
 // parent of every marked node is marked when the launch ends). A stale read -- another CU's store not seen yet -- only means
 // climbing further. Nothing is handed from one workgroup to another inside the launch: the flags are read by LATER launches.
 // MARK false: the triangles only (the full box passes follow, which ask nobody what is dirty).
-template <int MODE, bool MARK>
+template <int MODE, bool MARK, bool PLACED>
 __global__ void __launch_bounds__(256) k_refit_tris_listed(DevTri *tris, uint32_t n, const uint32_t *vertex_index, const uint32_t *slot_mesh,
 	const RefitMesh *meshes, uint32_t num_meshes, const uint32_t *mesh_slots, const uint32_t *slot_node, const RefitRange *ranges, uint32_t num_ranges,
-	uint32_t total, const uint32_t *parent, uint32_t *dirty, uint32_t num_nodes, uint32_t epoch)
+	uint32_t total, const uint32_t *parent, uint32_t *dirty, uint32_t num_nodes, uint32_t epoch, const rtk_placement *places)
 {
 	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
 	uint32_t node = RTK_REF_NONE;
@@ -169,7 +176,7 @@ __global__ void __launch_bounds__(256) k_refit_tris_listed(DevTri *tris, uint32_
 		if (mesh < num_meshes) {
 			const RefitMesh ms = meshes[mesh];
 			if (ms.pos) {
-				refit_tri<MODE>(tris, s, vertex_index, ms);
+				refit_tri<MODE, PLACED>(tris, s, vertex_index, ms, PLACED ? places + mesh : nullptr);
 				if (MARK) node = slot_node[s];
 			}
 		}
@@ -579,8 +586,9 @@ double partial_max_share()
 }
 
 // everything behind the argument checks; the scene's device is current. listed: NULL = every mesh (rtk_dev_scene_refit), else
-// one flag per mesh (rtk_dev_scene_refit_meshes), with listed_tris triangles (not zero) in the flagged ones.
-int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t stream, WorkspaceLoan &loan, const uint8_t *listed, uint64_t listed_tris)
+// one flag per mesh (rtk_dev_scene_refit_meshes), with listed_tris triangles (not zero) in the flagged ones. placements: NULL, or
+// one per mesh (the _placed entry points; only the entries of meshes that are read are looked at).
+int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, const rtk_placement *placements, hipStream_t stream, WorkspaceLoan &loan, const uint8_t *listed, uint64_t listed_tris)
 {
 	int rc = rtk_scene_side_arrays(ds, stream);
 	if (rc != RTK_AMD_OK) return rc;
@@ -608,8 +616,15 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 		upload[mi] = (size_t)rs.max_vertex[mi] * t.stride + (t.f64 ? 24 : 12);
 		upload_bytes += rtk_padded(upload[mi]);
 	}
+	// the placements of the meshes that are read go to the device beside the staged positions (entries of other meshes: zeros)
+	std::vector<rtk_placement> places;
+	if (placements) {
+		places.assign(num_meshes ? num_meshes : 1, rtk_placement{});
+		for (size_t mi = 0; mi < num_meshes; mi++) if (table[mi].pos) places[mi] = placements[mi];
+		upload_bytes += rtk_padded(places.size() * sizeof(rtk_placement));
+	}
 	// the workspace: first the temporaries of the schedule (the first refit of a scene; over when make_schedule returns), then
-	// those of the per-mesh tables (the first refit of some meshes), then the staged positions
+	// those of the per-mesh tables (the first refit of some meshes), then the staged positions and placements
 	const size_t schedule_bytes = rs.ready ? 0 : schedule_tmp(ds->view.num_nodes).bytes;
 	const size_t tables_bytes = listed && !ds->partial.ready ? tables_tmp(v.num_tris).bytes : 0;
 	size_t borrow = schedule_bytes > upload_bytes ? schedule_bytes : upload_bytes;
@@ -621,6 +636,7 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 		rc = make_partial_tables(ds, stream, loan.base);
 		if (rc != RTK_AMD_OK) return rc;
 	}
+	const rtk_placement *d_places = nullptr;
 	if (upload_bytes) {
 		char *base = loan.base;
 		size_t off = 0;
@@ -629,6 +645,10 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 			RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(base + off, table[mi].pos, upload[mi], hipMemcpyHostToDevice, stream));
 			table[mi].pos = base + off;
 			off += rtk_padded(upload[mi]);
+		}
+		if (placements) {
+			RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(base + off, places.data(), places.size() * sizeof(rtk_placement), hipMemcpyHostToDevice, stream));
+			d_places = (const rtk_placement *)(base + off);
 		}
 	}
 	// a mesh in device memory was written by the caller's own work, possibly still in flight on the NULL stream (as in a build)
@@ -645,6 +665,7 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 	DevTri *tris = const_cast<DevTri *>(v.tris);
 	DevNode *nodes = const_cast<DevNode *>(v.nodes);
 	const RefitMesh *dm = (const RefitMesh *)rs.d_meshes;
+	const int mode = any_f64 && any_f32 ? 2 : any_f64 ? 1 : 0;
 	if (listed) {
 		RefitPartial &rp = ds->partial;
 		// runs of listed meshes that are neighbours in mesh_slots, one thread per slot
@@ -664,24 +685,24 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 		const uint32_t total = (uint32_t)threads;
 		const dim3 grid((total + 255u) / 256u), block(256);
 		const RefitRange *dr = (const RefitRange *)rp.d_ranges;
-#define LISTED_ARGS tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, (uint32_t)num_meshes, rp.d_mesh_slots, rp.d_slot_node, dr, (uint32_t)ranges.size(), total, rp.d_parent, rp.d_dirty, v.num_nodes, rp.epoch
-		const int mode = any_f64 && any_f32 ? 2 : any_f64 ? 1 : 0;
-		if (dirty_set) {
-			if (mode == 2) hipLaunchKernelGGL((k_refit_tris_listed<2, true>), grid, block, 0, stream, LISTED_ARGS);
-			else if (mode == 1) hipLaunchKernelGGL((k_refit_tris_listed<1, true>), grid, block, 0, stream, LISTED_ARGS);
-			else hipLaunchKernelGGL((k_refit_tris_listed<0, true>), grid, block, 0, stream, LISTED_ARGS);
-		} else {
-			if (mode == 2) hipLaunchKernelGGL((k_refit_tris_listed<2, false>), grid, block, 0, stream, LISTED_ARGS);
-			else if (mode == 1) hipLaunchKernelGGL((k_refit_tris_listed<1, false>), grid, block, 0, stream, LISTED_ARGS);
-			else hipLaunchKernelGGL((k_refit_tris_listed<0, false>), grid, block, 0, stream, LISTED_ARGS);
-		}
-#undef LISTED_ARGS
+		// (MODE and PLACED are compile-time variants: the unplaced instantiations are what they were before there were placements)
+#define LISTED_LAUNCH(MODE, MARK, PLACED) hipLaunchKernelGGL((k_refit_tris_listed<MODE, MARK, PLACED>), grid, block, 0, stream, tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, \
+	(uint32_t)num_meshes, rp.d_mesh_slots, rp.d_slot_node, dr, (uint32_t)ranges.size(), total, rp.d_parent, rp.d_dirty, v.num_nodes, rp.epoch, d_places)
+#define LISTED_MODES(MARK, PLACED) do { if (mode == 2) LISTED_LAUNCH(2, MARK, PLACED); else if (mode == 1) LISTED_LAUNCH(1, MARK, PLACED); else LISTED_LAUNCH(0, MARK, PLACED); } while (0)
+		if (dirty_set && d_places) LISTED_MODES(true, true);
+		else if (dirty_set) LISTED_MODES(true, false);
+		else if (d_places) LISTED_MODES(false, true);
+		else LISTED_MODES(false, false);
+#undef LISTED_MODES
+#undef LISTED_LAUNCH
 		RTK_PASS_CHECK("rtk_dev_scene_refit", hipGetLastError());
 	} else if (v.num_tris) {
 		const dim3 grid((v.num_tris + 255u) / 256u), block(256);
-		if (any_f64 && any_f32) hipLaunchKernelGGL((k_refit_tris<2>), grid, block, 0, stream, tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, (uint32_t)num_meshes);
-		else if (any_f64) hipLaunchKernelGGL((k_refit_tris<1>), grid, block, 0, stream, tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, (uint32_t)num_meshes);
-		else hipLaunchKernelGGL((k_refit_tris<0>), grid, block, 0, stream, tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, (uint32_t)num_meshes);
+#define TRIS_LAUNCH(MODE, PLACED) hipLaunchKernelGGL((k_refit_tris<MODE, PLACED>), grid, block, 0, stream, tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, (uint32_t)num_meshes, d_places)
+#define TRIS_MODES(PLACED) do { if (mode == 2) TRIS_LAUNCH(2, PLACED); else if (mode == 1) TRIS_LAUNCH(1, PLACED); else TRIS_LAUNCH(0, PLACED); } while (0)
+		if (d_places) TRIS_MODES(true); else TRIS_MODES(false);
+#undef TRIS_MODES
+#undef TRIS_LAUNCH
 		RTK_PASS_CHECK("rtk_dev_scene_refit", hipGetLastError());
 	}
 
@@ -758,12 +779,12 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, hipStream_t s
 }
 
 // what both entry points do once nothing can be refused any more
-int refit_in_pass(ScenePass &pass, const rtk_scene_desc *desc, const uint8_t *listed, uint64_t listed_tris)
+int refit_in_pass(ScenePass &pass, const rtk_scene_desc *desc, const rtk_placement *placements, const uint8_t *listed, uint64_t listed_tris)
 {
 	if (!pass.on_device()) return RTK_AMD_ERR_NO_DEVICE;
 	WorkspaceLoan loan;
 	// (a failed pass has waited for whatever reads the workspace before the loan ends; the time is taken after it has)
-	const int rc = pass.end(refit_on_device(pass.ds, desc, pass.stream, loan, listed, listed_tris));
+	const int rc = pass.end(refit_on_device(pass.ds, desc, placements, pass.stream, loan, listed, listed_tris));
 	loan.release();
 	if (rc == RTK_AMD_OK) pass.ds->refit_ms = pass.ms();
 	return rc;
@@ -820,25 +841,27 @@ void RefitPartial::reset(SceneMem &mem)
 	*this = RefitPartial();
 }
 
-extern "C" int rtk_dev_scene_refit(rtk_dev_scene *ds, const rtk_scene_desc *desc, void *stream)
+// Both full refits. who: the public function the error texts name; placements: NULL (rtk_dev_scene_refit) or one per mesh.
+static int refit_all(const char *who, rtk_dev_scene *ds, const rtk_scene_desc *desc, const rtk_placement *placements, bool placed, void *stream)
 {
 	// ---- everything that can be refused is refused here, before HIP is touched
-	if (!ds || !desc) { rtk_set_error("rtk_dev_scene_refit: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
-	int rc = check_desc("rtk_dev_scene_refit", ds, desc);
+	if (!ds || !desc || (placed && !placements)) { rtk_set_error("%s: NULL argument", who); return RTK_AMD_ERR_BAD_ARG; }
+	int rc = check_desc(who, ds, desc);
 	if (rc != RTK_AMD_OK) return rc;
 	for (size_t mi = 0; mi < desc->num_meshes; mi++) {
-		rc = check_mesh_positions("rtk_dev_scene_refit", &desc->meshes[mi], mi);
+		rc = check_mesh_positions(who, &desc->meshes[mi], mi);
 		if (rc != RTK_AMD_OK) return rc;
 	}
 	ScenePass pass(ds, stream);
-	return refit_in_pass(pass, desc, nullptr, 0);
+	return refit_in_pass(pass, desc, placements, nullptr, 0);
 }
 
-extern "C" int rtk_dev_scene_refit_meshes(rtk_dev_scene *ds, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids, void *stream)
+// Both per-mesh refits, likewise.
+static int refit_some(const char *who, rtk_dev_scene *ds, const rtk_scene_desc *desc, const rtk_placement *placements, bool placed, const uint32_t *mesh_ids,
+	size_t num_ids, void *stream)
 {
-	// ---- as above: every refusal before HIP is touched; only the listed meshes' positions are looked at
-	const char *who = "rtk_dev_scene_refit_meshes";
-	if (!ds || !desc) { rtk_set_error("%s: NULL argument", who); return RTK_AMD_ERR_BAD_ARG; }
+	// ---- as above: every refusal before HIP is touched; only the listed meshes' positions (and placements) are looked at
+	if (!ds || !desc || (placed && !placements)) { rtk_set_error("%s: NULL argument", who); return RTK_AMD_ERR_BAD_ARG; }
 	if (!mesh_ids && num_ids) { rtk_set_error("%s: NULL mesh_ids with %zu ids", who, num_ids); return RTK_AMD_ERR_BAD_ARG; }
 	int rc = check_desc(who, ds, desc);
 	if (rc != RTK_AMD_OK) return rc;
@@ -862,7 +885,29 @@ extern "C" int rtk_dev_scene_refit_meshes(rtk_dev_scene *ds, const rtk_scene_des
 		return RTK_AMD_OK;
 	}
 	// every mesh that has a triangle is listed: that IS the full refit (no mesh it would read is one this call may not read)
-	return refit_in_pass(pass, desc, listed_tris == ds->mesh_base.back() ? nullptr : listed.data(), listed_tris);
+	return refit_in_pass(pass, desc, placements, listed_tris == ds->mesh_base.back() ? nullptr : listed.data(), listed_tris);
+}
+
+extern "C" int rtk_dev_scene_refit(rtk_dev_scene *ds, const rtk_scene_desc *desc, void *stream)
+{
+	return refit_all("rtk_dev_scene_refit", ds, desc, nullptr, false, stream);
+}
+
+extern "C" int rtk_dev_scene_refit_meshes(rtk_dev_scene *ds, const rtk_scene_desc *desc, const uint32_t *mesh_ids, size_t num_ids, void *stream)
+{
+	return refit_some("rtk_dev_scene_refit_meshes", ds, desc, nullptr, false, mesh_ids, num_ids, stream);
+}
+
+// the placed forms (rtk_amd.h): the same passes, the vertices through rtk_place_rule.h where refit_tri reads them
+extern "C" int rtk_dev_scene_refit_placed(rtk_dev_scene *ds, const rtk_scene_desc *desc, const rtk_placement *placements, void *stream)
+{
+	return refit_all("rtk_dev_scene_refit_placed", ds, desc, placements, true, stream);
+}
+
+extern "C" int rtk_dev_scene_refit_meshes_placed(rtk_dev_scene *ds, const rtk_scene_desc *desc, const rtk_placement *placements, const uint32_t *mesh_ids,
+	size_t num_ids, void *stream)
+{
+	return refit_some("rtk_dev_scene_refit_meshes_placed", ds, desc, placements, true, mesh_ids, num_ids, stream);
 }
 
 extern "C" double rtk_dev_scene_last_refit_ms(const rtk_dev_scene *ds)

@@ -61,6 +61,23 @@ assert C.sizeof(Buffer) == 24 and C.sizeof(Mesh) == 96 and C.sizeof(SceneDesc) =
 assert C.sizeof(SceneHeader) == 56 and C.sizeof(Task) == 40
 
 
+class Placement(C.Structure):
+    """rtk_placement: a 3 x 4 matrix row by row (include/rtk_amd.h)."""
+    _fields_ = [("m", C.c_float * 12)]
+
+
+assert C.sizeof(Placement) == 48
+
+
+def placement_array(placements, num_meshes):
+    """array-like (num_meshes, 3, 4) or (num_meshes, 12) -> the contiguous float32 [num_meshes, 12] the library reads as
+    rtk_placement[num_meshes]. The values are taken as float32: anything else is rounded once, here."""
+    a = np.ascontiguousarray(np.asarray(placements, np.float32).reshape(-1, 12) if np.size(placements) else np.zeros((0, 12), np.float32))
+    if a.shape[0] != num_meshes:
+        raise ValueError("placements: %d entries for %d meshes" % (a.shape[0], num_meshes))
+    return a if a.shape[0] else np.zeros((1, 12), np.float32)      # (never a NULL pointer: NULL means "no placements given")
+
+
 class MeshSet:
     """Keeps numpy buffers alive and exposes them as an rtk_scene_desc.
 
