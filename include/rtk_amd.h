@@ -110,7 +110,9 @@ typedef struct rtk_trace_counters {
 
 /* -- scenes -- */
 /* Validates the blob (every offset range-checked without wrap-around; it must be a tree: a node or leaf
- * reached twice is refused) and lays it out in HBM. rtk_dev_scene_upload trusts scene->size_in_bytes to be
+ * reached twice is refused; an empty child slot is the inverted box +1 / -1 on all three axes that every writer gives it,
+ * and a slot that is inverted or NaN on some axis without being exactly that box is refused, not taken for empty) and
+ * lays it out in HBM. rtk_dev_scene_upload trusts scene->size_in_bytes to be
  * readable, as the reference's bare rtk_scene* forces it to; a loader of untrusted files uses
  * rtk_dev_scene_upload_buffer, which also checks the header against the buffer size. */
 rtk_dev_scene *rtk_dev_scene_upload(const rtk_scene *scene);
@@ -328,7 +330,7 @@ int rtk_dev_scene_split_leaves(rtk_dev_scene *ds, uint32_t max_leaf, rtk_dev_spl
  *   - Fewer than two triangles: success, no bit changes, nothing is launched.
  *   - RTK_AMD_ERR_BAD_ARG: ds NULL, out->struct_size < sizeof(rtk_dev_rebuild_info); decided before any HIP call.
  *     RTK_AMD_ERR_UNSUPPORTED: the scene does not hold exactly one triangle record per primitive (an uploaded blob may
- *     name an id twice or never); decided before the scene is written, which stays as it was.
+ *     name an id twice or never, which rtk_dev_scene_validate reports as primitive_id_errors); decided before the scene is written, which stays as it was.
  * rtk_mgpu_rebuild does the same on every GPU of the context; rtk_mgpu_scene handles stay valid. */
 typedef struct rtk_dev_rebuild_info {
 	uint32_t struct_size;            /* sizeof(rtk_dev_rebuild_info), set by the caller */
@@ -354,7 +356,7 @@ typedef struct rtk_dev_scene_check {
 	uint64_t leaf_format_errors;
 	uint64_t triangles_missing, triangles_duplicated;
 	uint64_t nodes_unreachable, nodes_shared;
-	uint64_t primitive_id_errors;   /* id out of range, repeated, or prim -> slot table inconsistent */
+	uint64_t primitive_id_errors;   /* id out of range, repeated, never used (uploaded blobs too: a mesh has largest triangle index + 1 primitives), or prim -> slot table inconsistent */
 	uint64_t compressed_node_errors; /* a 64 B compressed node whose decoded child box does not contain the exact one */
 	uint64_t first_bad_index;       /* smallest node / slot index that raised an error, ~0 if none */
 	uint64_t content_hash;

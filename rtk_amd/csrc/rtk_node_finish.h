@@ -4,35 +4,45 @@
 // nodes in the pass that makes them instead of re-reading them.
 #pragma once
 
-#include "rtk_dev.h"
+// Includes no HIP: the same text runs on the host under tests/node_finish_driver.cpp, against a reference written from the format's
+// contract (tests/test_node_finish_cpu.py).
+#include "rtk_node.h"
 
 #include <math.h>
 
+#ifdef __HIPCC__
+#define RTK_NODE_FN __host__ __device__ __forceinline__
+#define RTK_NODE_UNROLL _Pragma("unroll")             // what "#pragma unroll" says, so the device code is the one it always was
+#else
+#define RTK_NODE_FN inline
+#define RTK_NODE_UNROLL                                  // (a pragma the host compiler does not know)
+#endif
 
 // largest power of two s.t. 254 steps still cover `extent` is too coarse by up to 2x; this picks the smallest
 // power of two with 254 * s >= extent (one level is kept in reserve for the round-up of the high planes)
-__device__ __forceinline__ float grid_step(float extent)
+RTK_NODE_FN float grid_step(float extent)
 {
 	if (!(extent > 0.0f)) return 1.17549435e-38f;            // flat on this axis: every plane sits at q = 0
 	int e;
 	(void)frexpf(extent, &e);                                // extent = m * 2^e, m in [0.5, 1)
-	float s = ldexpf(1.0f, e - 8);                           // 256 * s = 2^e > extent
+	// 256 * s = 2^e > extent; never below the smallest float: an extent under 2^-141 would get a step of 0, which no plane fits
+	float s = ldexpf(1.0f, e - 8 > -149 ? e - 8 : -149);
 	if (254.0f * s < extent) s *= 2.0f;
 	return s;
 }
 
 // Front-to-back order of the children per direction octant (DevNode::order): by the centre of the child box along the
 // octant's diagonal, empty slots last, ties by slot number.
-__device__ __forceinline__ void child_order(const DevNode &nd, uint32_t order[4])
+RTK_NODE_FN void child_order(const DevNode &nd, uint32_t order[4])
 {
 	order[0] = order[1] = order[2] = order[3] = 0u;
 	float cx[4], cy[4], cz[4];
-#pragma unroll
+	RTK_NODE_UNROLL
 	for (int k = 0; k < 4; k++) { cx[k] = nd.bx[0][k] + nd.bx[1][k]; cy[k] = nd.by[0][k] + nd.by[1][k]; cz[k] = nd.bz[0][k] + nd.bz[1][k]; }
-#pragma unroll
+	RTK_NODE_UNROLL
 	for (uint32_t o = 0; o < 8u; o++) {
 		float key[4];
-#pragma unroll
+		RTK_NODE_UNROLL
 		for (int k = 0; k < 4; k++) {
 			float s = ((o & 1u) ? -cx[k] : cx[k]) + ((o & 2u) ? -cy[k] : cy[k]) + ((o & 4u) ? -cz[k] : cz[k]);
 			if (!(s == s)) s = INFINITY;                           // NaN boxes sort behind everything real
@@ -52,11 +62,11 @@ __device__ __forceinline__ void child_order(const DevNode &nd, uint32_t order[4]
 
 // The compressed copy of `nd` (child words included). Returns false if some child box does not fit the 8-bit grid (extents
 // that are not finite in float): the scene then keeps to its exact nodes.
-__device__ __forceinline__ bool quantize_node(const DevNode &nd, DevNodeQ &q)
+RTK_NODE_FN bool quantize_node(const DevNode &nd, DevNodeQ &q)
 {
 	bool misfit = false;
 	const float *lo[3] = { nd.bx[0], nd.by[0], nd.bz[0] }, *hi[3] = { nd.bx[1], nd.by[1], nd.bz[1] };
-#pragma unroll
+	RTK_NODE_UNROLL
 	for (int a = 0; a < 3; a++) {
 		float mn = INFINITY, mx = -INFINITY;
 		for (int k = 0; k < 4; k++) if (nd.child[k] != RTK_REF_NONE) { mn = fminf(mn, lo[a][k]); mx = fmaxf(mx, hi[a][k]); }
@@ -112,7 +122,7 @@ __device__ __forceinline__ bool quantize_node(const DevNode &nd, DevNodeQ &q)
 
 // The scene bound from the root node (every box of a tree the device builds lies inside the root's child boxes): the largest
 // absolute plane, INFINITY if one is not finite. bound_hint: a bound the caller already knows (uploads), 0 = none.
-__device__ __forceinline__ float root_bound(const DevNode &nd, float bound_hint)
+RTK_NODE_FN float root_bound(const DevNode &nd, float bound_hint)
 {
 	float b = bound_hint;
 	for (int k = 0; k < 4; k++) {

@@ -39,6 +39,13 @@ bool slot_is_empty(const BlobNode &n, int i)
 	return !(n.bx[0][i] <= n.bx[1][i] && n.by[0][i] <= n.by[1][i] && n.bz[0][i] <= n.bz[1][i]);
 }
 
+// ... and every writer gives them exactly +1 / -1 on all three axes. A slot that is inverted (or NaN) on some axis and is not
+// that box is a damaged child box, not an empty slot: taking it for one would drop what is below it without a word.
+bool slot_is_canonical_empty(const BlobNode &n, int i)
+{
+	return n.bx[0][i] == 1.0f && n.by[0][i] == 1.0f && n.bz[0][i] == 1.0f && n.bx[1][i] == -1.0f && n.by[1][i] == -1.0f && n.bz[1][i] == -1.0f;
+}
+
 } // namespace
 
 // `avail`: bytes that are known to be readable at `scene` (the loader of an untrusted file passes the
@@ -74,7 +81,10 @@ int rtk_blob_to_host_bvh(const rtk_scene *scene, size_t avail, HostBvh *out)
 		BlobNode n;
 		memcpy(&n, blob + off, sizeof(n));                // off was range-checked when it was queued (root: size >= 256)
 		for (int i = 0; i < 4; i++) {
-			if (slot_is_empty(n, i)) continue;
+			if (slot_is_empty(n, i)) {
+				if (!slot_is_canonical_empty(n, i)) { rtk_set_error("scene blob: node at %llu, slot %d: an inverted or NaN box that is not the empty slot's +1 / -1", (unsigned long long)off, i); return RTK_AMD_ERR_BAD_SCENE; }
+				continue;
+			}
 			const uint64_t p = n.child[i];
 			if (p & 1u) {
 				const uint64_t lo = p ^ 1u;

@@ -170,8 +170,9 @@ extern "C" int rtk_dev_scene_validate(const rtk_dev_scene *ds, rtk_dev_scene_che
 		hipLaunchKernelGGL(k_check_nodes, dim3((v.num_nodes + 127u) / 128u), dim3(128), 0, 0, v, ds->tree.first_top, ds->tree.first_split, slot_seen, node_seen, d_c);
 		if (v.num_tris) hipLaunchKernelGGL(k_check_slots, dim3((v.num_tris + 255u) / 256u), dim3(256), 0, 0, v, slot_seen, prim_seen, d_c);
 		const uint32_t m = v.num_nodes > v.num_prims ? v.num_nodes : v.num_prims;
-		// a scene built here holds every primitive of its meshes; an uploaded blob may leave ids unused
-		hipLaunchKernelGGL(k_check_counts, dim3((m + 255u) / 256u), dim3(256), 0, 0, v, node_seen, prim_seen, v.num_prims == v.num_tris ? 1u : 0u, d_c);
+		// every primitive id occurs once, in a scene built here and in an uploaded blob alike: the loader sizes a mesh by its largest
+		// triangle index, so an id that never occurs is a record that was lost (a leaf count lowered, a leaf emptied)
+		hipLaunchKernelGGL(k_check_counts, dim3((m + 255u) / 256u), dim3(256), 0, 0, v, node_seen, prim_seen, 1u, d_c);
 		if (hipGetLastError() != hipSuccess || hipMemcpy(h, d_c, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) {
 			rtk_set_error("rtk_dev_scene_validate: %s", hipGetErrorString(hipGetLastError()));
 			rc = RTK_AMD_ERR_HIP; break;

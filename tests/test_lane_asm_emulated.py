@@ -48,7 +48,7 @@ def grid_step(extent):
     if not extent > 0:
         return np.float32(1.17549435e-38)
     m, e = np.frexp(np.float32(extent))
-    s = np.float32(np.ldexp(1.0, int(e) - 8))
+    s = np.float32(np.ldexp(1.0, max(int(e) - 8, -149)))
     if np.float32(254.0) * s < np.float32(extent):
         s = np.float32(s * 2)
     return s
