@@ -453,6 +453,15 @@ typedef struct rtk_packet_counters {
 int rtk_dev_trace_rays_packet_counted(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
 	rtk_hit_record *d_hits, const rtk_trace_opts *opts, rtk_packet_counters *out);
 
+/* For tests and tools: the entry-list pre-pass of an image frame alone (what rtk_dev_trace_rays runs ahead of the packet kernel
+ * when the image hint is given). image_w and image_h are multiples of 64; d_rays holds image_w * image_h rays, row-major;
+ * target and max_levels are the two list knobs (the library's defaults: 26 and 8). host_out receives (image_w / 64) *
+ * (image_h / 64) records of 512 bytes, one per 64x64-pixel block, row by row: float olo[3], ohi[3], rlo[3], rhi[3] (the
+ * block's beam), uint32 count at byte 48, float min_t at 52, and from byte 64 count pairs { uint32 node, float lower bound of
+ * the entry distance }, ascending. count = 0: the block's tiles start at the root. Runs on the NULL stream; synchronous. */
+int rtk_dev_debug_packet_entries(const rtk_dev_scene *ds, const rtk_ray *d_rays, uint32_t image_w, uint32_t image_h,
+	uint32_t target, uint32_t max_levels, void *host_out);
+
 /* -- several GPUs of one node, one process --
  * Rays shard, nothing else: the scene is replicated (the deterministic build or the upload runs on every GPU),
  * shard r of R owns the contiguous range rtk_amd_shard_range(n, r, R) of the batch, and the only exchange is the

@@ -110,6 +110,11 @@ class PacketCounters(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+# one record of rtk_dev_debug_packet_entries (PkBlockEntries, rtk_amd/csrc/rtk_trace_shared.h)
+PACKET_ENTRIES_DTYPE = np.dtype([("olo", "<f4", (3,)), ("ohi", "<f4", (3,)), ("rlo", "<f4", (3,)), ("rhi", "<f4", (3,)), ("count", "<u4"), ("tmin", "<f4"),
+                                 ("pad", "<u4", (2,)), ("e", [("ref", "<u4"), ("tlo", "<f4")], (56,))])
+assert PACKET_ENTRIES_DTYPE.itemsize == 512
+
 # every symbol include/rtk.h and include/rtk_amd.h declare
 RTK_H_SYMBOLS = ["rtk_start_build", "rtk_run_task", "rtk_get_build_size", "rtk_finish_build_to",
                  "rtk_finish_build", "rtk_build_scene", "rtk_free_scene", "rtk_trace_ray", "rtk_trace_ray_filter"]
@@ -117,7 +122,7 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_dev_scene_upload", "rtk_dev_scene_build", "rtk_dev_scene_free", "rtk_dev_scene_get_info",
                      "rtk_dev_scene_mesh_base", "rtk_dev_scene_primitive_order", "rtk_dev_scene_export_size", "rtk_dev_scene_export",
                      "rtk_dev_trace_rays", "rtk_dev_trace_rays_any", "rtk_dev_expand_hits",
-                     "rtk_dev_trace_rays_counted", "rtk_dev_trace_rays_any_counted", "rtk_dev_trace_rays_packet_counted", "rtk_dev_detect_image", "rtk_trace_rays", "rtk_amd_forget_scene",
+                     "rtk_dev_trace_rays_counted", "rtk_dev_trace_rays_any_counted", "rtk_dev_trace_rays_packet_counted", "rtk_dev_debug_packet_entries", "rtk_dev_detect_image", "rtk_trace_rays", "rtk_amd_forget_scene",
                      "rtk_dev_scene_validate", "rtk_amd_release_workspace", "rtk_dev_scene_upload_buffer",
                      "rtk_dev_trace_rays_filtered", "rtk_dev_trace_rays_any_filtered", "rtk_dev_trace_status",
                      "rtk_trace_rays_filter", "rtk_amd_shard_range", "rtk_mgpu_create", "rtk_mgpu_destroy", "rtk_mgpu_num_devices",
@@ -166,6 +171,8 @@ def lib():
     L.rtk_dev_trace_rays_any.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(TraceOpts), C.c_void_p]
     L.rtk_dev_expand_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rtk_dev_trace_rays_packet_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(TraceOpts), C.POINTER(PacketCounters)]
+    L.rtk_dev_debug_packet_entries.restype = C.c_int
+    L.rtk_dev_debug_packet_entries.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     L.rtk_dev_trace_rays_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(TraceOpts),
                                              C.POINTER(TraceCounters)]
     L.rtk_dev_trace_rays_any_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(TraceOpts),
@@ -608,6 +615,18 @@ class DeviceScene:
         w, h = C.c_uint32(0), C.c_uint32(0)
         _check(lib().rtk_dev_detect_image(self.handle, C.c_void_p(d_rays.data_ptr()), C.c_size_t(rays.shape[0]), C.byref(w), C.byref(h), _stream_ptr()), "rtk_dev_detect_image")
         return int(w.value), int(h.value)
+
+    def debug_packet_entries(self, rays, width, height, target=26, max_levels=8):
+        """rtk_dev_debug_packet_entries: the entry-list pre-pass of a width x height frame alone; one 512-byte record per
+        64x64-pixel block, row by row (numpy, PACKET_ENTRIES_DTYPE)."""
+        torch = _torch()
+        d_rays = rays if hasattr(rays, "data_ptr") else to_device(np.ascontiguousarray(rays))
+        assert d_rays.numel() * d_rays.element_size() == width * height * 32
+        out = np.zeros((width // 64) * (height // 64), dtype=PACKET_ENTRIES_DTYPE)
+        torch.cuda.synchronize()
+        _check(lib().rtk_dev_debug_packet_entries(self.handle, C.c_void_p(d_rays.data_ptr()), width, height, target, max_levels,
+                                                  C.c_void_p(out.ctypes.data)), "rtk_dev_debug_packet_entries")
+        return out
 
     def trace_packet_counted(self, rays, opts):
         """rtk_dev_trace_rays_packet_counted: (records, counters of the hand-written packet kernel itself)."""

@@ -174,6 +174,12 @@ extern "C" int rtk_dev_trace_rays_packet_counted(const rtk_dev_scene *ds, const 
 	return rtk_launch_trace(ds, d_rays, n, d_hits, nullptr, opts, nullptr, false, nullptr, nullptr, nullptr, nullptr, 0, out);
 }
 
+extern "C" int rtk_dev_debug_packet_entries(const rtk_dev_scene *ds, const rtk_ray *d_rays, uint32_t image_w, uint32_t image_h,
+	uint32_t target, uint32_t max_levels, void *host_out)
+{
+	return rtk_debug_packet_entries(ds, d_rays, image_w, image_h, target, max_levels, host_out);
+}
+
 extern "C" int rtk_dev_detect_image(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, uint32_t *width, uint32_t *height, void *stream)
 {
 	if (!ds || !width || !height || (!d_rays && n)) { rtk_set_error("rtk_dev_detect_image: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }

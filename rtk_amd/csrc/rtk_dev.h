@@ -300,6 +300,8 @@ int rtk_launch_trace(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, r
 	uint8_t *d_occluded, const rtk_trace_opts *opts, hipStream_t stream, bool any_hit, rtk_trace_counters *counted,
 	const rtk_dev_filter *filter = nullptr, rtk_hit_record *d_cand = nullptr, uint32_t *d_cand_count = nullptr, uint32_t cand_k = 0,
 	rtk_packet_counters *pk_counted = nullptr);
+// the entry-list pre-pass of a w x h frame alone; host_out receives (w / 64) * (h / 64) PkBlockEntries records (rtk_trace_shared.h). Synchronous.
+int rtk_debug_packet_entries(const rtk_dev_scene *ds, const rtk_ray *d_rays, uint32_t image_w, uint32_t image_h, uint32_t target, uint32_t max_levels, void *host_out);
 int rtk_detect_image(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, hipStream_t stream, uint32_t *w_out, uint32_t *h_out);
 int rtk_trace_status(const rtk_dev_scene *ds, hipStream_t stream);
 void rtk_scratch_free(LaunchScratch *s);

@@ -1352,6 +1352,37 @@ int rtk_launch_trace(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, size_t n,
 	return RTK_AMD_OK;
 }
 
+// rtk_dev_debug_packet_entries: the pre-pass of an image frame alone, on the null stream's scratch set, and its lists copied to the host
+int rtk_debug_packet_entries(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, uint32_t image_w, uint32_t image_h, uint32_t target, uint32_t max_levels, void *host_out)
+{
+	rtk_dev_scene *ds = const_cast<rtk_dev_scene *>(ds_c);
+	if (!ds || !d_rays || !host_out) { rtk_set_error("rtk_dev_debug_packet_entries: NULL argument"); return RTK_AMD_ERR_BAD_ARG; }
+	if (image_w == 0 || image_h == 0 || (image_w & 63u) || (image_h & 63u) || (unsigned long long)image_w * image_h > 0xffffffffull) {
+		rtk_set_error("rtk_dev_debug_packet_entries: %u x %u is not an image of whole 64x64-pixel blocks", image_w, image_h);
+		return RTK_AMD_ERR_BAD_ARG;
+	}
+	if (!on_scene_device(ds, "rtk_dev_debug_packet_entries")) return RTK_AMD_ERR_BAD_ARG;
+	if (ds->view.num_nodes == 0) { rtk_set_error("rtk_dev_debug_packet_entries: the scene has no nodes"); return RTK_AMD_ERR_BAD_ARG; }
+	const hipStream_t stream = nullptr;
+	std::lock_guard<std::mutex> lock(ds->scratch_mutex);
+	LaunchScratch *sc = scratch_for(ds, stream);
+	if (!sc) return RTK_AMD_ERR_OOM;
+	const size_t nblk = (size_t)(image_w >> 6) * (image_h >> 6);
+	const int rc = grow(&sc->d_entries, &sc->entries_capacity, nblk, nblk * sizeof(PkBlockEntries), stream);
+	if (rc != RTK_AMD_OK) return rc;
+	TraceParams p = {};
+	p.sc = ds->view;
+	p.rays = d_rays;
+	p.image_w = image_w;
+	p.image_h = image_h;
+	p.counter = sc->d_counter;
+	rtk_packet_entries_launch(p, (PkBlockEntries *)sc->d_entries, ds->tree.bound_abs > 1.0f ? ds->tree.bound_abs : 1.0f, target, max_levels, stream);
+	RTK_HIP_CHECK(hipGetLastError(), RTK_AMD_ERR_HIP);
+	RTK_HIP_CHECK(hipMemcpyAsync(host_out, sc->d_entries, nblk * sizeof(PkBlockEntries), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
+	RTK_HIP_CHECK(hipStreamSynchronize(stream), RTK_AMD_ERR_HIP);
+	return RTK_AMD_OK;
+}
+
 // Did any launch of this scene on `stream` since the last call overflow a traversal stack? Synchronises the stream.
 int rtk_trace_status(const rtk_dev_scene *ds_c, hipStream_t stream)
 {

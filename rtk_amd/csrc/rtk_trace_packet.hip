@@ -22,6 +22,7 @@
 // FLOATING POINT: compiled with -ffp-contract=off like rtk_trace.hip.
 #include "rtk_dev.h"
 #include "rtk_trace_shared.h"
+#include "rtk_entries_rule.h"
 
 #include <math.h>
 
@@ -649,27 +650,16 @@ __global__ void __launch_bounds__(TRACE_BLOCK_THREADS, PK_MIN_WAVES) rtk_trace_p
 // what the reference computes for any ray of the beam, rtk.c:458-470 -- widened by the packet kernels' own margin, so that
 // every child a tile's slab test admits is admitted here. The walk goes level by level until `target` nodes are on the list.
 namespace {
-struct PkBeam { float olo[3], ohi[3], rlo[3], rhi[3], m[3], tmin; uint32_t neg; };
-
-__device__ __forceinline__ bool pk_beam_child(const DevNode &nd, int k, const PkBeam &b, float &tlo)
-{
-	const float lo[3] = { nd.bx[0][k], nd.by[0][k], nd.bz[0][k] }, hi[3] = { nd.bx[1][k], nd.by[1][k], nd.bz[1][k] };
-	float n = b.tmin, f = INFINITY;
-#pragma unroll
-	for (int a = 0; a < 3; a++) {
-		const bool neg = (b.neg >> a) & 1u;
-		const float pn = neg ? hi[a] : lo[a], pf = neg ? lo[a] : hi[a];
-		const float n0 = (pn - b.olo[a]) * b.rlo[a], n1 = (pn - b.olo[a]) * b.rhi[a], n2 = (pn - b.ohi[a]) * b.rlo[a], n3 = (pn - b.ohi[a]) * b.rhi[a];
-		const float f0 = (pf - b.olo[a]) * b.rlo[a], f1 = (pf - b.olo[a]) * b.rhi[a], f2 = (pf - b.ohi[a]) * b.rlo[a], f3 = (pf - b.ohi[a]) * b.rhi[a];
-		n = fmaxf(n, fminf(fminf(n0, n1), fminf(n2, n3)) - b.m[a]);
-		f = fminf(f, fmaxf(fmaxf(f0, f1), fmaxf(f2, f3)) + b.m[a]);
-	}
-	tlo = n;
-	return n <= f;
-}
-
-__device__ __forceinline__ float wave_min(float v) { for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o)); return v; }
-__device__ __forceinline__ float wave_max(float v) { for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o)); return v; }
+// One step of a reduction over the 16 lanes of a DPP row (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror,
+// row_mirror: after the four, every lane of the row holds the row's result). Every lane of the wave must be active.
+template <int CTRL> __device__ __forceinline__ uint32_t pk_dpp(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false); }
+template <int CTRL> __device__ __forceinline__ float pk_dpp(float v) { return __uint_as_float(pk_dpp<CTRL>(__float_as_uint(v))); }
+#define PK_ROW_REDUCE(v, OP) do { v = OP(v, pk_dpp<0xB1>(v)); v = OP(v, pk_dpp<0x4E>(v)); v = OP(v, pk_dpp<0x141>(v)); v = OP(v, pk_dpp<0x140>(v)); } while (0)
+__device__ __forceinline__ uint32_t pk_and(uint32_t a, uint32_t b) { return a & b; }
+__device__ __forceinline__ uint32_t pk_or(uint32_t a, uint32_t b) { return a | b; }
+// the first row's minimum / maximum, in every lane of the wave (a scalar register)
+__device__ __forceinline__ float row0_min(float v) { PK_ROW_REDUCE(v, fminf); return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(v))); }
+__device__ __forceinline__ float row0_max(float v) { PK_ROW_REDUCE(v, fmaxf); return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(v))); }
 
 #define PK_FRONTIER 128
 __global__ void __launch_bounds__(64) rtk_packet_entries_kernel(const DevNode *nodes, const rtk_ray *rays, uint32_t image_w, uint32_t blocks_per_row,
@@ -683,7 +673,12 @@ __global__ void __launch_bounds__(64) rtk_packet_entries_kernel(const DevNode *n
 	__shared__ float s_out_t[PK_MAX_ENTRIES];
 	const uint32_t lane = threadIdx.x, blk = blockIdx.x;
 	const uint32_t bx = blk % blocks_per_row, by = blk / blocks_per_row;
-	PkBeam b;
+	// One (node, child) per lane: lane 4 q + k tests child k of the q-th node of a pass over the frontier, and loads that child's
+	// six planes and its reference only (28 of the node's 128 bytes). The root's go first: they do not wait for the rays.
+	const uint32_t k = lane & 3u, q = lane >> 2;
+	float lo[3] = { nodes[0].bx[0][k], nodes[0].by[0][k], nodes[0].bz[0][k] }, hi[3] = { nodes[0].bx[1][k], nodes[0].by[1][k], nodes[0].bz[1][k] };
+	uint32_t child = nodes[0].child[k];
+	RtkEntriesBeam b;
 	bool ok = true;
 	uint32_t s_and = 7u, s_or = 0u;
 	float tmin = INFINITY;
@@ -709,16 +704,19 @@ __global__ void __launch_bounds__(64) rtk_packet_entries_kernel(const DevNode *n
 		tmin = r.min_t;
 		s_and = sg; s_or = sg;
 	}
-	for (int o = 32; o > 0; o >>= 1) { s_and &= __shfl_xor(s_and, o); s_or |= __shfl_xor(s_or, o); }
+	// the nine live lanes are in the first DPP row: four row steps each, no trips through the LDS crossbar
+	PK_ROW_REDUCE(s_and, pk_and);
+	PK_ROW_REDUCE(s_or, pk_or);
+	s_and = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_and); s_or = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_or);
 	ok = __builtin_amdgcn_ballot_w64(!ok) == 0ull && s_and == s_or && bound_abs < 0x1p19f;
 	for (int a = 0; a < 3; a++) {
-		b.olo[a] = wave_min(b.olo[a]); b.ohi[a] = wave_max(b.ohi[a]); b.rlo[a] = wave_min(b.rlo[a]); b.rhi[a] = wave_max(b.rhi[a]);
+		b.olo[a] = row0_min(b.olo[a]); b.ohi[a] = row0_max(b.ohi[a]); b.rlo[a] = row0_min(b.rlo[a]); b.rhi[a] = row0_max(b.rhi[a]);
 		// two ulps outward: rtk_packet_beam2 checks its rays' v_rcp_f32 reciprocals (one ulp) against this box; the quotients here are
 		// the correctly rounded ones, and a corner ray of the block must not fall out of its own block's beam by that ulp
 		b.rlo[a] -= 0x1p-22f * fabsf(b.rlo[a]); b.rhi[a] += 0x1p-22f * fabsf(b.rhi[a]);
 		b.m[a] = 0x1p-21f * (fmaxf(fabsf(b.rlo[a]), fabsf(b.rhi[a])) * (fmaxf(fabsf(b.olo[a]), fabsf(b.ohi[a])) + bound_abs));
 	}
-	b.tmin = wave_min(tmin);
+	b.tmin = row0_min(tmin);
 	b.neg = s_or;
 	PkBlockEntries *e = out + blk;
 	if (lane == 0) {
@@ -727,49 +725,49 @@ __global__ void __launch_bounds__(64) rtk_packet_entries_kernel(const DevNode *n
 		if (!ok) e->count = 0u;
 	}
 	if (!ok) return;
-	// level by level from the root; wave-uniform counts, appends by ballot rank
+	// level by level from the root; wave-uniform counts, appends by ballot rank. The first level works from registers (the root
+	// loaded above, in lanes 0-3); its slot in the frontier is read back only by lane 0 itself, if no level runs at all.
 	uint32_t n_cur = 1u, n_out = 0u, cur = 0u;
 	bool over = false;
 	if (lane == 0) { s_ref[0][0] = 0u; s_t[0][0] = b.tmin; }
-	__syncthreads();
+	const unsigned long long below = (1ull << lane) - 1ull;
 	// (a block that looks past the scene's edge finds few nodes per level and would walk to the leaves: the deepest walk is the
-	// kernel's duration -- 30 us at 14 levels, 26 at 8 --, so the walk is capped)
+	// kernel's duration, so the walk is capped)
 	for (int level = 0; level < (int)max_levels && n_cur != 0u; level++) {
 		if (level > 0 && n_out + n_cur >= target) break;
 		uint32_t n_next = 0u;
-		for (uint32_t base = 0; base < n_cur; base += 64u) {
-			const bool have = base + lane < n_cur;
-			const uint32_t ref = have ? s_ref[cur][base + lane] : 0u;
-			const float t_self = have ? s_t[cur][base + lane] : 0.0f;
-			const DevNode nd = nodes[ref];
-			bool pass[4], leaf_below = false;
-			float tlo[4];
-#pragma unroll
-			for (int k = 0; k < 4; k++) {
-				tlo[k] = 0.0f;
-				pass[k] = have && nd.child[k] != RTK_REF_NONE && pk_beam_child(nd, k, b, tlo[k]);
-				leaf_below = leaf_below || (pass[k] && (nd.child[k] & RTK_REF_LEAF) != 0u);
+		for (uint32_t base = 0; base < n_cur; base += 16u) {
+			const bool have = base + q < n_cur;
+			uint32_t ref = 0u;
+			float t_self = b.tmin;
+			if (level > 0) {
+				if (have) { ref = s_ref[cur][base + q]; t_self = s_t[cur][base + q]; }
+				const DevNode &nd = nodes[ref];
+				lo[0] = nd.bx[0][k]; lo[1] = nd.by[0][k]; lo[2] = nd.bz[0][k];
+				hi[0] = nd.bx[1][k]; hi[1] = nd.by[1][k]; hi[2] = nd.bz[1][k];
+				child = nd.child[k];
 			}
+			float tlo = 0.0f;
+			const bool pass = have && child != RTK_REF_NONE && rtk_entries_child(lo, hi, b, &tlo);
 			// a node with a leaf among the children the beam reaches is listed itself (a listed leaf would be tested by every
-			// tile of the block); a node the beam reaches no child of is dropped
-			const bool list_self = have && leaf_below;
-			const unsigned long long below = (1ull << lane) - 1ull;
-			const unsigned long long m_out = __builtin_amdgcn_ballot_w64(list_self);
-			if (list_self) {
+			// tile of the block); a node the beam reaches no child of is dropped. The four lanes of a node agree by their
+			// four bits of one ballot.
+			const unsigned long long m_leaf = __builtin_amdgcn_ballot_w64(pass && (child & RTK_REF_LEAF) != 0u);
+			const bool list_self = ((uint32_t)(m_leaf >> (lane & ~3u)) & 0xfu) != 0u;
+			const bool first = list_self && k == 0u;
+			const unsigned long long m_out = __builtin_amdgcn_ballot_w64(first);
+			if (first) {
 				const uint32_t at = n_out + (uint32_t)__popcll(m_out & below);
 				if (at < PK_MAX_ENTRIES) { s_out_ref[at] = ref; s_out_t[at] = t_self; }
 			}
 			n_out += (uint32_t)__popcll(m_out);
-#pragma unroll
-			for (int k = 0; k < 4; k++) {
-				const bool push = pass[k] && !list_self;
-				const unsigned long long m_next = __builtin_amdgcn_ballot_w64(push);
-				if (push) {
-					const uint32_t at = n_next + (uint32_t)__popcll(m_next & below);
-					if (at < PK_FRONTIER) { s_ref[cur ^ 1u][at] = nd.child[k]; s_t[cur ^ 1u][at] = tlo[k]; }
-				}
-				n_next += (uint32_t)__popcll(m_next);
+			const bool push = pass && !list_self;
+			const unsigned long long m_next = __builtin_amdgcn_ballot_w64(push);
+			if (push) {
+				const uint32_t at = n_next + (uint32_t)__popcll(m_next & below);
+				if (at < PK_FRONTIER) { s_ref[cur ^ 1u][at] = child; s_t[cur ^ 1u][at] = tlo; }
 			}
+			n_next += (uint32_t)__popcll(m_next);
 		}
 		over = over || n_out > PK_MAX_ENTRIES || n_next > PK_FRONTIER;
 		if (over) break;
@@ -785,12 +783,18 @@ __global__ void __launch_bounds__(64) rtk_packet_entries_kernel(const DevNode *n
 	}
 	__syncthreads();
 	if (over) { if (lane == 0) e->count = 0u; return; }
-	// front to back by the lower bound of the entry distance (rank = entries that come before; ties by position)
-	if (lane < n_out) {
-		const float t = s_out_t[lane];
-		uint32_t rank = 0;
-		for (uint32_t j = 0; j < n_out; j++) { const float tj = s_out_t[j]; rank += (tj < t || (tj == t && j < lane)) ? 1u : 0u; }
-		e->e[rank].ref = s_out_ref[lane];
+	// front to back by the lower bound of the entry distance (rank = entries that come before; ties by position): one entry per
+	// lane, the others' bounds read lane by lane
+	const bool mine = lane < n_out;
+	const float t = mine ? s_out_t[lane] : INFINITY;
+	const uint32_t r_mine = mine ? s_out_ref[lane] : 0u;
+	uint32_t rank = 0;
+	for (uint32_t j = 0; j < n_out; j++) {
+		const float tj = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(t), (int)j));
+		rank += (tj < t || (tj == t && j < lane)) ? 1u : 0u;
+	}
+	if (mine) {
+		e->e[rank].ref = r_mine;
 		e->e[rank].tlo = t;
 	}
 	if (lane == 0) e->count = n_out;
