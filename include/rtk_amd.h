@@ -419,6 +419,59 @@ int rtk_dev_trace_rays_filtered(const rtk_dev_scene *ds, const rtk_ray *d_rays, 
 	rtk_hit_record *d_hits, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream);
 int rtk_dev_trace_rays_any_filtered(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
 	uint8_t *d_occluded, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream);
+
+/* ---- Ray lists: which rays of a batch are traced is decided on the device ----
+ * After a trace a caller keeps some rays (the ones that hit, the ones that are not occluded); how many and which is known
+ * on the device only. A rtk_ray_list names them there, rtk_dev_select_rays makes one from a trace's output, and the listed
+ * traces take one: bounce after bounce is enqueued on one stream without a host wait in between.
+ *
+ * Listed traces. m = min(*d_count, num_rays) entries are traced. num_rays is the size of d_rays, of d_hits / d_occluded
+ * and of the per-ray filter arrays (d_ignore_prim, d_after), as the host knows it; d_ids holds at least m entries. The
+ * result for ray r goes to slot r of the output -- the rule the per-ray filter arrays follow --, and A SLOT THAT IS NOT
+ * LISTED IS NOT WRITTEN. A listed slot holds bit for bit what rtk_dev_trace_rays[_any][_filtered] writes there for the same
+ * ray array. An id may repeat: the ray is traced twice and written twice with the same bytes. An id >= num_rays is the
+ * caller's error and, like a bad ray pointer, is NOT CHECKED (the ray is read and the result written out of range).
+ * *d_count == 0 writes nothing and is not an error. The calls are asynchronous on `stream` and read nothing back: no host
+ * wait anywhere. A count or a list that earlier work on the same stream wrote (a select, a kernel of the caller's) is
+ * seen. They use the per-(scene, stream) scratch set like every other launch: the thread-safety rules above hold unchanged.
+ * Listed batches never go to the packet kernels (a listed subset is not an image): image_width, image_height,
+ * RTK_TRACE_SORT_RAYS and RTK_TRACE_STATIC of `opts` are IGNORED (they are speed hints); refill_min, node_exit,
+ * blocks_per_cu, RTK_TRACE_NO_ASM and RTK_TRACE_EXACT_NODES apply as always.
+ * Refused before anything is launched, RTK_AMD_ERR_BAD_ARG: list == NULL, d_count == NULL, a struct_size that is too small,
+ * flags != 0, a missing output, num_rays >= 2^32; scene and device refusals are those of rtk_dev_trace_rays.
+ * num_rays == 0 is RTK_AMD_OK with nothing launched. `filter` may be NULL. */
+typedef struct rtk_ray_list {
+	uint32_t struct_size;        /* sizeof(rtk_ray_list) */
+	uint32_t flags;              /* 0 */
+	const uint64_t *d_ids;       /* device; optional. Entry i names ray (uint32_t)d_ids[i]; only the low 32 bits are read,
+	                                so a torch int64 index tensor is a list as it stands. NULL: the list is 0, 1, 2, ... */
+	const uint64_t *d_count;     /* device; required. Read when the work reaches it on `stream`, never by the host. */
+} rtk_ray_list;
+int rtk_dev_trace_rays_listed(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t num_rays, const rtk_ray_list *list,
+	rtk_hit_record *d_hits, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream);
+int rtk_dev_trace_rays_any_listed(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t num_rays, const rtk_ray_list *list,
+	uint8_t *d_occluded, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream);
+
+/* Select: the list of the rays whose source element matches `kind`. The input list is gone through in order -- `in` == NULL:
+ * 0 .. num_rays - 1; else the first min(*in->d_count, num_rays) entries of `in` -- and the ids r are kept whose element r of
+ * d_src matches: d_src as rtk_hit_record[num_rays], prim != RTK_PRIM_NONE is a hit (RTK_SELECT_RECORD_HIT) and prim ==
+ * RTK_PRIM_NONE a miss (RTK_SELECT_RECORD_MISS); d_src as uint8_t[num_rays], non-zero (RTK_SELECT_BYTE_NONZERO) or zero
+ * (RTK_SELECT_BYTE_ZERO). The output is STABLE: kept ids appear in input order, packed from d_out_ids[0] (8 bytes each, the
+ * upper half zero), and *d_out_count is their number; entries of d_out_ids at and beyond *d_out_count are not written. The
+ * result is deterministic: the same inputs give the same bytes. Asynchronous on `stream`, no host wait. d_out_ids has room
+ * for num_rays entries and MAY NOT ALIAS in->d_ids, nor d_out_count in->d_count (both are read after the outputs are begun).
+ * As in the listed traces an input id >= num_rays is the caller's error. Scratch (one bit per ray and a few words per 1024)
+ * comes from the scene's scratch set of the stream and grows like the rest: that is why `ds` is a parameter, and the
+ * thread-safety rules above hold. RTK_AMD_ERR_BAD_ARG: an unknown kind, a NULL scene, source or output, a bad `in` (as for
+ * the listed traces), num_rays >= 2^32. num_rays == 0: *d_out_count = 0. */
+enum { RTK_SELECT_RECORD_HIT = 0, RTK_SELECT_RECORD_MISS = 1, RTK_SELECT_BYTE_NONZERO = 2, RTK_SELECT_BYTE_ZERO = 3 };
+int rtk_dev_select_rays(const rtk_dev_scene *ds, const void *d_src, uint32_t kind, size_t num_rays,
+	const rtk_ray_list *in, uint64_t *d_out_ids, uint64_t *d_out_count, void *stream);
+/* (what one workgroup of the select's count / scatter kernels and one workgroup of its scan level cover, in rays: the sizes at
+ * which the kernels take another path, for tests) */
+uint32_t rtk_amd_select_block_items(void);
+uint32_t rtk_amd_select_scan_items(void);
+
 /* Waits for `stream` and reports whether a launch of this scene on it overflowed a traversal stack
  * (RTK_AMD_ERR_BAD_SCENE; impossible for a validated tree -- the push is dropped, never written out of bounds). */
 int rtk_dev_trace_status(const rtk_dev_scene *ds, void *stream);

@@ -88,6 +88,25 @@ class DevFilter(C.Structure):
                 ("d_ignore_prim", C.c_void_p), ("d_after", C.c_void_p)]
 
 
+class RayList(C.Structure):
+    """rtk_ray_list: the rays of a batch that a listed trace takes, named on the device."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("d_ids", C.c_void_p), ("d_count", C.c_void_p)]
+
+
+# rtk_dev_select_rays kinds
+SELECT_RECORD_HIT, SELECT_RECORD_MISS, SELECT_BYTE_NONZERO, SELECT_BYTE_ZERO = 0, 1, 2, 3
+
+
+def make_ray_list(count, ids=None):
+    """count: a cuda tensor whose first 8 bytes are the number of entries; ids: a cuda int64 tensor of ray numbers, or None for
+    0, 1, 2, ... The tensors must outlive the calls that read them."""
+    l = RayList()
+    l.struct_size = C.sizeof(RayList)
+    l.d_ids = ids.data_ptr() if ids is not None else None
+    l.d_count = count.data_ptr() if count is not None else None
+    return l
+
+
 FILTER_FN = C.CFUNCTYPE(C.c_bool, C.c_void_p, C.c_void_p, C.c_void_p)   # rtk_filter_fn (rtk.h:117)
 
 
@@ -134,7 +153,9 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_dev_scene_quality", "rtk_dev_scene_split_leaves", "rtk_mgpu_split_leaves",
                      "rtk_dev_scene_rebuild", "rtk_mgpu_rebuild",
                      "rtk_dev_scene_build_placed", "rtk_dev_scene_refit_placed", "rtk_dev_scene_refit_meshes_placed",
-                     "rtk_mgpu_build_placed", "rtk_mgpu_refit_placed", "rtk_mgpu_refit_meshes_placed"]
+                     "rtk_mgpu_build_placed", "rtk_mgpu_refit_placed", "rtk_mgpu_refit_meshes_placed",
+                     "rtk_dev_trace_rays_listed", "rtk_dev_trace_rays_any_listed", "rtk_dev_select_rays",
+                     "rtk_amd_select_block_items", "rtk_amd_select_scan_items"]
 
 _lib = None
 
@@ -188,6 +209,15 @@ def lib():
     L.rtk_dev_trace_rays_any_filtered.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(DevFilter),
                                                   C.POINTER(TraceOpts), C.c_void_p]
     L.rtk_dev_trace_status.argtypes = [C.c_void_p, C.c_void_p]
+    for fn in (L.rtk_dev_trace_rays_listed, L.rtk_dev_trace_rays_any_listed):
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.POINTER(DevFilter), C.POINTER(TraceOpts), C.c_void_p]
+        fn.restype = C.c_int
+    L.rtk_dev_select_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtk_dev_select_rays.restype = C.c_int
+    L.rtk_amd_select_block_items.argtypes = []
+    L.rtk_amd_select_block_items.restype = C.c_uint32
+    L.rtk_amd_select_scan_items.argtypes = []
+    L.rtk_amd_select_scan_items.restype = C.c_uint32
     L.rtk_trace_rays_filter.restype = C.c_size_t
     L.rtk_trace_rays_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rtk_amd_shard_range.restype = None
@@ -501,6 +531,45 @@ class DeviceScene:
         _check(lib().rtk_dev_trace_rays_any(self.handle, C.c_void_p(d_rays.data_ptr()), n, C.c_void_p(d_occluded.data_ptr()),
                                             C.byref(opts) if opts is not None else None, _stream_ptr()), "rtk_dev_trace_rays_any")
         return d_occluded
+
+    # -- ray lists: which rays are traced is decided on the device (rtk_ray_list); nothing here waits for the stream --
+
+    def trace_listed_device(self, d_rays, num_rays, count, ids=None, d_records=None, filter=None, opts=None):
+        """Closest hits of the first min(count[0], num_rays) rays that `ids` names (None: of the rays themselves), written to the
+        rays' own slots of d_records; slots that are not listed are not written. count, ids: cuda int64 tensors."""
+        torch = _torch()
+        if d_records is None:
+            d_records = torch.empty(num_rays * 16, dtype=torch.uint8, device="cuda")
+        l = make_ray_list(count, ids)
+        _check(lib().rtk_dev_trace_rays_listed(self.handle, C.c_void_p(d_rays.data_ptr()), num_rays, C.byref(l), C.c_void_p(d_records.data_ptr()),
+                                               C.byref(filter) if filter is not None else None, C.byref(opts) if opts is not None else None,
+                                               _stream_ptr()), "rtk_dev_trace_rays_listed")
+        return d_records
+
+    def trace_any_listed_device(self, d_rays, num_rays, count, ids=None, d_occluded=None, filter=None, opts=None):
+        """The any-hit form of trace_listed_device: one byte per ray, in the rays' own slots."""
+        torch = _torch()
+        if d_occluded is None:
+            d_occluded = torch.empty(num_rays, dtype=torch.uint8, device="cuda")
+        l = make_ray_list(count, ids)
+        _check(lib().rtk_dev_trace_rays_any_listed(self.handle, C.c_void_p(d_rays.data_ptr()), num_rays, C.byref(l), C.c_void_p(d_occluded.data_ptr()),
+                                                   C.byref(filter) if filter is not None else None, C.byref(opts) if opts is not None else None,
+                                                   _stream_ptr()), "rtk_dev_trace_rays_any_listed")
+        return d_occluded
+
+    def select_rays(self, src, kind, num_rays, in_ids=None, in_count=None):
+        """The rays of 0 .. num_rays - 1 (or of the list in_ids / in_count, in its order) whose element of `src` -- hit records for
+        SELECT_RECORD_*, bytes for SELECT_BYTE_* -- matches `kind`. Returns (ids, count): cuda int64 tensors of num_rays and 1
+        entries; ids beyond count[0] are not written."""
+        torch = _torch()
+        ids = torch.empty(max(num_rays, 1), dtype=torch.int64, device="cuda")
+        count = torch.empty(1, dtype=torch.int64, device="cuda")
+        if in_ids is not None and in_count is None:
+            raise RtkError("select_rays: in_ids without in_count (a list's length lives on the device)")
+        l = make_ray_list(in_count, in_ids) if in_count is not None else None
+        _check(lib().rtk_dev_select_rays(self.handle, C.c_void_p(src.data_ptr()), kind, num_rays, C.byref(l) if l is not None else None,
+                                         C.c_void_p(ids.data_ptr()), C.c_void_p(count.data_ptr()), _stream_ptr()), "rtk_dev_select_rays")
+        return ids, count
 
     def expand_device(self, d_records, n):
         torch = _torch()

@@ -153,6 +153,37 @@ extern "C" int rtk_dev_trace_rays_any_filtered(const rtk_dev_scene *ds, const rt
 	return rtk_launch_trace(ds, d_rays, n, nullptr, d_occluded, opts, (hipStream_t)stream, true, nullptr, filter);
 }
 
+// Listed batches (rtk_ray_list): everything about the list that the host can see is refused here, before anything is launched
+static int listed_trace(const char *who, const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t num_rays, const rtk_ray_list *list,
+	rtk_hit_record *d_hits, uint8_t *d_occluded, bool any_hit, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream)
+{
+	if (!list) { rtk_set_error("%s: NULL list", who); return RTK_AMD_ERR_BAD_ARG; }
+	if (list->struct_size < sizeof(rtk_ray_list)) { rtk_set_error("%s: rtk_ray_list.struct_size is too small", who); return RTK_AMD_ERR_BAD_ARG; }
+	if (list->flags != 0u) { rtk_set_error("%s: rtk_ray_list.flags must be 0", who); return RTK_AMD_ERR_BAD_ARG; }
+	if (!list->d_count) { rtk_set_error("%s: rtk_ray_list.d_count is NULL", who); return RTK_AMD_ERR_BAD_ARG; }
+	if (any_hit ? !d_occluded : !d_hits) { rtk_set_error("%s: NULL output", who); return RTK_AMD_ERR_BAD_ARG; }
+	if (num_rays >= ((size_t)1 << 32)) { rtk_set_error("%s: %zu rays: a listed batch holds fewer than 2^32", who, num_rays); return RTK_AMD_ERR_BAD_ARG; }
+	return rtk_launch_trace(ds, d_rays, num_rays, d_hits, d_occluded, opts, (hipStream_t)stream, any_hit, nullptr, filter, nullptr, nullptr, 0, nullptr, list);
+}
+
+extern "C" int rtk_dev_trace_rays_listed(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t num_rays, const rtk_ray_list *list,
+	rtk_hit_record *d_hits, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream)
+{
+	return listed_trace("rtk_dev_trace_rays_listed", ds, d_rays, num_rays, list, d_hits, nullptr, false, filter, opts, stream);
+}
+
+extern "C" int rtk_dev_trace_rays_any_listed(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t num_rays, const rtk_ray_list *list,
+	uint8_t *d_occluded, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream)
+{
+	return listed_trace("rtk_dev_trace_rays_any_listed", ds, d_rays, num_rays, list, nullptr, d_occluded, true, filter, opts, stream);
+}
+
+extern "C" int rtk_dev_select_rays(const rtk_dev_scene *ds, const void *d_src, uint32_t kind, size_t num_rays,
+	const rtk_ray_list *in, uint64_t *d_out_ids, uint64_t *d_out_count, void *stream)
+{
+	return rtk_launch_select(const_cast<rtk_dev_scene *>(ds), d_src, kind, num_rays, in, d_out_ids, d_out_count, (hipStream_t)stream);
+}
+
 extern "C" int rtk_dev_trace_rays_counted(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
 	rtk_hit_record *d_hits, const rtk_trace_opts *opts, rtk_trace_counters *out)
 {

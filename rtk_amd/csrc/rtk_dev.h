@@ -89,6 +89,8 @@ struct LaunchScratch {
 	volatile uint32_t *h_verdict = nullptr;     // pinned: where k_detect_check leaves (width, height) of an image nobody announced
 	uint32_t *d_leftover = nullptr;             // tiles the assembly packet kernel hands to the C++ one, or rays the assembly per-lane kernel hands to rtk_trace_kernel; grown on demand
 	size_t leftover_capacity = 0;               // bytes
+	void *d_select = nullptr;                   // rtk_dev_select_rays: keep masks, per-workgroup counts and their sums (rtk_select.hip), grown on demand
+	size_t select_capacity = 0;                 // bytes
 };
 
 // What a refit needs besides the scene (rtk_refit.hip): the node numbers grouped by HEIGHT (0: every child is a leaf or
@@ -299,7 +301,14 @@ bool rtk_sort_words_async(unsigned long long *keys_a, unsigned long long *keys_b
 int rtk_launch_trace(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, rtk_hit_record *d_hits,
 	uint8_t *d_occluded, const rtk_trace_opts *opts, hipStream_t stream, bool any_hit, rtk_trace_counters *counted,
 	const rtk_dev_filter *filter = nullptr, rtk_hit_record *d_cand = nullptr, uint32_t *d_cand_count = nullptr, uint32_t cand_k = 0,
-	rtk_packet_counters *pk_counted = nullptr);
+	rtk_packet_counters *pk_counted = nullptr, const rtk_ray_list *list = nullptr);
+// the scratch set of (scene, stream), made on first use (NULL: out of memory), and one of its buffers grown to `need` units in `bytes`
+// bytes; the caller holds ds->scratch_mutex until everything that uses the set is enqueued
+LaunchScratch *rtk_scratch_for(rtk_dev_scene *ds, hipStream_t stream);
+int rtk_scratch_grow(void **ptr, size_t *capacity, size_t need, size_t bytes, hipStream_t stream);
+// -- rtk_dev_select_rays (rtk_select.hip) --
+int rtk_launch_select(rtk_dev_scene *ds, const void *d_src, uint32_t kind, size_t num_rays, const rtk_ray_list *in, uint64_t *d_out_ids,
+	uint64_t *d_out_count, hipStream_t stream);
 // the entry-list pre-pass of a w x h frame alone; host_out receives (w / 64) * (h / 64) PkBlockEntries records (rtk_trace_shared.h). Synchronous.
 int rtk_debug_packet_entries(const rtk_dev_scene *ds, const rtk_ray *d_rays, uint32_t image_w, uint32_t image_h, uint32_t target, uint32_t max_levels, void *host_out);
 int rtk_detect_image(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, hipStream_t stream, uint32_t *w_out, uint32_t *h_out);

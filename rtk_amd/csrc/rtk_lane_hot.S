@@ -32,6 +32,9 @@
 //
 // Two kernels from one source: rtk_lane_hot_closest (16-byte hit records) and rtk_lane_hot_any (1 byte per ray).
 // Kernel argument: LnHotParams (rtk_trace_shared.h), 88 bytes. Launch: 256 threads (4 waves), persistent grid.
+// And their LISTED forms, rtk_lane_hot_closest_listed / rtk_lane_hot_any_listed (rtk_dev_trace_rays*_listed: the host does not know
+// how many rays the batch has): the same macro with listed = 1, LnHotListedParams = the 88 bytes and a pointer to an 8-byte count
+// at 88. They read the count when they start, take n = min(count, n of the argument) and are the same code from there on.
 // Registers: 88 VGPRs, 88 SGPRs + VCC. LDS: 30 KB per workgroup (4 waves x 15 entries x 64 lanes x 8 B): five per CU.
 
 	.amdgcn_target "amdgcn-amd-amdhsa--gfx950"
@@ -396,7 +399,7 @@ L_tri_next_\name\()_\sfx:
 	s_branch L_tri_\name\()_\sfx
 .endm
 
-.macro LANE_KERNEL name, anyhit
+.macro LANE_KERNEL name, anyhit, listed
 	.globl	\name
 	.p2align	8
 	.type	\name,@function
@@ -405,6 +408,9 @@ L_tri_next_\name\()_\sfx:
 	s_load_dwordx8 s[12:19], s[0:1], 0x20
 	s_load_dwordx2 s[20:21], s[0:1], 0x40
 	s_load_dwordx4 s[80:83], s[0:1], 0x48
+	.if \listed
+	s_load_dwordx2 s[86:87], s[0:1], 0x58       // where the batch's count is (s[86:87] is s_fm, free until the first leaf)
+	.endif
 	// LDS column of this lane: wave * (LDS_ENTRIES * ROW_BYTES) + lane * 8
 	v_and_b32_e32 v26, 63, v0
 	v_lshrrev_b32_e32 v27, 6, v0
@@ -433,6 +439,14 @@ L_tri_next_\name\()_\sfx:
 	s_mov_b32 s_c60, 0x5d800000
 	s_mov_b32 s_cm60, 0x21800000
 	s_waitcnt lgkmcnt(0)
+	.if \listed
+	// n = min(the count an earlier kernel or copy on this stream left, n): a count of 2^32 and more is "all of them"
+	s_load_dwordx2 s[86:87], s[86:87], 0x0
+	s_waitcnt lgkmcnt(0)
+	s_cmp_eq_u32 s87, 0
+	s_cselect_b32 s86, s86, s18
+	s_min_u32 s18, s18, s86
+	.endif
 	s_add_u32 s_chunks, s18, 63
 	s_lshr_b32 s_chunks, s_chunks, 6
 	s_add_u32 s_cpq, s_chunks, 7
@@ -831,15 +845,17 @@ L_end_\name:
 	.size	\name, .Lfunc_end_\name-\name
 .endm
 
-	LANE_KERNEL rtk_lane_hot_closest, 0
-	LANE_KERNEL rtk_lane_hot_any, 1
+	LANE_KERNEL rtk_lane_hot_closest, 0, 0
+	LANE_KERNEL rtk_lane_hot_any, 1, 0
+	LANE_KERNEL rtk_lane_hot_closest_listed, 0, 1
+	LANE_KERNEL rtk_lane_hot_any_listed, 1, 1
 
-.macro LANE_DESCRIPTOR name
+.macro LANE_DESCRIPTOR name, kernarg
 	.p2align	6
 	.amdhsa_kernel \name
 		.amdhsa_group_segment_fixed_size LDS_BYTES
 		.amdhsa_private_segment_fixed_size 0
-		.amdhsa_kernarg_size 88
+		.amdhsa_kernarg_size \kernarg
 		.amdhsa_user_sgpr_count 2
 		.amdhsa_user_sgpr_dispatch_ptr 0
 		.amdhsa_user_sgpr_queue_ptr 0
@@ -871,8 +887,10 @@ L_end_\name:
 .endm
 
 	.rodata
-	LANE_DESCRIPTOR rtk_lane_hot_closest
-	LANE_DESCRIPTOR rtk_lane_hot_any
+	LANE_DESCRIPTOR rtk_lane_hot_closest, 88
+	LANE_DESCRIPTOR rtk_lane_hot_any, 88
+	LANE_DESCRIPTOR rtk_lane_hot_closest_listed, 96
+	LANE_DESCRIPTOR rtk_lane_hot_any_listed, 96
 
 	.amdgpu_metadata
 ---
@@ -910,6 +928,44 @@ amdhsa.kernels:
     .sgpr_count:     90
     .sgpr_spill_count: 0
     .symbol:         rtk_lane_hot_any.kd
+    .uniform_work_group_size: 1
+    .uses_dynamic_stack: false
+    .vgpr_count:     88
+    .vgpr_spill_count: 0
+    .wavefront_size: 64
+  - .agpr_count:     0
+    .args:
+      - .offset:         0
+        .size:           96
+        .value_kind:     by_value
+    .group_segment_fixed_size: LDS_BYTES
+    .kernarg_segment_align: 8
+    .kernarg_segment_size: 96
+    .max_flat_workgroup_size: 256
+    .name:           rtk_lane_hot_closest_listed
+    .private_segment_fixed_size: 0
+    .sgpr_count:     90
+    .sgpr_spill_count: 0
+    .symbol:         rtk_lane_hot_closest_listed.kd
+    .uniform_work_group_size: 1
+    .uses_dynamic_stack: false
+    .vgpr_count:     88
+    .vgpr_spill_count: 0
+    .wavefront_size: 64
+  - .agpr_count:     0
+    .args:
+      - .offset:         0
+        .size:           96
+        .value_kind:     by_value
+    .group_segment_fixed_size: LDS_BYTES
+    .kernarg_segment_align: 8
+    .kernarg_segment_size: 96
+    .max_flat_workgroup_size: 256
+    .name:           rtk_lane_hot_any_listed
+    .private_segment_fixed_size: 0
+    .sgpr_count:     90
+    .sgpr_spill_count: 0
+    .symbol:         rtk_lane_hot_any_listed.kd
     .uniform_work_group_size: 1
     .uses_dynamic_stack: false
     .vgpr_count:     88

@@ -86,8 +86,9 @@ __global__ void __launch_bounds__(BLOCK_THREADS, PL_MIN_WAVES) rtk_trace_kernel(
 	const char *const qnodes = reinterpret_cast<const char *>(p.sc.qnodes);
 	const char *const tris = reinterpret_cast<const char *>(p.sc.tris);
 
-	// (a list whose length an earlier kernel of the launch wrote: the rays the assembly kernel, rtk_lane_hot.S, left over)
-	if (p.n_indirect) p.n = *p.n_indirect;
+	// (a list whose length earlier work on the stream wrote: the rays the assembly kernel, rtk_lane_hot.S, left over, or the caller's
+	// own list, rtk_ray_list. p.n is what the arrays hold: a larger count is clamped to it)
+	if (p.n_indirect) { const unsigned long long listed = *p.n_indirect; p.n = listed < p.n ? listed : p.n; }
 	// wave-uniform ray range owned by this wave
 	unsigned long long w_next, w_end;
 	bool pool_empty;
@@ -1008,8 +1009,9 @@ const TraceKnobs &rtk_trace_knobs()
 AsmModule &rtk_lane_module()
 {
 	// 80 VGPRs, 30 KB of LDS per workgroup: five workgroups per CU; the any-hit kernel is launched on the same figure
-	static const AsmKernel table[2] = { { "rtk_lane_hot_closest", rtk_trace_knobs().lane_blocks }, { "rtk_lane_hot_any", 0 } };
-	static AsmModule m(rtk_lane_hot_image, table, 2, "rtk_dev_trace: the assembly per-lane kernels are not loaded");
+	static const AsmKernel table[4] = { { "rtk_lane_hot_closest", rtk_trace_knobs().lane_blocks }, { "rtk_lane_hot_any", 0 },
+		{ "rtk_lane_hot_closest_listed", 0 }, { "rtk_lane_hot_any_listed", 0 } };
+	static AsmModule m(rtk_lane_hot_image, table, 4, "rtk_dev_trace: the assembly per-lane kernels are not loaded");
 	return m;
 }
 
@@ -1052,6 +1054,7 @@ void rtk_scratch_free(LaunchScratch *s)
 	if (s->d_sort) (void)hipFree(s->d_sort);
 	if (s->d_leftover) (void)hipFree(s->d_leftover);
 	if (s->d_entries) (void)hipFree(s->d_entries);
+	if (s->d_select) (void)hipFree(s->d_select);
 	delete s;
 }
 
@@ -1109,6 +1112,7 @@ DeviceKernels device_kernels(int device)
 	}
 	if (const AsmModule::Loaded *h = rtk_lane_module().on(device)) {
 		dk.lane = h->fn[0] && h->fn[1];
+		dk.lane_listed = h->fn[2] && h->fn[3];
 		dk.lane_blocks_per_cu = h->blocks_per_cu[0];
 	}
 	return dk;
@@ -1198,7 +1202,8 @@ int enqueue_packet_hot(const rtk_dev_scene *ds, LaunchScratch *sc, TraceParams &
 int enqueue_lane_hot(const rtk_dev_scene *ds, LaunchScratch *sc, const TraceParams &p, const TracePlan &plan, bool any_hit, bool refill_given,
 	const TraceKnobs &knobs, hipStream_t stream)
 {
-	LnHotParams hp = {};
+	LnHotListedParams lhp = {};
+	LnHotParams &hp = lhp.hot;
 	hp.qnodes = p.sc.qnodes; hp.tris = p.sc.tris; hp.rays = p.rays;
 	hp.out = any_hit ? (void *)p.occluded : (void *)p.hits;
 	hp.counter = p.counter;
@@ -1212,7 +1217,10 @@ int enqueue_lane_hot(const rtk_dev_scene *ds, LaunchScratch *sc, const TracePara
 	hp.spill = p.spill;
 	hp.spill_stride = p.spill_stride;
 	hp.spill_cap = p.spill_cap;
-	const int rc = rtk_lane_module().launch(ds->device, any_hit ? 1 : 0, &hp, sizeof(hp), (unsigned)plan.lane_grid, stream);
+	// (a listed batch: the kernel reads how many entries of `perm` -- or how many of the rays themselves -- it traces)
+	lhp.count = p.n_indirect;
+	const int rc = p.n_indirect ? rtk_lane_module().launch(ds->device, any_hit ? 3 : 2, &lhp, sizeof(lhp), (unsigned)plan.lane_grid, stream)
+		: rtk_lane_module().launch(ds->device, any_hit ? 1 : 0, &hp, sizeof(hp), (unsigned)plan.lane_grid, stream);
 	if (rc != RTK_AMD_OK) return rc;
 	if (knobs.lane_stats) {           // (diagnostics: how many rays the assembly kernel handed back; synchronises the stream)
 		unsigned long long left = 0;
@@ -1223,8 +1231,7 @@ int enqueue_lane_hot(const rtk_dev_scene *ds, LaunchScratch *sc, const TracePara
 	// (none in most batches: a small grid that finds an empty list costs next to nothing)
 	TraceParams lp = p;
 	lp.perm = hp.leftover;
-	lp.n_indirect = p.counter + RTK_LANE_LEFTOVER_WORD;
-	lp.n = 0;
+	lp.n_indirect = p.counter + RTK_LANE_LEFTOVER_WORD;      // (never more than the p.n it is clamped to: a ray is handed back once)
 	const size_t left_blocks = std::min<size_t>(plan.grid, (size_t)ds->num_cus);
 	hipLaunchKernelGGL(trace_variant(plan.variant), dim3((unsigned)left_blocks), dim3(BLOCK_THREADS), 0, stream, lp);
 	return RTK_AMD_OK;
@@ -1261,9 +1268,13 @@ int read_counters(LaunchScratch *sc, hipStream_t stream, rtk_trace_counters *out
 
 } // namespace
 
+LaunchScratch *rtk_scratch_for(rtk_dev_scene *ds, hipStream_t stream) { return scratch_for(ds, stream); }
+int rtk_scratch_grow(void **ptr, size_t *capacity, size_t need, size_t bytes, hipStream_t stream) { return grow(ptr, capacity, need, bytes, stream); }
+
 int rtk_launch_trace(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, size_t n, rtk_hit_record *d_hits,
 	uint8_t *d_occluded, const rtk_trace_opts *opts, hipStream_t stream, bool any_hit, rtk_trace_counters *counted,
-	const rtk_dev_filter *filter, rtk_hit_record *d_cand, uint32_t *d_cand_count, uint32_t cand_k, rtk_packet_counters *pk_counted)
+	const rtk_dev_filter *filter, rtk_hit_record *d_cand, uint32_t *d_cand_count, uint32_t cand_k, rtk_packet_counters *pk_counted,
+	const rtk_ray_list *list)
 {
 	rtk_dev_scene *ds = const_cast<rtk_dev_scene *>(ds_c);
 	const bool collect = d_cand != nullptr;
@@ -1271,6 +1282,8 @@ int rtk_launch_trace(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, size_t n,
 	if (pk_counted) *pk_counted = rtk_packet_counters();
 	if (collect && (!d_cand_count || cand_k == 0 || any_hit || counted)) { rtk_set_error("rtk_dev_trace: bad collect arguments"); return RTK_AMD_ERR_BAD_ARG; }
 	if (!ds || (!d_rays && n) || (!collect && (any_hit ? !d_occluded : !d_hits) && n)) { rtk_set_error("rtk_dev_trace: bad argument"); return RTK_AMD_ERR_BAD_ARG; }
+	// (a listed batch: rtk_dev_trace_rays*_listed have checked the list; n is the size of the arrays, below 2^32)
+	if (list && (counted || pk_counted || collect)) { rtk_set_error("rtk_dev_trace: a ray list with a counted or collecting launch"); return RTK_AMD_ERR_BAD_ARG; }
 	if (n == 0) { if (counted) *counted = rtk_trace_counters(); return RTK_AMD_OK; }
 	if (!on_scene_device(ds, "rtk_dev_trace")) return RTK_AMD_ERR_BAD_ARG;
 	if (!within_4gib(ds->view)) {
@@ -1286,6 +1299,7 @@ int rtk_launch_trace(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, size_t n,
 	p.cand_count = d_cand_count;
 	p.cand_k = cand_k;
 	p.n = n;
+	if (list) { p.perm = reinterpret_cast<const unsigned long long *>(list->d_ids); p.n_indirect = reinterpret_cast<const unsigned long long *>(list->d_count); }
 	if (filter) {
 		if (filter->struct_size < sizeof(rtk_dev_filter)) { rtk_set_error("rtk_dev_trace: rtk_dev_filter.struct_size is too small"); return RTK_AMD_ERR_BAD_ARG; }
 		if (filter->d_mesh_mask && filter->mesh_mask_bits == 0) { rtk_set_error("rtk_dev_trace: mesh mask without mesh_mask_bits"); return RTK_AMD_ERR_BAD_ARG; }
@@ -1301,6 +1315,7 @@ int rtk_launch_trace(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, size_t n,
 	TraceRequest rq;
 	rq.n = n; rq.any_hit = any_hit; rq.counted = counted != nullptr; rq.pk_counted = pk_counted != nullptr; rq.collect = collect;
 	rq.filtered = p.mesh_mask || p.ignore_prim || p.after; rq.has_filter = filter != nullptr;
+	rq.listed = list != nullptr;
 	SceneFacts facts;
 	facts.num_nodes = ds->view.num_nodes; facts.num_tris = ds->view.num_tris; facts.has_qnodes = ds->view.qnodes != nullptr;
 	facts.stack_entries = ds->tree.stack_entries(); facts.bound_abs = ds->tree.bound_abs; facts.big_leaf_fraction = ds->tree.big_leaf_fraction;

@@ -100,6 +100,7 @@ struct DeviceKernels {
 	bool packet[NUM_PACKET_KERNELS] = {};
 	int packet_blocks_per_cu[NUM_PACKET_KERNELS] = {};
 	bool lane = false;             // rtk_lane_hot_closest and rtk_lane_hot_any
+	bool lane_listed = false;      // rtk_lane_hot_closest_listed and rtk_lane_hot_any_listed (the count of the batch read on the device)
 	int lane_blocks_per_cu = 0;
 	bool has(PacketKernel k) const { return k >= PacketKernel::Hot && packet[(int)k]; }
 };
@@ -113,6 +114,7 @@ struct TraceRequest {
 	bool collect = false;          // the k closest candidates per ray (host-callback filters)
 	bool filtered = false;         // a built-in filter is set (mesh mask, ignored primitive, "after")
 	bool has_filter = false;       // a rtk_dev_filter came with the call, set or not
+	bool listed = false;           // rtk_dev_trace_rays*_listed: n is the size of the arrays, how many rays are traced is read on the device
 };
 
 struct TracePlan {
@@ -145,6 +147,15 @@ inline bool hinted_image(const TraceRequest &rq, const TraceOpts &o)
 	return o.image_w && o.image_h && (size_t)o.image_w * o.image_h == rq.n && (o.image_w % 8u) == 0 && (o.image_h % 8u) == 0;
 }
 
+// A listed batch (rtk_ray_list) is no image, is not re-ordered and is always dealt from the queues (the host does not know how
+// many of its rays are traced): the options as such a batch reads them, the image hint and the two flags taken out.
+inline TraceOpts listed_opts(TraceOpts o)
+{
+	o.image_w = o.image_h = 0;
+	o.flags &= ~(uint32_t)(RTK_TRACE_SORT_RAYS | RTK_TRACE_STATIC);
+	return o;
+}
+
 // a batch that fits one workgroup needs no work queue (and no counter reset)
 inline bool dynamic_launch(const TraceRequest &rq, const TraceOpts &o) { return rq.n > TRACE_BLOCK_THREADS && !(o.flags & RTK_TRACE_STATIC); }
 
@@ -153,17 +164,21 @@ inline bool dynamic_launch(const TraceRequest &rq, const TraceOpts &o) { return 
 // stands between this batch and the host's next enqueue: a caller that knows its image says so in the options).
 inline bool wants_image_look(const TraceRequest &rq, const TraceOpts &o, const SceneFacts &f, const TraceKnobs &k)
 {
-	return k.detect_image != 0 && !hinted_image(rq, o) && !rq.has_filter && !rq.collect && !rq.counted && !rq.pk_counted &&
+	return !rq.listed && k.detect_image != 0 && !hinted_image(rq, o) && !rq.has_filter && !rq.collect && !rq.counted && !rq.pk_counted &&
 		rq.n >= 16384u && (rq.n % 4096u) == 0u && rq.n <= 0x40000000ull && dynamic_launch(rq, o) && f.stack_entries <= 64 &&
 		!(o.flags & (RTK_TRACE_NO_DETECT | RTK_TRACE_NO_PACKET | RTK_TRACE_SORT_RAYS | RTK_TRACE_STATIC));
 }
 
 // Everything of the plan that needs no occupancy figure. look_w x look_h: what the image look found (0 x 0: nothing, or not asked).
-inline TracePlan plan_kernels(const TraceRequest &rq, const TraceOpts &o, uint32_t look_w, uint32_t look_h, const SceneFacts &f,
+inline TracePlan plan_kernels(const TraceRequest &rq, const TraceOpts &o_given, uint32_t look_w, uint32_t look_h, const SceneFacts &f,
 	const DeviceKernels &dk, const TraceKnobs &k)
 {
 	TracePlan pl;
-	pl.dynamic = dynamic_launch(rq, o) ? 1u : 0u;
+	const TraceOpts o = rq.listed ? listed_opts(o_given) : o_given;
+	if (rq.listed) look_w = look_h = 0u;
+	// (the assembly per-lane kernels take the batches a queue-fed launch of the plain call takes: more than one workgroup of rays)
+	const bool many = dynamic_launch(rq, o);
+	pl.dynamic = (many || rq.listed) ? 1u : 0u;
 	// Defaults from sweeps on MI355X (profiles/r01_sweep_opts*.log, r02_ab_r2o/p.log): leave the node
 	// loop once fewer than 32 lanes still descend (24 for image-shaped batches); image-shaped (tiled, coherent)
 	// batches refill a wave only when it is empty, everything else as soon as 8 lanes are idle.
@@ -215,10 +230,10 @@ inline TracePlan plan_kernels(const TraceRequest &rq, const TraceOpts &o, uint32
 	// Plain closest-hit / any-hit batches on compressed nodes go to the hand-written per-lane kernels (rtk_lane_hot.S); the rays
 	// they hand back (not tame, a leaf of four or more triangles, a stack deeper than the LDS column) follow in rtk_trace_kernel.
 	// Byte offsets into nodes, triangles, rays and the ray order are 32-bit and kept below 2^31 there.
-	pl.lane_hot = !pl.packet && !rq.collect && !rq.counted && !rq.filtered && pl.qn && pl.dynamic && pl.image_w == 0 && k.lane_asm != 0 &&
+	pl.lane_hot = !pl.packet && !rq.collect && !rq.counted && !rq.filtered && pl.qn && many && pl.image_w == 0 && k.lane_asm != 0 &&
 		f.tri_stride == 48 && rq.n <= ((size_t)1 << 26) && (uint64_t)f.num_nodes * 64u < 0x80000000ull &&
 		(uint64_t)f.num_tris * f.tri_stride < 0x80000000ull && f.bound_abs < 0x1p60f && (!rq.any_hit || f.big_leaf_fraction <= 0.02) &&
-		!(o.flags & (RTK_TRACE_NO_ASM | RTK_TRACE_STATIC)) && f.stack_entries < 512u && dk.lane;
+		!(o.flags & (RTK_TRACE_NO_ASM | RTK_TRACE_STATIC)) && f.stack_entries < 512u && (rq.listed ? dk.lane_listed : dk.lane);
 	// entry points shared by the tiles of a 64x64-pixel block (rtk_packet_entries_kernel, one small launch ahead of the traversal)
 	pl.entries = pl.packet && pl.tile_blocks && k.packet_entries != 0 && f.bound_abs < 0x1p19f && f.num_nodes != 0u && !(o.flags & RTK_TRACE_NO_ENTRIES);
 	// optional ray reordering pre-pass (per-lane kernels only)

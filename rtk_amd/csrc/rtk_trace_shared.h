@@ -35,8 +35,9 @@ struct TraceParams {
 	uint32_t *cand_count;          // MODE 2: how many of them are valid
 	uint32_t cand_k;
 	uint32_t tile_blocks;          // image batches: tiles are numbered block by block (8x8 tiles = 64x64 pixels), not row by row
-	const unsigned long long *n_indirect;   // rtk_trace_kernel: if set, the number of rays is read from here when the kernel starts (the list the assembly
-	                                        // per-lane kernel left over: `perm` then points at it, its length is counter[RTK_LANE_LEFTOVER_WORD])
+	const unsigned long long *n_indirect;   // rtk_trace_kernel: if set, the number of rays is read from here when the kernel starts and clamped to n: the list the
+	                                        // assembly per-lane kernel left over (`perm` then points at it, its length is counter[RTK_LANE_LEFTOVER_WORD]),
+	                                        // or the caller's own (rtk_ray_list: `perm` = d_ids or NULL, n = the size of the arrays)
 	const struct PkBlockEntries *entries;   // packet kernels only: per 64x64-pixel block the entry points of its rays (or NULL: every tile starts at the root)
 	const uint32_t *tile_list;     // packet kernel only: trace the tiles listed here (counter[RTK_LEFTOVER_COUNT_WORD] of them, dealt through
 	                               // counter[RTK_LEFTOVER_HEAD_WORD]) instead of all tiles: what the assembly kernel handed back
@@ -105,6 +106,12 @@ struct LnHotParams {
 };
 static_assert(sizeof(LnHotParams) == 88 && offsetof(LnHotParams, n) == 56 && offsetof(LnHotParams, bound_abs) == 68 && offsetof(LnHotParams, spill) == 72 &&
 	offsetof(LnHotParams, spill_cap) == 84, "rtk_lane_hot.S reads this layout");
+// ... and of their listed forms, rtk_lane_hot_closest_listed / rtk_lane_hot_any_listed: n = min(*count, hot.n), read by the kernel
+struct LnHotListedParams {
+	LnHotParams hot;
+	const unsigned long long *count;   // 88
+};
+static_assert(sizeof(LnHotListedParams) == 96 && offsetof(LnHotListedParams, count) == 88, "rtk_lane_hot.S reads this layout");
 
 // DevTri.flags: bit 0 = last triangle of its leaf, bits 8.. = mesh index (for the mesh-mask filter)
 #define RTK_TRI_MESH_SHIFT 8
@@ -169,5 +176,5 @@ struct AsmModule {
 	const Loaded *on(int device);
 	int launch(int device, int kernel, void *params, size_t size, unsigned blocks, hipStream_t stream);
 };
-AsmModule &rtk_lane_module();      // rtk_lane_hot.S: 0 rtk_lane_hot_closest, 1 rtk_lane_hot_any (rtk_trace.hip)
+AsmModule &rtk_lane_module();      // rtk_lane_hot.S: 0 rtk_lane_hot_closest, 1 rtk_lane_hot_any, 2 and 3 their listed forms (rtk_trace.hip)
 AsmModule &rtk_packet_module();    // rtk_packet_hot.S, rtk_packet_beam2.S: kernels numbered by PacketKernel (rtk_trace_packet.hip)
