@@ -1,9 +1,10 @@
 // rtk_capi.hip -- the C-ABI of librtk_amd.so: the nine rtk.h entry points plus the
 // additive batch/device surface of rtk_amd.h. Thin: argument checks, residency cache,
 // HIP plumbing. No intersection arithmetic lives here and there is no CPU fallback:
-// every trace call runs the HIP kernels of rtk_trace.hip or fails with an error.
+// every trace call runs the HIP kernels behind rtk_launch.hip or fails with an error.
 #include "rtk_dev.h"
 #include "rtk_trace_plan.h"
+#include "rtk_detect_rule.h"
 
 #include <algorithm>
 #include "rtk_layout_check.h"
@@ -89,8 +90,7 @@ extern "C" void rtk_dev_scene_free(rtk_dev_scene *ds)
 	if (!ds) return;
 	rtk_scene_forget_derived(ds, RTK_FORGET_BOXES | RTK_FORGET_TREE);
 	ds->mem.release_all();
-	for (LaunchScratch *s : ds->scratch) rtk_scratch_free(s);
-	delete ds;
+	delete ds;                         // (with its launch scratch: ScratchSets)
 }
 
 extern "C" int rtk_dev_scene_get_info(const rtk_dev_scene *ds, rtk_dev_scene_info *info)
@@ -129,28 +129,44 @@ extern "C" long long rtk_dev_scene_primitive_order(const rtk_dev_scene *ds, uint
 
 // ---------------------------------------------------------------------------- batches
 
+// what every batch call says; the rest of a TraceCall stays "not given" unless the entry point means it
+static TraceCall batch_call(const rtk_ray *d_rays, size_t n, const rtk_trace_opts *opts, void *stream)
+{
+	TraceCall c;
+	c.rays = d_rays; c.n = n; c.opts = opts; c.stream = (hipStream_t)stream;
+	return c;
+}
+
 extern "C" int rtk_dev_trace_rays(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
 	rtk_hit_record *d_hits, const rtk_trace_opts *opts, void *stream)
 {
-	return rtk_launch_trace(ds, d_rays, n, d_hits, nullptr, opts, (hipStream_t)stream, false, nullptr);
+	TraceCall c = batch_call(d_rays, n, opts, stream);
+	c.hits = d_hits;
+	return rtk_launch_trace(ds, c);
 }
 
 extern "C" int rtk_dev_trace_rays_any(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
 	uint8_t *d_occluded, const rtk_trace_opts *opts, void *stream)
 {
-	return rtk_launch_trace(ds, d_rays, n, nullptr, d_occluded, opts, (hipStream_t)stream, true, nullptr);
+	TraceCall c = batch_call(d_rays, n, opts, stream);
+	c.occluded = d_occluded; c.any_hit = true;
+	return rtk_launch_trace(ds, c);
 }
 
 extern "C" int rtk_dev_trace_rays_filtered(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
 	rtk_hit_record *d_hits, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream)
 {
-	return rtk_launch_trace(ds, d_rays, n, d_hits, nullptr, opts, (hipStream_t)stream, false, nullptr, filter);
+	TraceCall c = batch_call(d_rays, n, opts, stream);
+	c.hits = d_hits; c.filter = filter;
+	return rtk_launch_trace(ds, c);
 }
 
 extern "C" int rtk_dev_trace_rays_any_filtered(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
 	uint8_t *d_occluded, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream)
 {
-	return rtk_launch_trace(ds, d_rays, n, nullptr, d_occluded, opts, (hipStream_t)stream, true, nullptr, filter);
+	TraceCall c = batch_call(d_rays, n, opts, stream);
+	c.occluded = d_occluded; c.any_hit = true; c.filter = filter;
+	return rtk_launch_trace(ds, c);
 }
 
 // Listed batches (rtk_ray_list): everything about the list that the host can see is refused here, before anything is launched
@@ -163,7 +179,9 @@ static int listed_trace(const char *who, const rtk_dev_scene *ds, const rtk_ray 
 	if (!list->d_count) { rtk_set_error("%s: rtk_ray_list.d_count is NULL", who); return RTK_AMD_ERR_BAD_ARG; }
 	if (any_hit ? !d_occluded : !d_hits) { rtk_set_error("%s: NULL output", who); return RTK_AMD_ERR_BAD_ARG; }
 	if (num_rays >= ((size_t)1 << 32)) { rtk_set_error("%s: %zu rays: a listed batch holds fewer than 2^32", who, num_rays); return RTK_AMD_ERR_BAD_ARG; }
-	return rtk_launch_trace(ds, d_rays, num_rays, d_hits, d_occluded, opts, (hipStream_t)stream, any_hit, nullptr, filter, nullptr, nullptr, 0, nullptr, list);
+	TraceCall c = batch_call(d_rays, num_rays, opts, stream);
+	c.hits = d_hits; c.occluded = d_occluded; c.any_hit = any_hit; c.filter = filter; c.list = list;
+	return rtk_launch_trace(ds, c);
 }
 
 extern "C" int rtk_dev_trace_rays_listed(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t num_rays, const rtk_ray_list *list,
@@ -188,21 +206,27 @@ extern "C" int rtk_dev_trace_rays_counted(const rtk_dev_scene *ds, const rtk_ray
 	rtk_hit_record *d_hits, const rtk_trace_opts *opts, rtk_trace_counters *out)
 {
 	if (!out) { rtk_set_error("rtk_dev_trace_rays_counted: NULL counters"); return RTK_AMD_ERR_BAD_ARG; }
-	return rtk_launch_trace(ds, d_rays, n, d_hits, nullptr, opts, nullptr, false, out);
+	TraceCall c = batch_call(d_rays, n, opts, nullptr);
+	c.hits = d_hits; c.counted = out;
+	return rtk_launch_trace(ds, c);
 }
 
 extern "C" int rtk_dev_trace_rays_any_counted(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
 	uint8_t *d_occluded, const rtk_trace_opts *opts, rtk_trace_counters *out)
 {
 	if (!out) { rtk_set_error("rtk_dev_trace_rays_any_counted: NULL counters"); return RTK_AMD_ERR_BAD_ARG; }
-	return rtk_launch_trace(ds, d_rays, n, nullptr, d_occluded, opts, nullptr, true, out);
+	TraceCall c = batch_call(d_rays, n, opts, nullptr);
+	c.occluded = d_occluded; c.any_hit = true; c.counted = out;
+	return rtk_launch_trace(ds, c);
 }
 
 extern "C" int rtk_dev_trace_rays_packet_counted(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
 	rtk_hit_record *d_hits, const rtk_trace_opts *opts, rtk_packet_counters *out)
 {
 	if (!out) { rtk_set_error("rtk_dev_trace_rays_packet_counted: NULL counters"); return RTK_AMD_ERR_BAD_ARG; }
-	return rtk_launch_trace(ds, d_rays, n, d_hits, nullptr, opts, nullptr, false, nullptr, nullptr, nullptr, nullptr, 0, out);
+	TraceCall c = batch_call(d_rays, n, opts, nullptr);
+	c.hits = d_hits; c.pk_counted = out;
+	return rtk_launch_trace(ds, c);
 }
 
 extern "C" int rtk_dev_debug_packet_entries(const rtk_dev_scene *ds, const rtk_ray *d_rays, uint32_t image_w, uint32_t image_h,
@@ -491,7 +515,9 @@ bool enqueue_piece(rtk_dev_scene *ds, HostCtx &c, const rtk_ray *rays, size_t n,
 		if (hipMemcpyAsync(c.d_after, c.h_after, n * sizeof(rtk_hit_record), hipMemcpyHostToDevice, c.stream) != hipSuccess) { rtk_set_error("rtk_trace_rays: H2D copy failed"); return false; }
 		f.d_after = c.d_after;
 	}
-	if (rtk_launch_trace(ds, d_rays, n, c.d_rec, nullptr, opts, c.stream, false, nullptr, with_after ? &f : nullptr) != RTK_AMD_OK) return false;
+	TraceCall call = batch_call(d_rays, n, opts, c.stream);
+	call.hits = c.d_rec; call.filter = with_after ? &f : nullptr;
+	if (rtk_launch_trace(ds, call) != RTK_AMD_OK) return false;
 	c.status_mirrored = false;
 	if (zero_copy) {
 		c.ticket_in_flight = 0;
@@ -563,41 +589,6 @@ size_t trace_one(rtk_dev_scene *ds, HostCtx &c, const rtk_ray *ray, rtk_hit *hit
 	return m ? 1 : 0;
 }
 
-// The look of rtk_dev_trace_rays for an un-announced image (rtk_trace.hip, k_detect_row / k_detect_check), on host rays: the step
-// from ray to ray (origin and direction) is regular and jumps at the same distance every time. A batch of host rays is cut into
-// pieces for the staging buffers; an image is cut into bands of whole 64-pixel rows so that every piece is an image the packet
-// kernels take.
-bool host_step_jumps(const rtk_ray *rays, size_t i)
-{
-	const float *a = reinterpret_cast<const float *>(rays + i - 1), *b = reinterpret_cast<const float *>(rays + i), *c = reinterpret_cast<const float *>(rays + i + 1);
-	float m = 0.0f, dmax = 0.0f;
-	for (int k = 0; k < 6; k++) {
-		const float s0 = b[k] - a[k], s1 = c[k] - b[k];
-		m = fabsf(s0) > m ? fabsf(s0) : m;
-		dmax = fabsf(s1 - s0) > dmax ? fabsf(s1 - s0) : dmax;
-	}
-	return !(dmax <= 8.0f * m);
-}
-
-void host_detect_image(const rtk_ray *rays, size_t n, uint32_t *w_out, uint32_t *h_out)
-{
-	*w_out = *h_out = 0u;
-	if (n < 4 || n > 0x40000000ull) return;
-	const size_t limit = n < ((size_t)1 << 17) ? n : ((size_t)1 << 17);
-	size_t first = 0;
-	for (size_t i = 1; i + 1 < limit; i++) if (host_step_jumps(rays, i)) { first = i; break; }
-	const size_t w = first + 1;
-	if (!first || w < 64 || (n % w) != 0 || n / w < 2 || n / w > 0xffffffffull) return;
-	const size_t rows = n / w, stride = rows > 256 ? rows / 256 : 1;
-	for (size_t k = 0; k < 256; k++) {
-		const size_t r = k * stride;
-		if (r + 1 >= rows) break;
-		if (!host_step_jumps(rays, (r + 1) * w - 1)) return;
-		for (size_t q = 1; q < 4; q++) if (host_step_jumps(rays, r * w + q * (w / 4))) return;
-	}
-	*w_out = (uint32_t)w;
-	*h_out = (uint32_t)rows;
-}
 
 std::atomic<int> g_test_fail_calls{0};
 // Fault injection for the tests of the per-ray calls' failure reporting. Not in the installed header; a no-op unless the process
@@ -636,14 +627,14 @@ extern "C" size_t rtk_trace_rays(const rtk_scene *scene, const rtk_ray *rays, si
 	}
 	// Two staging sets on two streams: while the GPU works on one piece the host copies the previous piece's results out
 	// and the next piece's rays in (both single-threaded memcpy-speed work that used to sit between the launches).
-	// An image (recognised by its regular step, as rtk_dev_trace_rays does for device rays) goes in bands of whole 64-pixel rows, each
+	// An image (recognised by its regular step, as rtk_dev_trace_rays does for device rays: rtk_detect_rule.h) goes in bands of whole 64-pixel rows, each
 	// announced to the launch as the image it is: the packet kernels instead of one ray per lane.
 	size_t PIPE_CHUNK = PIPE_CHUNK_RAYS;
 	rtk_trace_opts band_opts;
 	const rtk_trace_opts *piece_opts = nullptr;
 	{
 		uint32_t iw = 0, ih = 0;
-		if (rtk_trace_knobs().detect_image != 0) host_detect_image(rays, n, &iw, &ih);
+		if (rtk_trace_knobs().detect_image != 0) rtk_detect_host(rays, n, &iw, &ih);
 		if (iw >= 128u && whole_blocks(iw, ih) && (size_t)iw * 64u <= ((size_t)1 << 21)) {
 			size_t band_rows = 64;
 			while ((band_rows * 2) * (size_t)iw <= ((size_t)1 << 18) && band_rows * 2 <= ih) band_rows *= 2;
@@ -726,7 +717,9 @@ extern "C" size_t rtk_trace_rays_filter(const rtk_scene *scene, const rtk_ray *r
 			f.d_after = c.d_after;
 			// unused list slots stay "no primitive" so that the expand kernel leaves them alone
 			if (hipMemsetAsync(c.d_cand, 0xff, r * k * sizeof(rtk_hit_record), c.stream) != hipSuccess) { rtk_set_error("rtk_trace_rays_filter: memset failed"); return (size_t)-1; }
-			if (rtk_launch_trace(ds, c.d_rays, r, nullptr, nullptr, nullptr, c.stream, false, nullptr, &f, c.d_cand, c.d_cand_count, (uint32_t)k) != RTK_AMD_OK) return (size_t)-1;
+			TraceCall call = batch_call(c.d_rays, r, nullptr, c.stream);
+			call.filter = &f; call.cand = c.d_cand; call.cand_count = c.d_cand_count; call.cand_k = (uint32_t)k;
+			if (rtk_launch_trace(ds, call) != RTK_AMD_OK) return (size_t)-1;
 			if (rtk_launch_expand(ds, c.d_cand, r * k, c.d_cand_hits, nullptr, c.stream) != RTK_AMD_OK) return (size_t)-1;
 			ok = hipMemcpyAsync(c.h_cand, c.d_cand, r * k * sizeof(rtk_hit_record), hipMemcpyDeviceToHost, c.stream) == hipSuccess &&
 				hipMemcpyAsync(c.h_cand_hits, c.d_cand_hits, r * k * sizeof(rtk_hit), hipMemcpyDeviceToHost, c.stream) == hipSuccess &&

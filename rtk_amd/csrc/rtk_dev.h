@@ -21,6 +21,7 @@
 #include "rtk_carve.h"
 #include "rtk_node.h"       // DevNode, DevNodeQ, RTK_REF_NONE, RTK_REF_LEAF
 #include "rtk_scene_mem.h"
+#include "rtk_launch_scratch.h"   // LaunchScratch, ScratchSets
 
 #define RTK_MAX_DEVICES 64       // per-device tables (workspaces, cached properties)
 #define RTK_TRI_LAST 1u           // DevTri.flags: last triangle of its leaf
@@ -32,6 +33,9 @@
 // non-zero: a traversal stack overflowed (cannot happen for a validated tree). One word past the ones a launch clears: it
 // stays set until rtk_trace_status has reported it.
 #define RTK_ERROR_WORD RTK_COUNTER_WORDS
+// ... and behind it the words of the image look (rtk_detect.hip)
+#define RTK_DETECT_WORDS 4
+#define RTK_DETECT_WORD (RTK_ERROR_WORD + 1)
 
 // 48 B of payload at a stride of RTK_TRI_STRIDE bytes. At 48 a record straddles two 128-B lines three times in
 // eight (and two 64-B scalar-cache lines every other time); at 64 it never does, for 16 B more per triangle.
@@ -69,28 +73,6 @@ struct DevSceneView {
 	uint32_t num_nodes;
 	uint32_t num_tris;
 	uint32_t num_prims;
-};
-
-// Device memory a launch writes besides its outputs: work-queue heads and visit counters, the global
-// part of the traversal stacks, and the ray-reordering buffers. One set per (scene, stream): launches on
-// one stream are ordered by the stream, launches on different streams (or from different host threads)
-// never share a set, so tracing one scene from many threads is safe (the reference's rtk_trace_ray is a
-// pure function of a const scene, rtk.c:543-577).
-struct LaunchScratch {
-	hipStream_t stream = nullptr;
-	unsigned long long *d_counter = nullptr;   // RTK_COUNTER_WORDS
-	uint2 *d_spill = nullptr;
-	size_t spill_entries_per_lane = 0;
-	size_t spill_lanes = 0;
-	void *d_sort = nullptr;                     // ray reordering scratch (RTK_TRACE_SORT_RAYS), grown on demand
-	size_t sort_capacity = 0;                   // rays
-	void *d_entries = nullptr;                  // packet kernels: entry lists of the image's 64x64-pixel blocks (PkBlockEntries), grown on demand
-	size_t entries_capacity = 0;                // blocks
-	volatile uint32_t *h_verdict = nullptr;     // pinned: where k_detect_check leaves (width, height) of an image nobody announced
-	uint32_t *d_leftover = nullptr;             // tiles the assembly packet kernel hands to the C++ one, or rays the assembly per-lane kernel hands to rtk_trace_kernel; grown on demand
-	size_t leftover_capacity = 0;               // bytes
-	void *d_select = nullptr;                   // rtk_dev_select_rays: keep masks, per-workgroup counts and their sums (rtk_select.hip), grown on demand
-	size_t select_capacity = 0;                 // bytes
 };
 
 // What a refit needs besides the scene (rtk_refit.hip): the node numbers grouped by HEIGHT (0: every child is a leaf or
@@ -153,7 +135,10 @@ struct SceneTree {
 	const uint32_t *d_vidx_in = nullptr;       // [3 * prim + k] original vertex indices in input order; NULL: every mesh has implicit indices
 	const unsigned long long *d_mesh_base = nullptr;   // num_meshes + 1, on the device (made by a build or a rebuild; NULL: a blob as it was uploaded)
 	uint32_t stack_entries() const { return 3u * max_depth + 1u; }   // traversal stack entries a ray can need: at most three pushes per level of descent
+	float bound_floor1() const { return bound_abs > 1.0f ? bound_abs : 1.0f; }   // what the packet kernels' slab margins are relative to (empty slots carry +1 / -1)
 };
+
+const ScratchHooks &rtk_scratch_hooks();       // hipMalloc / hipFree / hipStreamSynchronize (rtk_launch.hip)
 
 struct rtk_dev_scene {
 	int device = 0;
@@ -164,9 +149,9 @@ struct rtk_dev_scene {
 	double build_ms = 0.0;
 	// owned device allocations, and what each adds to total_device_bytes (rtk_scene_mem.h)
 	SceneMem mem{ rtk_dev_malloc, rtk_dev_free };
-	// per-stream launch scratch, created on first use; the mutex covers the list and the enqueue of a launch
+	// per-stream launch scratch, created on first use (rtk_launch_scratch.h); the mutex covers the collection and the enqueue of a launch
 	std::mutex scratch_mutex;
-	std::vector<LaunchScratch *> scratch;
+	ScratchSets scratch{ rtk_scratch_hooks() };
 	int num_cus = 0;
 	// Device-built scenes make the four side arrays of the view (vertex_index, prim_slot, slot_mesh, slot_tri: what the expansion of
 	// hit records, the validator and the exporter read -- never a traversal) on first use, not in every build: 52 of the 100
@@ -297,24 +282,40 @@ bool rtk_sort_pairs_async(unsigned long long *keys_a, unsigned long long *keys_b
 bool rtk_sort_words_async(unsigned long long *keys_a, unsigned long long *keys_b, uint32_t n, uint32_t first_bit, uint32_t last_bit,
 	uint32_t *scratch, hipStream_t stream);
 
-// -- trace launches (rtk_trace.hip) --
-int rtk_launch_trace(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, rtk_hit_record *d_hits,
-	uint8_t *d_occluded, const rtk_trace_opts *opts, hipStream_t stream, bool any_hit, rtk_trace_counters *counted,
-	const rtk_dev_filter *filter = nullptr, rtk_hit_record *d_cand = nullptr, uint32_t *d_cand_count = nullptr, uint32_t cand_k = 0,
-	rtk_packet_counters *pk_counted = nullptr, const rtk_ray_list *list = nullptr);
-// the scratch set of (scene, stream), made on first use (NULL: out of memory), and one of its buffers grown to `need` units in `bytes`
-// bytes; the caller holds ds->scratch_mutex until everything that uses the set is enqueued
-LaunchScratch *rtk_scratch_for(rtk_dev_scene *ds, hipStream_t stream);
-int rtk_scratch_grow(void **ptr, size_t *capacity, size_t need, size_t bytes, hipStream_t stream);
+// -- trace launches (rtk_launch.hip) --
+// One launch: every field starts as "not given", a caller sets the ones it means.
+struct TraceCall {
+	const rtk_ray *rays = nullptr;
+	size_t n = 0;
+	rtk_hit_record *hits = nullptr;            // closest hit: one record per ray
+	uint8_t *occluded = nullptr;               // any hit: one byte per ray
+	const rtk_trace_opts *opts = nullptr;
+	hipStream_t stream = nullptr;
+	bool any_hit = false;
+	rtk_trace_counters *counted = nullptr;     // rtk_dev_trace_rays*_counted (synchronises the stream)
+	const rtk_dev_filter *filter = nullptr;
+	rtk_hit_record *cand = nullptr;            // collect the cand_k closest candidates per ray (host-callback filters) ...
+	uint32_t *cand_count = nullptr;            // ... and how many of them are valid
+	uint32_t cand_k = 0;
+	rtk_packet_counters *pk_counted = nullptr; // rtk_dev_trace_rays_packet_counted (synchronises the stream)
+	const rtk_ray_list *list = nullptr;        // rtk_dev_trace_rays*_listed have checked it; n is the size of the arrays, below 2^32
+};
+int rtk_launch_trace(const rtk_dev_scene *ds, const TraceCall &call);
+// the scene's memory, its scratch and the stream must all belong to the device this thread has current: a launch from a
+// thread on another GPU would read the scene across devices (a fault without peer access). false: rtk_set_error has said so
+bool rtk_on_scene_device(const rtk_dev_scene *ds, const char *caller);
+// the launch-error word of (scene, stream), or NULL: nothing was launched there yet. Takes scratch_mutex.
+unsigned long long *rtk_error_word(rtk_dev_scene *ds, hipStream_t stream);
+// the entry-list pre-pass of a w x h frame alone; host_out receives (w / 64) * (h / 64) PkBlockEntries records (rtk_trace_shared.h). Synchronous.
+int rtk_debug_packet_entries(const rtk_dev_scene *ds, const rtk_ray *d_rays, uint32_t image_w, uint32_t image_h, uint32_t target, uint32_t max_levels, void *host_out);
+int rtk_trace_status(const rtk_dev_scene *ds, hipStream_t stream);
+void rtk_scene_drop_stream(rtk_dev_scene *ds, hipStream_t stream);   // the stream is about to be destroyed (and has been synchronised)
 // -- rtk_dev_select_rays (rtk_select.hip) --
 int rtk_launch_select(rtk_dev_scene *ds, const void *d_src, uint32_t kind, size_t num_rays, const rtk_ray_list *in, uint64_t *d_out_ids,
 	uint64_t *d_out_count, hipStream_t stream);
-// the entry-list pre-pass of a w x h frame alone; host_out receives (w / 64) * (h / 64) PkBlockEntries records (rtk_trace_shared.h). Synchronous.
-int rtk_debug_packet_entries(const rtk_dev_scene *ds, const rtk_ray *d_rays, uint32_t image_w, uint32_t image_h, uint32_t target, uint32_t max_levels, void *host_out);
+// -- the look for an image nobody announced (rtk_detect.hip) --
 int rtk_detect_image(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, hipStream_t stream, uint32_t *w_out, uint32_t *h_out);
-int rtk_trace_status(const rtk_dev_scene *ds, hipStream_t stream);
-void rtk_scratch_free(LaunchScratch *s);
-void rtk_scene_drop_stream(rtk_dev_scene *ds, hipStream_t stream);   // the stream is about to be destroyed (and has been synchronised)
+// -- hit records to full hits, and rtk_trace_ray's one-ray launch (rtk_expand.hip) --
 // h_status (host-visible): also receives the stream's launch-error word (see rtk_trace_status), or is left alone if the stream has none.
 // ticket != 0 and n <= 256: the word becomes (ticket << 32 | error) once every result of the launch is visible to the host.
 int rtk_launch_trace_one(const rtk_dev_scene *ds, const rtk_ray *d_ray, rtk_hit *d_hit, uint8_t *d_mask, hipStream_t stream,

@@ -282,7 +282,9 @@ static int trace_shard(DeviceSlot &s, const rtk_ray *d_rays, size_t count, rtk_h
 		if (image) band.image_height = (uint32_t)(m / opts->image_width);
 		else { band.image_width = 0; band.image_height = 0; }
 		const rtk_trace_opts *o = opts ? &band : nullptr;
-		const int rc = rtk_launch_trace(s.scene, d_rays + at, m, d_rec + at, nullptr, o, s.trace_stream, false, nullptr);
+		TraceCall call;
+		call.rays = d_rays + at; call.n = m; call.hits = d_rec + at; call.opts = o; call.stream = s.trace_stream;
+		const int rc = rtk_launch_trace(s.scene, call);
 		if (rc != RTK_AMD_OK) return rc;
 		RTK_HIP_CHECK(hipEventRecord(s.events[k], s.trace_stream), RTK_AMD_ERR_HIP);
 		RTK_HIP_CHECK(hipStreamWaitEvent(s.copy_stream, s.events[k], 0), RTK_AMD_ERR_HIP);

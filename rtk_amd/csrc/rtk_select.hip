@@ -174,11 +174,7 @@ int rtk_launch_select(rtk_dev_scene *ds, const void *d_src, uint32_t kind, size_
 		return RTK_AMD_ERR_BAD_ARG;
 	}
 	if (num_rays >= ((size_t)1 << 32)) { rtk_set_error("rtk_dev_select_rays: %zu rays: a list holds fewer than 2^32", num_rays); return RTK_AMD_ERR_BAD_ARG; }
-	int cur = -1;
-	if (hipGetDevice(&cur) != hipSuccess || cur != ds->device) {
-		rtk_set_error("rtk_dev_select_rays: the scene lives on device %d, the calling thread's current device is %d", ds->device, cur);
-		return RTK_AMD_ERR_BAD_ARG;
-	}
+	if (!rtk_on_scene_device(ds, "rtk_dev_select_rays")) return RTK_AMD_ERR_BAD_ARG;
 	if (num_rays == 0) {
 		RTK_HIP_CHECK(hipMemsetAsync(d_out_count, 0, sizeof(uint64_t), stream), RTK_AMD_ERR_HIP);
 		return RTK_AMD_OK;
@@ -198,12 +194,12 @@ int rtk_launch_select(rtk_dev_scene *ds, const void *d_src, uint32_t kind, size_
 
 	// the scratch set of (scene, stream), held until everything is enqueued (rtk_launch_trace does the same)
 	std::lock_guard<std::mutex> lock(ds->scratch_mutex);
-	LaunchScratch *sc = rtk_scratch_for(ds, stream);
+	LaunchScratch *sc = ds->scratch.get(stream);
 	if (!sc) return RTK_AMD_ERR_OOM;
-	const int rc = rtk_scratch_grow(&sc->d_select, &sc->select_capacity, bytes, bytes, stream);
+	const int rc = sc->grow(sc->select, bytes, bytes);
 	if (rc != RTK_AMD_OK) return rc;
-	p.masks = reinterpret_cast<unsigned long long *>(sc->d_select);
-	p.counts = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(sc->d_select) + mask_bytes);
+	p.masks = sc->select.as<unsigned long long>();
+	p.counts = reinterpret_cast<uint32_t *>(sc->select.as<char>() + mask_bytes);
 	p.groups = p.counts + p.blocks;
 	hipLaunchKernelGGL(k_select_count, dim3(p.blocks), dim3(SELECT_THREADS), 0, stream, p);
 	hipLaunchKernelGGL(k_select_scan, dim3(p.num_groups), dim3(SELECT_THREADS), 0, stream, p);

@@ -1,6 +1,6 @@
 // rtk_trace_plan.h -- which kernels a trace launch runs, decided by a pure function of the batch, the options, the scene, the
 // kernels this device has loaded and the environment defaults. Plain C++17, no HIP: the host compiler builds it alone
-// (tests/test_trace_plan_cpu.py does). rtk_launch_trace (rtk_trace.hip) gathers the inputs and carries the plan out.
+// (tests/test_trace_plan_cpu.py does). rtk_launch_trace (rtk_launch.hip) gathers the inputs and carries the plan out.
 #pragma once
 
 #include "rtk_amd.h"
@@ -29,7 +29,7 @@ enum { VARIANT_COLLECT = 16, VARIANT_PACKET = 18, VARIANT_PACKET_COUNTED = 19, N
 enum class PacketKernel { Cpp = -1, Hot, Beam, Beam2, Count2, Any2 };
 enum { NUM_PACKET_KERNELS = 5 };
 
-// Environment defaults of the launch path, RTK_AMD_<NAME> each; read once per process by rtk_trace_knobs (rtk_trace.hip).
+// Environment defaults of the launch path, RTK_AMD_<NAME> each; read once per process by rtk_trace_knobs (rtk_launch.hip).
 struct TraceKnobs {
 	int detect_image = 1;          // DETECT_IMAGE=0: batches without an image hint are not looked at
 	int tile_blocks = 1;           // TILE_BLOCKS=0: image batches number their 8x8 tiles row by row, not by 64x64-pixel blocks

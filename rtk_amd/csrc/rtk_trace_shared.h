@@ -1,5 +1,5 @@
 // rtk_trace_shared.h -- pieces shared by the two traversal kernels (rtk_trace.hip: one ray
-// per lane; rtk_trace_packet.hip: one 8x8 tile per wave).
+// per lane; rtk_trace_packet.hip: one 8x8 tile per wave) and the launch code that feeds them (rtk_launch.hip).
 #pragma once
 
 #include "rtk_dev.h"
@@ -149,6 +149,19 @@ __device__ __forceinline__ unsigned long long map_index(unsigned long long i, ui
 }
 
 
+// the kernels address nodes and triangles as SGPR base + 32-bit byte offset
+inline bool rtk_within_4gib(const DevSceneView &v)
+{
+	return (uint64_t)v.num_nodes * 128u <= 0xffffff00ull && (uint64_t)v.num_tris * RTK_TRI_STRIDE <= 0xffffff00ull;
+}
+
+// The doors of the kernel files: each holds one kernel family, and these launch it.
+// rtk_trace.hip: rtk_trace_kernel's variant (rtk_trace_plan.h). The occupancy query also answers for the C++ packet kernel's variants; cached per device
+int rtk_trace_occupancy(int device, int variant);
+void rtk_trace_kernel_launch(int variant, const TraceParams &p, unsigned blocks, hipStream_t stream);
+// rtk_ray_sort.hip: the ray-reordering pre-pass; sc->sort holds rtk_ray_sort_bytes(n) for a capacity of n rays
+size_t rtk_ray_sort_bytes(size_t n);
+int rtk_ray_sort_launch(const rtk_dev_scene *ds, LaunchScratch *sc, const rtk_ray *d_rays, size_t n, const TraceKnobs &knobs, hipStream_t stream, const unsigned long long **perm);
 // rtk_trace_packet.hip
 int rtk_packet_occupancy(bool counted);
 void rtk_packet_launch(const TraceParams &p, unsigned blocks, hipStream_t stream, bool counted);
@@ -176,5 +189,5 @@ struct AsmModule {
 	const Loaded *on(int device);
 	int launch(int device, int kernel, void *params, size_t size, unsigned blocks, hipStream_t stream);
 };
-AsmModule &rtk_lane_module();      // rtk_lane_hot.S: 0 rtk_lane_hot_closest, 1 rtk_lane_hot_any, 2 and 3 their listed forms (rtk_trace.hip)
+AsmModule &rtk_lane_module();      // rtk_lane_hot.S: 0 rtk_lane_hot_closest, 1 rtk_lane_hot_any, 2 and 3 their listed forms (rtk_launch.hip)
 AsmModule &rtk_packet_module();    // rtk_packet_hot.S, rtk_packet_beam2.S: kernels numbered by PacketKernel (rtk_trace_packet.hip)

@@ -361,3 +361,40 @@ def test_the_references_leaf_sizes_stay_on_the_hand_written_kernels(api, oracle,
     assert ((r2["prim"] != 0xFFFFFFFF) == om).all()
     assert (r2["t"][om] == oh["t"][om]).all() and (r2["u"][om] == oh["u"][om]).all() and (r2["v"][om] == oh["v"][om]).all()
     assert r2.tobytes() == ds.trace(inc, opts=api.make_opts(no_asm=True), full=False).tobytes()
+
+
+def test_scratch_regrown_between_launches_on_a_live_stream(api):
+    """A scratch buffer that has to grow while earlier launches on its stream may still be using it (rtk_launch_scratch.h: wait for
+    the stream, free, allocate): 4096, then 65536, then 4096 incoherent rays with RTK_TRACE_SORT_RAYS on one non-default stream with
+    nothing waited for in between, closest hit and then any hit. Every result is, byte for byte, that batch traced alone on a
+    freshly built scene."""
+    import torch
+    g = np.linspace(0.0, 1.0, 33, dtype=np.float32)
+    x, y = np.meshgrid(g, g, indexing="ij")
+    p = np.stack([x, y, (0.5 + 0.2 * np.sin(4.0 * x) * np.cos(4.0 * y)).astype(np.float32)], axis=-1)
+    a, b, c, d = p[:-1, :-1], p[1:, :-1], p[:-1, 1:], p[1:, 1:]
+    tris = np.ascontiguousarray(np.stack([a, b, c, b, d, c], axis=2).reshape(-1, 3))      # a 32 x 32 grid of quads: 2048 triangles
+    assert tris.shape == (3 * 2048, 3)
+    batches = [synth.rays_incoherent(n, first=first) for n, first in ((4096, 0), (65536, 4096), (4096, 69632))]
+    opts = api.make_opts(sort_rays=True)
+
+    def alone(rays, any_hit):
+        fresh = api.DeviceScene.build([dict(positions=tris)])
+        if any_hit:
+            return np.asarray(fresh.trace_any(rays, opts=opts)).astype(np.uint8).tobytes()
+        return fresh.trace(rays, opts=opts, full=False).tobytes()
+
+    ds = api.DeviceScene.build([dict(positions=tris)])
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        d_rays = [api.to_device(r) for r in batches]
+        recs = [ds.trace_device(dr, len(r), opts=opts) for dr, r in zip(d_rays, batches)]
+        occs = [ds.trace_any_device(dr, len(r), opts=opts) for dr, r in zip(d_rays, batches)]
+        assert api.lib().rtk_dev_trace_status(ds.handle, api._stream_ptr()) == 0
+    side.synchronize()
+    for r, rec, occ in zip(batches, recs, occs):
+        want = alone(r, False)
+        assert 0 < (np.frombuffer(want, np.uint32)[3::4] != 0xFFFFFFFF).sum() < len(r)      # (hits and misses both)
+        assert rec.cpu().numpy().tobytes() == want
+        assert occ.cpu().numpy().tobytes() == alone(r, True)
