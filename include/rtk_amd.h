@@ -472,6 +472,44 @@ int rtk_dev_select_rays(const rtk_dev_scene *ds, const void *d_src, uint32_t kin
 uint32_t rtk_amd_select_block_items(void);
 uint32_t rtk_amd_select_scan_items(void);
 
+/* ---- Closest points: which triangle of the scene is nearest to a point, how far, and where on it ----
+ * The second question the tree answers (signed-distance baking, proximity and collision checks, projection, snapping, ICP). It
+ * reads the scene as it stands -- a device build, an uploaded blob, after any refit, split or rebuild -- and changes no bit of it.
+ *
+ * THE RESULT DOES NOT DEPEND ON THE TREE. It is a function of the scene's triangle records and the query alone, stated in float
+ * arithmetic (rtk_amd/csrc/rtk_closest_rule.h; INTEGRATION.md "Closest points"): every triangle has a squared distance dist2,
+ * barycentrics and a closest point q by Ericson's region walk, every operation rounded on its own, q clamped to the triangle's
+ * own box; the answer to (p, max_dist2) is the triangle with the smallest dist2 < max_dist2, THE LOWEST PRIMITIVE ID AMONG EQUAL
+ * dist2, or a miss. Leaf sizes, loose boxes and the node format only decide how many triangles are never looked at.
+ *   hit    dist2, u (weight of vertex 0), v (weight of vertex 1) and the global primitive id; d_points[3 i ..] = q
+ *   miss   dist2 = max_dist2 as given, u = v = 0, prim = RTK_PRIM_NONE; d_points[3 i ..] = the query point as given
+ * The record has the shape of rtk_hit_record with dist2 in the place of t, and its miss is that record's miss: rtk_dev_select_rays
+ * (RTK_SELECT_RECORD_HIT / _MISS) and rtk_dev_expand_hits take these records as they are. A max_dist2 that is NaN, zero or
+ * negative is a miss, and so is a query with a non-finite coordinate; RTK_INF means no limit. A scene without triangles
+ * answers every query with a miss.
+ * `list` may be NULL: all num_queries queries are answered. Otherwise the words of the listed traces hold: m = min(*d_count,
+ * num_queries) entries are answered, the result of query r goes to slot r of d_records (and d_points), A SLOT THAT IS NOT LISTED
+ * IS NOT WRITTEN, an id may repeat, and the count is read when the work reaches it on `stream`. d_points may be NULL.
+ * Asynchronous on `stream`: no host wait, nothing read back. The scene is only read, so the thread-safety rules of the batches
+ * hold; the part of the walk's stack that does not fit on chip lives in the per-(scene, stream) scratch set, and a dropped push
+ * (impossible for a tree) is reported by rtk_dev_trace_status like a trace's. Nothing it allocates counts toward the scene.
+ * Refused before anything is launched, RTK_AMD_ERR_BAD_ARG: a NULL scene; NULL d_queries or d_records with num_queries != 0; a
+ * bad list (as for the listed traces); num_queries >= 2^32; a calling thread whose current device is not the scene's.
+ * num_queries == 0 is RTK_AMD_OK with nothing launched. Works as it is on rtk_mgpu_scene(m, i).
+ * A scene with non-finite vertex coordinates: the call terminates and writes only inside its outputs; NOTHING ELSE IS PROMISED
+ * about its results. */
+typedef struct rtk_point_query { float x, y, z, max_dist2; } rtk_point_query;
+typedef struct rtk_closest_record { float dist2, u, v; uint32_t prim; } rtk_closest_record;
+int rtk_dev_closest_points(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries,
+	const rtk_ray_list *list, rtk_closest_record *d_records, float *d_points, void *stream);
+/* Same result as rtk_dev_closest_points without a list, plus visit counts: rays = queries answered, nodes = 128 B node records
+ * fetched, leaves, triangles = 48 B triangle records fetched, hits = queries that found a triangle, stack_spills = pushes that
+ * went past the on-chip part of the stack (the wave_ fields stay 0). Null stream, synchronous; not for timing. */
+int rtk_dev_closest_points_counted(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries,
+	rtk_closest_record *d_records, float *d_points, rtk_trace_counters *out);
+/* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
+uint32_t rtk_amd_closest_stack_entries(void);
+
 /* Waits for `stream` and reports whether a launch of this scene on it overflowed a traversal stack
  * (RTK_AMD_ERR_BAD_SCENE; impossible for a validated tree -- the push is dropped, never written out of bounds). */
 int rtk_dev_trace_status(const rtk_dev_scene *ds, void *stream);

@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from .types import (HIT_DTYPE, HIT_RECORD_DTYPE, RAY_DTYPE, MeshSet, Placement, SceneDesc, SceneHeader, placement_array)
+from .types import (CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, MeshSet, Placement, SceneDesc, SceneHeader, placement_array)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RTK_AMD_LIB") or os.path.join(HERE, "librtk_amd.so")   # RTK_AMD_LIB: kernel A/B builds only
@@ -155,7 +155,8 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_dev_scene_build_placed", "rtk_dev_scene_refit_placed", "rtk_dev_scene_refit_meshes_placed",
                      "rtk_mgpu_build_placed", "rtk_mgpu_refit_placed", "rtk_mgpu_refit_meshes_placed",
                      "rtk_dev_trace_rays_listed", "rtk_dev_trace_rays_any_listed", "rtk_dev_select_rays",
-                     "rtk_amd_select_block_items", "rtk_amd_select_scan_items"]
+                     "rtk_amd_select_block_items", "rtk_amd_select_scan_items",
+                     "rtk_dev_closest_points", "rtk_dev_closest_points_counted", "rtk_amd_closest_stack_entries"]
 
 _lib = None
 
@@ -218,6 +219,12 @@ def lib():
     L.rtk_amd_select_block_items.restype = C.c_uint32
     L.rtk_amd_select_scan_items.argtypes = []
     L.rtk_amd_select_scan_items.restype = C.c_uint32
+    L.rtk_dev_closest_points.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtk_dev_closest_points.restype = C.c_int
+    L.rtk_dev_closest_points_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
+    L.rtk_dev_closest_points_counted.restype = C.c_int
+    L.rtk_amd_closest_stack_entries.argtypes = []
+    L.rtk_amd_closest_stack_entries.restype = C.c_uint32
     L.rtk_trace_rays_filter.restype = C.c_size_t
     L.rtk_trace_rays_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rtk_amd_shard_range.restype = None
@@ -570,6 +577,60 @@ class DeviceScene:
         _check(lib().rtk_dev_select_rays(self.handle, C.c_void_p(src.data_ptr()), kind, num_rays, C.byref(l) if l is not None else None,
                                          C.c_void_p(ids.data_ptr()), C.c_void_p(count.data_ptr()), _stream_ptr()), "rtk_dev_select_rays")
         return ids, count
+
+    # -- closest points (rtk_dev_closest_points): asynchronous on the current stream, nothing here waits for it --
+
+    def closest_points_device(self, d_queries, n, d_records=None, d_points=None, count=None, ids=None, want_points=True):
+        """The nearest triangle to each of n queries (POINT_QUERY_DTYPE bytes on the device): returns (d_records, d_points), uint8
+        cuda tensors of CLOSEST_RECORD_DTYPE records and of 3 floats per query. want_points=False: no points are written (the
+        call gets NULL for them and None is returned). count / ids: cuda int64 tensors naming the queries to answer, as for trace_listed_device;
+        slots that are not listed are not written."""
+        torch = _torch()
+        if d_records is None:
+            d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        if not want_points:
+            d_points = None
+        elif d_points is None:
+            d_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        if ids is not None and count is None:
+            raise RtkError("closest_points_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        _check(lib().rtk_dev_closest_points(self.handle, C.c_void_p(d_queries.data_ptr()), n, C.byref(l) if l is not None else None,
+                                            C.c_void_p(d_records.data_ptr()), C.c_void_p(d_points.data_ptr()) if d_points is not None else None,
+                                            _stream_ptr()), "rtk_dev_closest_points")
+        return d_records, d_points
+
+    def closest_points_counted(self, d_queries, n):
+        """closest_points_device of all n queries on the null stream, synchronous, with the visit counts of
+        rtk_dev_closest_points_counted: returns (d_records, d_points, counts dict)."""
+        torch = _torch()
+        d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        d_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        ctr = TraceCounters()
+        torch.cuda.synchronize()
+        _check(lib().rtk_dev_closest_points_counted(self.handle, C.c_void_p(d_queries.data_ptr()), n, C.c_void_p(d_records.data_ptr()),
+                                                    C.c_void_p(d_points.data_ptr()), C.byref(ctr)), "rtk_dev_closest_points_counted")
+        return d_records, d_points, ctr.as_dict()
+
+    def closest_points(self, points, max_dist=None):
+        """points: array-like (n, 3) float32. max_dist: a distance (scalar or one per point) beyond which a triangle does not
+        count, squared in float32; None = no limit (RTK_INF). Returns (records CLOSEST_RECORD_DTYPE, points (n, 3) float32):
+        prim == 0xFFFFFFFF is a miss, whose point is the query itself."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        q = np.zeros(n, POINT_QUERY_DTYPE)
+        q["point"] = pts
+        if max_dist is None:
+            q["max_dist2"] = RTK_INF
+        else:
+            d = np.broadcast_to(np.asarray(max_dist, np.float32), (n,))
+            with np.errstate(over="ignore", invalid="ignore"):
+                q["max_dist2"] = d * d
+        if n == 0:
+            return np.zeros(0, CLOSEST_RECORD_DTYPE), np.zeros((0, 3), np.float32)
+        d_rec, d_pts = self.closest_points_device(to_device(q), n)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return d_rec.cpu().numpy().view(CLOSEST_RECORD_DTYPE), d_pts.cpu().numpy().view(np.float32).reshape(n, 3)
 
     def expand_device(self, d_records, n):
         torch = _torch()

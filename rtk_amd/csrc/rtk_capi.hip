@@ -202,6 +202,19 @@ extern "C" int rtk_dev_select_rays(const rtk_dev_scene *ds, const void *d_src, u
 	return rtk_launch_select(const_cast<rtk_dev_scene *>(ds), d_src, kind, num_rays, in, d_out_ids, d_out_count, (hipStream_t)stream);
 }
 
+extern "C" int rtk_dev_closest_points(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries,
+	const rtk_ray_list *list, rtk_closest_record *d_records, float *d_points, void *stream)
+{
+	return rtk_launch_closest(ds, d_queries, num_queries, list, d_records, d_points, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_closest_points_counted(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries,
+	rtk_closest_record *d_records, float *d_points, rtk_trace_counters *out)
+{
+	if (!out) { rtk_set_error("rtk_dev_closest_points_counted: NULL counters"); return RTK_AMD_ERR_BAD_ARG; }
+	return rtk_launch_closest(ds, d_queries, num_queries, nullptr, d_records, d_points, nullptr, out);
+}
+
 extern "C" int rtk_dev_trace_rays_counted(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
 	rtk_hit_record *d_hits, const rtk_trace_opts *opts, rtk_trace_counters *out)
 {

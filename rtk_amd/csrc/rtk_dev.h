@@ -313,6 +313,9 @@ void rtk_scene_drop_stream(rtk_dev_scene *ds, hipStream_t stream);   // the stre
 // -- rtk_dev_select_rays (rtk_select.hip) --
 int rtk_launch_select(rtk_dev_scene *ds, const void *d_src, uint32_t kind, size_t num_rays, const rtk_ray_list *in, uint64_t *d_out_ids,
 	uint64_t *d_out_count, hipStream_t stream);
+// -- rtk_dev_closest_points (rtk_closest.hip) --
+int rtk_launch_closest(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries, const rtk_ray_list *list,
+	rtk_closest_record *d_records, float *d_points, hipStream_t stream, rtk_trace_counters *counted = nullptr);   // counted: synchronises the stream
 // -- the look for an image nobody announced (rtk_detect.hip) --
 int rtk_detect_image(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, hipStream_t stream, uint32_t *w_out, uint32_t *h_out);
 // -- hit records to full hits, and rtk_trace_ray's one-ray launch (rtk_expand.hip) --

@@ -23,5 +23,7 @@ static_assert(sizeof(rtk_dev_scene_quality_info) == 96 && offsetof(rtk_dev_scene
 static_assert(sizeof(rtk_dev_split_info) == 48 && offsetof(rtk_dev_split_info, leaves_split) == 8 && offsetof(rtk_dev_split_info, largest_leaf_before) == 24 &&
 	offsetof(rtk_dev_split_info, max_depth_after) == 36 && offsetof(rtk_dev_split_info, split_ms) == 40, "rtk_dev_split_info");
 static_assert(sizeof(rtk_placement) == 48 && offsetof(rtk_placement, m) == 0, "rtk_placement");
+static_assert(sizeof(rtk_point_query) == 16 && offsetof(rtk_point_query, max_dist2) == 12, "rtk_point_query");
+static_assert(sizeof(rtk_closest_record) == 16 && offsetof(rtk_closest_record, prim) == 12, "rtk_closest_record");
 static_assert(sizeof(rtk_dev_rebuild_info) == 40 && offsetof(rtk_dev_rebuild_info, nodes_before) == 8 && offsetof(rtk_dev_rebuild_info, max_depth_before) == 24 &&
 	offsetof(rtk_dev_rebuild_info, rebuild_ms) == 32, "rtk_dev_rebuild_info");
