@@ -1,4 +1,5 @@
-// rtk_build_layout.h -- where every temporary of a device build lies in the build workspace (rtk_build.hip).
+// rtk_build_layout.h -- where every temporary of a device build lies in the build workspace (rtk_build.hip owns it, the stage files
+// rtk_build_*.hip take their buffers from it).
 //
 // Host only, no HIP: one carve both sizes the workspace (BuildLayout::bytes) and places every buffer in it (byte offsets from
 // the workspace's base), so a buffer cannot be placed without being counted. tests/test_build_layout_cpu.py checks the carve
@@ -10,11 +11,12 @@
 
 #include <vector>
 
-#define RTK_BUILD_REFIT_TILE 1024u       // sorted triangles per refit tile (REFIT_TILE of rtk_build.hip)
+#define RTK_BUILD_REFIT_TILE 1024u       // sorted triangles per refit tile (REFIT_TILE of rtk_build_internal.h)
 #define RTK_BUILD_COLLAPSE_BLOCK 256u    // jobs per workgroup of the level-by-level collapse (COLLAPSE_BLOCK)
 #define RTK_BUILD_COLLAPSE_RING 64u      // level states in flight (COLLAPSE_RING)
+#define RTK_BUILD_COLLAPSE_SMALL_JOBS 64u   // largest level the one-workgroup collapse kernel takes (COLLAPSE_SMALL_JOBS)
 
-// sizes of the records the build kernels define (rtk_build.hip asserts its structs against these)
+// sizes of the records the build kernels define (rtk_build_internal.h asserts its structs against these)
 #define RTK_BUILD_SIZEOF_INTRI 48u
 #define RTK_BUILD_SIZEOF_BINNODE 32u
 #define RTK_BUILD_SIZEOF_CLIMB 12u

@@ -21,6 +21,7 @@
 // (rtk_trace_ray[s] upload it), and nothing falls back to it on its own.
 #include "rtk.h"
 #include "rtk_amd.h"
+#include "rtk_cpu_build.h"
 
 #include <math.h>
 #include <stdint.h>
@@ -502,7 +503,7 @@ void plan(rtk_cpu_build *b)
 
 } // namespace
 
-// ---------------------------------------------------------------------------- entry points (called from rtk_build.hip)
+// ---------------------------------------------------------------------------- entry points (rtk_cpu_build.h; called from rtk_build_api.hip)
 
 // The first task of a build (rtk.c:1679-1681): it does nothing itself, running it opens phase A.
 void rtk_cpu_task_start(const rtk_task *, rtk_task_ctx *) {}

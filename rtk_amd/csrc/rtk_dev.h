@@ -155,7 +155,7 @@ struct rtk_dev_scene {
 	int num_cus = 0;
 	// Device-built scenes make the four side arrays of the view (vertex_index, prim_slot, slot_mesh, slot_tri: what the expansion of
 	// hit records, the validator and the exporter read -- never a traversal) on first use, not in every build: 52 of the 100
-	// bytes per triangle the build's emit kernel wrote, one of them scattered (rtk_scene_side_arrays, rtk_build.hip).
+	// bytes per triangle the build's emit kernel wrote, one of them scattered (rtk_scene_side_arrays, rtk_build_refit.hip).
 	// RTK_FORGET_TREE keeps them: they go by slot and primitive, not by node, and the split kernel moves their entries with the
 	// triangle records it reorders (k_split_leaves<true>, under side_mutex). RTK_FORGET_SLOTS drops them (a rebuild: every slot changes).
 	std::mutex side_mutex;
@@ -255,7 +255,7 @@ int rtk_scene_consts(rtk_dev_scene *ds, hipStream_t stream);
 int rtk_quantize_node_list(rtk_dev_scene *ds, hipStream_t stream, const uint32_t *list, const uint32_t *d_count);
 void rtk_quantize_finish(rtk_dev_scene *ds);   // after that stream has been synchronised
 
-// -- the build workspace lent to another pass, helpers shared with the build (rtk_build.hip) --
+// -- the build workspace lent to another pass, helpers shared with the build (rtk_build.hip; its stages: rtk_build_internal.h) --
 // The workspace of a device, at least `bytes` large, lent to a pass that is not a build (rtk_refit.hip: the temporaries of the
 // schedule, host-resident positions staged as a build stages them). Builds on the device wait while it is out; whatever the
 // borrower enqueued on the memory must have completed before release() (the destructor).
@@ -272,8 +272,13 @@ struct WorkspaceLoan {
 bool rtk_is_device_ptr(const void *p);         // hipMalloc'ed memory?
 void rtk_export_forget(const rtk_dev_scene *ds);   // the scene's cached export plan, if any (rtk_export.hip)
 // the two constants of the surface area heuristic, for the builder that splits by them and for rtk_dev_scene_quality that
-// measures by them: 0.5 per node visited, 1.0 per triangle tested, RTK_AMD_SAH_CN / RTK_AMD_SAH_CT override (rtk_build.hip)
+// measures by them: 0.5 per node visited, 1.0 per triangle tested, RTK_AMD_SAH_CN / RTK_AMD_SAH_CT override (rtk_build.hip; the
+// defaults and the environment: rtk_build_plan.h)
 void rtk_sah_costs(float *cost_node, float *cost_tri);
+// RTK_AMD_MAX_LEAF, 1 .. 63, default 3: the device builder's leaf limit, and what rtk_dev_scene_split_leaves takes for max_leaf 0
+uint32_t rtk_build_max_leaf();
+// a blob that rtk_finish_build_to exported from `ds` takes the scene over as its resident device copy (rtk_capi.hip)
+void rtk_cache_adopt(const rtk_scene *scene, rtk_dev_scene *ds);
 
 // -- radix sort shared with the builder (rtk_sort.hip) --
 size_t rtk_sort_scratch_words(uint32_t n);

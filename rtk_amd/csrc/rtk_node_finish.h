@@ -1,6 +1,6 @@
 // rtk_node_finish.h -- what turns the boxes and child words of a 4-wide node into its final form: the front-to-back child
 // order words (DevNode::order) and the 64-byte compressed copy (DevNodeQ). Shared by k_quantize (rtk_quant.hip: uploads, and
-// the top of a device-built tree) and by the tile-local collapse of the device build (rtk_build.hip), which finishes its
+// the top of a device-built tree) and by the tile-local collapse of the device build (rtk_build_collapse.hip), which finishes its
 // nodes in the pass that makes them instead of re-reading them.
 #pragma once
 

@@ -1,5 +1,5 @@
 // rtk_place_rule.h -- the one rule by which a placement moves a vertex (rtk_placement, rtk_amd.h), for the host and the device:
-// the ingest of a build (k_ingest, and the host's decode of callback and tiny scenes: rtk_build.hip), the gather of a refit
+// the ingest of a build (k_ingest, and the host's decode of callback and tiny scenes: rtk_build_ingest.hip), the gather of a refit
 // (refit_tri, rtk_refit.hip) and tests/place_rule_driver.cpp all include this file and nothing else decides a placed bit.
 //
 // A placement is 12 floats m[0..11], a 3 x 4 matrix row by row. The vertex is made float first, exactly as an unplaced

@@ -8,9 +8,9 @@
 //   upload_vec (rtk_upload.hip), six arrays     max(elements, 1) * sizeof(T)          the same
 //   rtk_scene_consts (rtk_quant.hip)            sizeof(DevSceneConsts)                0
 //   rtk_quantize_nodes, an upload's qnodes      max(num_nodes, 1) * 64                num_nodes * 64
-//   Build::dev_alloc (rtk_build.hip)            bytes, 16 if that is 0                bytes
+//   Build::dev_alloc (rtk_build_internal.h)     bytes, 16 if that is 0                bytes
 //   the build's node block                      node_cap * (128 + 64)                 the same (the capacity, not num_nodes)
-//   rtk_scene_side_arrays (rtk_build.hip)       four arrays, one Carve                the same (Carve::bytes: padded)
+//   rtk_scene_side_arrays (rtk_build_refit.hip) four arrays, one Carve                the same (Carve::bytes: padded)
 //   make_schedule (rtk_refit.hip), d_order      num_nodes * 4                         the same
 //   make_schedule, level starts + mesh table    padded starts + max(meshes, 1) * 24   starts * 4 + meshes * 24 (unpadded)
 //   make_partial_tables (rtk_refit.hip)         eight tables, one Carve               Carve::counted: the tables' unpadded sum

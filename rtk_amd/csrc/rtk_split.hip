@@ -30,8 +30,6 @@
 
 #include <algorithm>
 
-uint32_t rtk_build_max_leaf();                 // RTK_AMD_MAX_LEAF as the device builder reads it (rtk_build.hip)
-
 namespace {
 
 #define SPLIT_WAVES 4                          // big leaves per workgroup of k_split_leaves

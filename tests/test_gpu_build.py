@@ -209,7 +209,7 @@ def test_device_resident_mesh_is_read_in_place(api, oracle):
 
 
 def _morton_keys(tris):
-    """Morton keys exactly as rtk_build.hip's k_bounds/k_morton compute them (float32 ops): 63 bits, of which
+    """Morton keys exactly as rtk_build_ingest.hip's k_bounds/k_morton compute them (float32 ops): 63 bits, of which
     the builder keeps the top 48 for scenes below 2^24 triangles."""
     t = tris.reshape(-1, 3, 3)
     c2 = (t.min(axis=1) + t.max(axis=1)).astype(np.float32)
@@ -231,7 +231,7 @@ def _morton_keys(tris):
     if len(t) >= (1 << 24):
         return k
     # the packed sort word keeps ceil(log2 n) + 8 bits of the 63-bit code, in whole 8-bit radix passes, 24 ... 40 of them
-    # (rtk_build.hip: key width from n)
+    # (rtk_build_plan.h: key width from n)
     lg = int(np.ceil(np.log2(max(2, len(t)))))
     bits = min(40, max(24, ((lg + 8 + 7) // 8) * 8))
     return k >> np.uint64(63 - bits)
