@@ -1,5 +1,5 @@
 // rtk_detect.hip -- rtk_detect_image: is a batch of device rays a row-major image nobody told us about? The rule is
-// rtk_detect_rule.h's (the host applies the same one to host rays, rtk_capi.hip); here are its two kernels and their launch.
+// rtk_detect_rule.h's (the host applies the same one to host rays, rtk_host_calls.hip); here are its two kernels and their launch.
 #include "rtk_dev.h"
 #include "rtk_detect_rule.h"
 

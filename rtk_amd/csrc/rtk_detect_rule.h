@@ -1,5 +1,5 @@
 // rtk_detect_rule.h -- is a batch a row-major image nobody told us about? The rule, once, for the device (rtk_detect.hip:
-// k_detect_row, k_detect_check) and for the host (rtk_detect_host below, for rtk_trace_rays in rtk_capi.hip; tests/detect_rule_driver.cpp).
+// k_detect_row, k_detect_check) and for the host (rtk_detect_host below, for rtk_trace_rays in rtk_host_calls.hip; tests/detect_rule_driver.cpp).
 //
 // The reference's interface has no notion of an image (rtk.h:129); a host that only hands over rays should still get the packet
 // kernels. Along a row of an image the step from one ray to the next (origin and direction, six

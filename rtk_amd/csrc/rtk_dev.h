@@ -277,7 +277,7 @@ void rtk_export_forget(const rtk_dev_scene *ds);   // the scene's cached export 
 void rtk_sah_costs(float *cost_node, float *cost_tri);
 // RTK_AMD_MAX_LEAF, 1 .. 63, default 3: the device builder's leaf limit, and what rtk_dev_scene_split_leaves takes for max_leaf 0
 uint32_t rtk_build_max_leaf();
-// a blob that rtk_finish_build_to exported from `ds` takes the scene over as its resident device copy (rtk_capi.hip)
+// a blob that rtk_finish_build_to exported from `ds` takes the scene over as its resident device copy (rtk_host_calls.hip)
 void rtk_cache_adopt(const rtk_scene *scene, rtk_dev_scene *ds);
 
 // -- radix sort shared with the builder (rtk_sort.hip) --
@@ -305,6 +305,13 @@ struct TraceCall {
 	rtk_packet_counters *pk_counted = nullptr; // rtk_dev_trace_rays_packet_counted (synchronises the stream)
 	const rtk_ray_list *list = nullptr;        // rtk_dev_trace_rays*_listed have checked it; n is the size of the arrays, below 2^32
 };
+// what every batch call says; the rest of a TraceCall stays "not given" unless the entry point means it
+inline TraceCall batch_call(const rtk_ray *d_rays, size_t n, const rtk_trace_opts *opts, void *stream)
+{
+	TraceCall c;
+	c.rays = d_rays; c.n = n; c.opts = opts; c.stream = (hipStream_t)stream;
+	return c;
+}
 int rtk_launch_trace(const rtk_dev_scene *ds, const TraceCall &call);
 // the scene's memory, its scratch and the stream must all belong to the device this thread has current: a launch from a
 // thread on another GPU would read the scene across devices (a fault without peer access). false: rtk_set_error has said so

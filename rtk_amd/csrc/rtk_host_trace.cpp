@@ -6,7 +6,7 @@
 // per-ray symbols of rtk.h walk the caller's blob where it lies, on the calling thread: no residency, no stream, no staging.
 // This is the per-ray symbols' implementation, not a fallback: nothing else ever routes here -- every batch entry point
 // (rtk_trace_rays*, rtk_dev_*, rtk_mgpu_*) runs the HIP kernels or fails -- and RTK_AMD_PER_RAY=gpu sends the per-ray
-// symbols through the one-ray kernel again (rtk_capi.hip).
+// symbols through the one-ray kernel again (rtk_host_calls.hip).
 //
 // What it computes is what the GPU's exact path computes on the same blob, bit for bit (tests/test_host_per_ray.py):
 //   * node test: (plane - origin) * (1/d) per plane, near / far row picked by the direction's sign BIT, entry = max of the

@@ -1,5 +1,7 @@
 """Device build at sizes around every internal boundary (sort tile 4096, refit tile 1024, collapse levels of 1024 jobs,
 256-job blocks): structure validates, two builds agree, and the traversal matches the oracle on the exported blob."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -161,3 +163,27 @@ def test_ray_batch_sizes_through_every_entry_point(api, oracle, n):
         _, ctr = ds.trace_counted(rays)
         assert ctr["rays"] == n
     assert api.lib().rtk_dev_trace_status(ds.handle, None) == 0
+
+
+@pytest.fixture(scope="module")
+def blob_and_device_answers(api):
+    """A blob of 5 000 triangles in host memory, 98 305 incoherent rays, and what rtk_dev_trace_rays + rtk_dev_expand_hits answer
+    on a device copy uploaded from those bytes (computed once)."""
+    blob = np.ascontiguousarray(api.DeviceScene.build([dict(positions=synth.triangle_soup(5000, 0.05, seed=11))]).export_blob())
+    rays = synth.rays_incoherent(98305)
+    hits, mask, _ = api.DeviceScene.upload(blob).trace(rays)
+    assert mask.any() and not mask.all()
+    yield blob, rays, hits, mask
+    api.lib().rtk_amd_forget_scene(ctypes.c_void_p(blob.ctypes.data))
+
+
+@pytest.mark.parametrize("n", [65535, 65536, 65537, 98305])
+def test_host_pointer_batches_around_the_pipeline_threshold(api, blob_and_device_answers, n):
+    """rtk_trace_rays on host rays: one piece below 2 x 32 768 rays, two staging sets in turn from there on (two whole pieces,
+    two and one ray, three whole pieces and one ray). Hits and mask equal the device calls' on the same rays, byte for byte;
+    the hit of a miss is left as it was."""
+    blob, rays, hits, mask = blob_and_device_answers
+    got_hits, got_mask = api.trace_rays(blob.ctypes.data, rays[:n])
+    assert got_mask.tobytes() == mask[:n].tobytes()
+    assert got_hits[mask[:n]].tobytes() == hits[:n][mask[:n]].tobytes()
+    assert not got_hits[~mask[:n]].view(np.uint8).any()
