@@ -19,28 +19,20 @@
 // alone, height by height as above. The result is bit for bit the full refit's; DESIGN.md 3.4a has the reasoning.
 // A box is made by the validator's rule (rtk_validate.hip: fminf / fmaxf over the vertices of a leaf, over the non-empty
 // slots of an inner child), so after a refit every box is the exact union of what is below it.
+// This file holds the kernels and the HIP calls. What the host decides between them -- refusals, where positions are read from
+// and staged, sizes and offsets, the workspace to borrow, runs, the dirty-set decision, which heights share a launch -- is
+// rtk_refit_plan.h, which includes no HIP; refit_on_device carries one plan out as stage_inputs, gather_triangles, remake_boxes,
+// finish_refit.
 #include "rtk_dev.h"
 #include "rtk_place_rule.h"
+#include "rtk_refit_plan.h"
 
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <vector>
 
 namespace {
-
-// where one mesh's positions are read from (device memory: the caller's own buffer or its copy in the workspace)
-struct RefitMesh {
-	const char *pos;
-	unsigned long long stride;
-	uint32_t f64;
-	uint32_t pad;
-};
-static_assert(sizeof(RefitMesh) == 24, "RefitMesh");
-
-#define REFIT_SMALL_THREADS 1024                 // k_refit_small: four lanes per node, 256 nodes per trip
-#define REFIT_SMALL_LEVEL 1024u                // heights of at most this many nodes go to k_refit_small
 
 // ---------------------------------------------------------------------------------- schedule (once per scene)
 
@@ -146,10 +138,6 @@ __global__ void __launch_bounds__(256) k_refit_tris(DevTri *tris, uint32_t n, co
 	const RefitMesh ms = meshes[mesh];
 	refit_tri<MODE, PLACED>(tris, s, vertex_index, ms, PLACED ? places + mesh : nullptr);
 }
-
-// A run of listed meshes that are neighbours in mesh_slots: its entries from entry_begin on belong to the threads from
-// thread_begin on (the last run is followed by one that begins at the thread count).
-struct RefitRange { uint32_t entry_begin, thread_begin; };
 
 // The slots of the listed meshes only, one thread each (RefitMesh::pos of a mesh that is not listed is NULL), and the dirty
 // set: every node from the slot's leaf up to the root gets dirty[node] = epoch. Plain stores of one and the same value by
@@ -406,15 +394,12 @@ __global__ void __launch_bounds__(REFIT_SMALL_THREADS) k_refit_small(DevNode *no
 	}
 }
 
-// ---------------------------------------------------------------------------------- host
+// ---------------------------------------------------------------------------------- host: tables made once per scene
+// (sizes, offsets, sort widths and the rules of the sweeps: rtk_refit_plan.h)
 
-// temporaries of the schedule: heights, the changed word, two key arrays, the sort's scratch, level starts
-struct ScheduleTmp { size_t o_height, o_changed, o_ka, o_kb, o_sort, o_ls, bytes; };
-ScheduleTmp schedule_tmp(uint32_t n)
-{
-	Carve c;       // (a braced list is evaluated left to right: the pieces in the order of the members, then their sum)
-	return ScheduleTmp{ c.take((size_t)n * 4), c.take(4), c.take((size_t)n * 8), c.take((size_t)n * 8), c.take(rtk_sort_scratch_words(n) * 4), c.take(((size_t)n + 2) * 4), c.bytes };
-}
+// what make_schedule allocates, given back on every way out that has not handed it to the scene
+struct FreeUnlessKept { void *&p; ~FreeUnlessKept() { if (p) (void)hipFree(p); } };
+#define SCHEDULE_CHECK(expr) do { if ((expr) != hipSuccess) { rtk_set_error("rtk_dev_scene_refit: schedule: %s failed: %s", #expr, hipGetErrorString(hipGetLastError())); return RTK_AMD_ERR_HIP; } } while (0)
 
 // heights, node numbers grouped by height, the mesh table's memory: once per scene. tmp: schedule_tmp(num_nodes).bytes of
 // device memory (the borrowed workspace: no allocation of a quarter of a gigabyte at 10M triangles, freed again at once)
@@ -424,75 +409,55 @@ int make_schedule(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
 	if (rs.ready) return RTK_AMD_OK;
 	const uint32_t n = ds->view.num_nodes;
 	const size_t num_meshes = ds->mesh_base.empty() ? 0 : ds->mesh_base.size() - 1;
-	const ScheduleTmp T = schedule_tmp(n);
+	const ScheduleTmp T = schedule_tmp(n, rtk_sort_scratch_words(n));
 	uint32_t *d_height = (uint32_t *)(tmp + T.o_height), *d_changed = (uint32_t *)(tmp + T.o_changed), *d_ls = (uint32_t *)(tmp + T.o_ls);
 	unsigned long long *keys_a = (unsigned long long *)(tmp + T.o_ka), *keys_b = (unsigned long long *)(tmp + T.o_kb);
 	void *d_order = nullptr, *d_small = nullptr;
+	FreeUnlessKept free_order{ d_order }, free_small{ d_small };
+	const unsigned blocks = (n + 255u) / 256u;
+	SCHEDULE_CHECK(hipMemsetAsync(d_height, 0, (size_t)n * 4, stream));
+	// the last sweep of a round must change nothing: the one wait of the host
 	int rc = RTK_AMD_OK;
-	std::vector<uint32_t> level_start;
-	Carve small;
-	do {
-#define SCHED_CHECK(expr) if ((expr) != hipSuccess) { rtk_set_error("rtk_dev_scene_refit: schedule: %s failed: %s", #expr, hipGetErrorString(hipGetLastError())); rc = RTK_AMD_ERR_HIP; break; }
-		const unsigned blocks = (n + 255u) / 256u;
-		SCHED_CHECK(hipMemsetAsync(d_height, 0, (size_t)n * 4, stream));
-		// A tree has no cycle and its heights are below max_depth, so max_depth sweeps settle them; one more, which must change
-		// nothing, is the proof, and the one wait of the host. (Should a scene's max_depth be too small the rounds go on, eight
-		// sweeps at a time.)
-		uint32_t sweeps = 0, round = ds->tree.max_depth < 4096u ? ds->tree.max_depth + 1u : 4096u;
-		bool converged = false;
-		while (!converged && rc == RTK_AMD_OK) {
-			uint32_t h_changed = 0;
-			for (uint32_t k = 0; k + 1u < round; k++) hipLaunchKernelGGL(k_refit_heights, dim3(blocks), dim3(256), 0, stream, ds->view.nodes, n, d_height, d_changed);
-			if (hipMemsetAsync(d_changed, 0, 4, stream) != hipSuccess) { rc = RTK_AMD_ERR_HIP; break; }
-			hipLaunchKernelGGL(k_refit_heights, dim3(blocks), dim3(256), 0, stream, ds->view.nodes, n, d_height, d_changed);
-			sweeps += round;
-			round = 8u;
-			if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&h_changed, d_changed, 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-				hipStreamSynchronize(stream) != hipSuccess) { rc = RTK_AMD_ERR_HIP; break; }
-			converged = h_changed == 0u;
-			if (!converged && sweeps > n + 8u) { rc = RTK_AMD_ERR_BAD_SCENE; break; }
-		}
-		if (rc != RTK_AMD_OK) { rtk_set_error("rtk_dev_scene_refit: schedule: heights did not settle (%s)", rc == RTK_AMD_ERR_HIP ? hipGetErrorString(hipGetLastError()) : "not a tree"); break; }
-		hipLaunchKernelGGL(k_refit_keys, dim3(blocks), dim3(256), 0, stream, d_height, n, keys_a);
-		// heights are below n: that many bits of the upper word, in whole 8-bit passes; stable, so numbers stay in order
-		const unsigned long long bound = n;
-		uint32_t bits = 1;
-		while (bits < 32u && (1ull << bits) <= bound) bits++;
-		const unsigned long long *sorted = keys_a;
-		if (n > 1u) sorted = rtk_sort_words_async(keys_a, keys_b, n, 32u, 32u + bits, (uint32_t *)(tmp + T.o_sort), stream) ? keys_b : keys_a;
-		SCHED_CHECK(hipMalloc(&d_order, (size_t)n * 4));
-		hipLaunchKernelGGL(k_refit_order, dim3(blocks), dim3(256), 0, stream, sorted, n, (uint32_t *)d_order, d_ls);
-		unsigned long long last = 0;
-		SCHED_CHECK(hipGetLastError());
-		SCHED_CHECK(hipMemcpyAsync(&last, sorted + (n - 1u), 8, hipMemcpyDeviceToHost, stream));
-		SCHED_CHECK(hipStreamSynchronize(stream));
-		const uint32_t heights = (uint32_t)(last >> 32) + 1u;
-		if (heights > n) { rtk_set_error("rtk_dev_scene_refit: schedule: %u heights for %u nodes", heights, n); rc = RTK_AMD_ERR_BAD_SCENE; break; }
-		level_start.resize((size_t)heights + 1);
-		SCHED_CHECK(hipMemcpy(level_start.data(), d_ls, level_start.size() * 4, hipMemcpyDeviceToHost));
-		bool sane = level_start.front() == 0u && level_start.back() == n;
-		for (size_t h = 0; h + 1 < level_start.size(); h++) sane = sane && level_start[h] < level_start[h + 1];
-		if (!sane) { rtk_set_error("rtk_dev_scene_refit: schedule: heights are not contiguous"); rc = RTK_AMD_ERR_BAD_SCENE; break; }
-		// the level starts and the mesh table share one small allocation. The table lies behind the carve: the last piece, not
-		// padded, with room for one record even where there is no mesh, which the ledger does not count
-		small.take(level_start.size() * 4);
-		SCHED_CHECK(hipMalloc(&d_small, small.bytes + (num_meshes ? num_meshes : 1) * sizeof(RefitMesh)));
-		SCHED_CHECK(hipMemcpy(d_small, level_start.data(), level_start.size() * 4, hipMemcpyHostToDevice));
-		rs.d_meshes = (char *)d_small + small.bytes;
-#undef SCHED_CHECK
-	} while (0);
-	if (rc != RTK_AMD_OK) {
-		if (d_order) (void)hipFree(d_order);
-		if (d_small) (void)hipFree(d_small);
-		rs.d_meshes = nullptr;
-		return rc;
+	uint32_t sweeps = 0;
+	for (bool first = true, converged = false; !converged && rc == RTK_AMD_OK; first = false) {
+		const uint32_t round = sweep_round(first, ds->tree.max_depth);
+		uint32_t h_changed = 0;
+		for (uint32_t k = 0; k + 1u < round; k++) hipLaunchKernelGGL(k_refit_heights, dim3(blocks), dim3(256), 0, stream, ds->view.nodes, n, d_height, d_changed);
+		if (hipMemsetAsync(d_changed, 0, 4, stream) != hipSuccess) { rc = RTK_AMD_ERR_HIP; break; }
+		hipLaunchKernelGGL(k_refit_heights, dim3(blocks), dim3(256), 0, stream, ds->view.nodes, n, d_height, d_changed);
+		sweeps += round;
+		if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&h_changed, d_changed, 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+			hipStreamSynchronize(stream) != hipSuccess) { rc = RTK_AMD_ERR_HIP; break; }
+		converged = h_changed == 0u;
+		if (!converged && sweeps_exhausted(sweeps, n)) rc = RTK_AMD_ERR_BAD_SCENE;
 	}
+	if (rc != RTK_AMD_OK) { rtk_set_error("rtk_dev_scene_refit: schedule: heights did not settle (%s)", rc == RTK_AMD_ERR_HIP ? hipGetErrorString(hipGetLastError()) : "not a tree"); return rc; }
+	hipLaunchKernelGGL(k_refit_keys, dim3(blocks), dim3(256), 0, stream, d_height, n, keys_a);
+	const unsigned long long *sorted = keys_a;
+	if (n > 1u) sorted = rtk_sort_words_async(keys_a, keys_b, n, 32u, 32u + height_sort_bits(n), (uint32_t *)(tmp + T.o_sort), stream) ? keys_b : keys_a;
+	SCHEDULE_CHECK(hipMalloc(&d_order, (size_t)n * 4));
+	hipLaunchKernelGGL(k_refit_order, dim3(blocks), dim3(256), 0, stream, sorted, n, (uint32_t *)d_order, d_ls);
+	unsigned long long last = 0;
+	SCHEDULE_CHECK(hipGetLastError());
+	SCHEDULE_CHECK(hipMemcpyAsync(&last, sorted + (n - 1u), 8, hipMemcpyDeviceToHost, stream));
+	SCHEDULE_CHECK(hipStreamSynchronize(stream));
+	const uint32_t heights = (uint32_t)(last >> 32) + 1u;
+	if (heights > n) { rtk_set_error("rtk_dev_scene_refit: schedule: %u heights for %u nodes", heights, n); return RTK_AMD_ERR_BAD_SCENE; }
+	std::vector<uint32_t> level_start;
+	level_start.resize((size_t)heights + 1);
+	SCHEDULE_CHECK(hipMemcpy(level_start.data(), d_ls, level_start.size() * 4, hipMemcpyDeviceToHost));
+	if (!level_starts_sane(level_start, n)) { rtk_set_error("rtk_dev_scene_refit: schedule: heights are not contiguous"); return RTK_AMD_ERR_BAD_SCENE; }
+	const ScheduleSmall small = schedule_small(heights, num_meshes);
+	SCHEDULE_CHECK(hipMalloc(&d_small, small.bytes));
+	SCHEDULE_CHECK(hipMemcpy(d_small, level_start.data(), level_start.size() * 4, hipMemcpyHostToDevice));
 	ds->mem.adopt(d_order, (size_t)n * 4);
-	ds->mem.adopt(d_small, small.counted + num_meshes * sizeof(RefitMesh));
+	ds->mem.adopt(d_small, small.counted);
 	rs.d_order = (uint32_t *)d_order;
 	rs.d_level_start = (uint32_t *)d_small;
+	rs.d_meshes = (char *)d_small + small.o_meshes;
 	rs.level_start.swap(level_start);
 	rs.ready = true;
+	d_order = d_small = nullptr;                               // (the scene's now)
 	return RTK_AMD_OK;
 }
 
@@ -518,14 +483,6 @@ int make_max_vertex(rtk_dev_scene *ds, hipStream_t stream)
 	return RTK_AMD_OK;
 }
 
-// temporaries of the per-mesh tables: two key arrays over the slots and the sort's scratch
-struct TablesTmp { size_t o_ka, o_kb, o_sort, bytes; };
-TablesTmp tables_tmp(uint32_t num_tris)
-{
-	Carve c;
-	return TablesTmp{ c.take((size_t)num_tris * 8), c.take((size_t)num_tris * 8), c.take(rtk_sort_scratch_words(num_tris) * 4), c.bytes };
-}
-
 // parent[], the node of every slot's leaf, the slots grouped by mesh, and the memory of the dirty set: once per scene, after
 // the schedule. tmp: tables_tmp(num_tris).bytes of device memory (the borrowed workspace).
 int make_partial_tables(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
@@ -535,26 +492,20 @@ int make_partial_tables(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
 	const DevSceneView &v = ds->view;
 	const uint32_t n = v.num_nodes, nt = v.num_tris;
 	const size_t num_meshes = ds->mesh_base.size() - 1;
-	const uint32_t nb = (n + RTK_DIRTY_BLOCK - 1u) / RTK_DIRTY_BLOCK;
-	const size_t heights = ds->refit.level_start.size() - 1;
-	Carve c;
-	const size_t o_parent = c.take((size_t)n * 4), o_slot_node = c.take((size_t)nt * 4), o_mesh_slots = c.take((size_t)nt * 4), o_dirty = c.take((size_t)n * 4),
-		o_list = c.take((size_t)n * 4), o_block = c.take(((size_t)nb + 1) * 4), o_list_start = c.take((heights + 1) * 4), o_ranges = c.take((num_meshes + 1) * sizeof(RefitRange));
+	const PartialTables P = partial_tables(n, nt, num_meshes, ds->refit.level_start.size() - 1, (n + RTK_DIRTY_BLOCK - 1u) / RTK_DIRTY_BLOCK);
 	void *mem = nullptr;
-	if (hipMalloc(&mem, c.bytes) != hipSuccess) { (void)hipGetLastError(); rtk_set_error("rtk_dev_scene_refit_meshes: out of device memory"); return RTK_AMD_ERR_OOM; }
+	if (hipMalloc(&mem, P.bytes) != hipSuccess) { (void)hipGetLastError(); rtk_set_error("rtk_dev_scene_refit_meshes: out of device memory"); return RTK_AMD_ERR_OOM; }
 	char *base = (char *)mem;
-	uint32_t *d_parent = (uint32_t *)(base + o_parent), *d_slot_node = (uint32_t *)(base + o_slot_node), *d_mesh_slots = (uint32_t *)(base + o_mesh_slots);
-	const TablesTmp T = tables_tmp(nt);
+	uint32_t *d_parent = (uint32_t *)(base + P.o_parent), *d_slot_node = (uint32_t *)(base + P.o_slot_node), *d_mesh_slots = (uint32_t *)(base + P.o_mesh_slots);
+	const TablesTmp T = tables_tmp(nt, rtk_sort_scratch_words(nt));
 	unsigned long long *keys_a = (unsigned long long *)(tmp + T.o_ka), *keys_b = (unsigned long long *)(tmp + T.o_kb);
 	// (RTK_REF_NONE everywhere first: the root has no parent, and a slot no leaf names stays without a node)
-	bool ok = hipMemsetAsync(base, 0xff, o_mesh_slots, stream) == hipSuccess && hipMemsetAsync(base + o_dirty, 0, o_list - o_dirty, stream) == hipSuccess;
+	bool ok = hipMemsetAsync(base, 0xff, P.o_mesh_slots, stream) == hipSuccess && hipMemsetAsync(base + P.o_dirty, 0, P.o_list - P.o_dirty, stream) == hipSuccess;
 	if (ok) {
 		hipLaunchKernelGGL(k_refit_parents, dim3((unsigned)(((size_t)n * 4 + 255) / 256)), dim3(256), 0, stream, v.nodes, n, v.tris, nt, d_parent, d_slot_node);
 		const unsigned blocks = (nt + 255u) / 256u;
 		hipLaunchKernelGGL(k_refit_mesh_keys, dim3(blocks), dim3(256), 0, stream, v.slot_mesh, nt, keys_a);
-		// mesh numbers are below num_meshes: that many bits of the upper word; stable, so the slots of a mesh stay ascending
-		uint32_t bits = 0;
-		while (bits < 32u && (1ull << bits) < (unsigned long long)num_meshes) bits++;
+		const uint32_t bits = mesh_sort_bits(num_meshes);
 		const unsigned long long *sorted = keys_a;
 		if (bits) sorted = rtk_sort_words_async(keys_a, keys_b, nt, 32u, 32u + bits, (uint32_t *)(tmp + T.o_sort), stream) ? keys_b : keys_a;
 		hipLaunchKernelGGL(k_refit_mesh_slots, dim3(blocks), dim3(256), 0, stream, sorted, nt, d_mesh_slots);
@@ -565,207 +516,151 @@ int make_partial_tables(rtk_dev_scene *ds, hipStream_t stream, char *tmp)
 		(void)hipFree(mem);
 		return RTK_AMD_ERR_HIP;
 	}
-	ds->mem.adopt(mem, c.counted);
+	ds->mem.adopt(mem, P.counted);
 	rp.d_parent = d_parent; rp.d_slot_node = d_slot_node; rp.d_mesh_slots = d_mesh_slots;
-	rp.d_dirty = (uint32_t *)(base + o_dirty); rp.d_list = (uint32_t *)(base + o_list); rp.d_block = (uint32_t *)(base + o_block);
-	rp.d_list_start = (uint32_t *)(base + o_list_start); rp.d_ranges = base + o_ranges;
+	rp.d_dirty = (uint32_t *)(base + P.o_dirty); rp.d_list = (uint32_t *)(base + P.o_list); rp.d_block = (uint32_t *)(base + P.o_block);
+	rp.d_list_start = (uint32_t *)(base + P.o_list_start); rp.d_ranges = base + P.o_ranges;
 	rp.epoch = 0;
 	rp.ready = true;
 	return RTK_AMD_OK;
 }
 
-// Above this share of the scene's triangles in the listed meshes the dirty-set passes lose against the full box and finish
-// passes, which then run instead (the triangles are still regathered for the listed meshes only). Where the two measured
-// curves meet, rounded down to a power of two: profiles/refit_meshes_timing.log. RTK_AMD_REFIT_MESHES_SHARE overrides it
-// (0: always the full passes, 1: never), for A/B; read at every call, so one process can measure both.
-#define REFIT_MESHES_MAX_SHARE 0.25
-double partial_max_share()
-{
-	const char *e = getenv("RTK_AMD_REFIT_MESHES_SHARE");
-	return e ? atof(e) : REFIT_MESHES_MAX_SHARE;
-}
+// ---------------------------------------------------------------------------------- host: one refit, step by step
 
-// everything behind the argument checks; the scene's device is current. listed: NULL = every mesh (rtk_dev_scene_refit), else
-// one flag per mesh (rtk_dev_scene_refit_meshes), with listed_tris triangles (not zero) in the flagged ones. placements: NULL, or
-// one per mesh (the _placed entry points; only the entries of meshes that are read are looked at).
-int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, const rtk_placement *placements, hipStream_t stream, WorkspaceLoan &loan, const uint8_t *listed, uint64_t listed_tris)
+// One call between its steps. listed: NULL = every mesh (rtk_dev_scene_refit), else one flag per mesh
+// (rtk_dev_scene_refit_meshes), with listed_tris triangles (not zero) in the flagged ones.
+struct RefitCall {
+	rtk_dev_scene *ds;
+	hipStream_t stream;
+	const uint8_t *listed;
+	uint64_t listed_tris;
+	RefitSource src;                           // where the positions are read from (plan_source)
+	const rtk_placement *d_places = nullptr;   // the placed forms: the placement table in the borrowed workspace, for the length of the call
+	bool dirty_set = false;                    // boxes and compressed nodes are remade for the nodes above the listed meshes alone
+};
+
+// The workspace, what is made once per scene in it, then the caller's host-resident positions and the placements in it, and
+// the mesh table that says where each mesh is read from.
+int stage_inputs(RefitCall &c, WorkspaceLoan &loan)
 {
-	int rc = rtk_scene_side_arrays(ds, stream);
-	if (rc != RTK_AMD_OK) return rc;
-	RefitSchedule &rs = ds->refit;
-	if (ds->view.num_nodes == 0u) { rtk_set_error("rtk_dev_scene_refit: scene without a root node"); return RTK_AMD_ERR_BAD_SCENE; }
+	rtk_dev_scene *ds = c.ds;
 	const DevSceneView &v = ds->view;
-	const size_t num_meshes = desc->num_meshes;
-
-	// ---- where every mesh's positions are read from
-	std::vector<RefitMesh> table(num_meshes ? num_meshes : 1, RefitMesh{ nullptr, 0ull, 0u, 0u });
-	std::vector<size_t> upload(num_meshes, 0);
-	size_t upload_bytes = 0;
-	bool any_device = false, any_f32 = false, any_f64 = false;
-	for (size_t mi = 0; mi < num_meshes; mi++) {
-		const rtk_mesh *m = &desc->meshes[mi];
-		if (m->num_triangles == 0 || (listed && !listed[mi])) continue;
-		RefitMesh &t = table[mi];
-		t.f64 = m->position.type == RTK_TYPE_F64 ? 1u : 0u;
-		t.stride = m->position.stride ? m->position.stride : (t.f64 ? 24 : 12);
-		t.pos = (const char *)m->position.data;
-		(t.f64 ? any_f64 : any_f32) = true;
-		if (rtk_is_device_ptr(m->position.data)) { any_device = true; continue; }
-		rc = make_max_vertex(ds, stream);
-		if (rc != RTK_AMD_OK) return rc;
-		upload[mi] = (size_t)rs.max_vertex[mi] * t.stride + (t.f64 ? 24 : 12);
-		upload_bytes += rtk_padded(upload[mi]);
-	}
-	// the placements of the meshes that are read go to the device beside the staged positions (entries of other meshes: zeros)
-	std::vector<rtk_placement> places;
-	if (placements) {
-		places.assign(num_meshes ? num_meshes : 1, rtk_placement{});
-		for (size_t mi = 0; mi < num_meshes; mi++) if (table[mi].pos) places[mi] = placements[mi];
-		upload_bytes += rtk_padded(places.size() * sizeof(rtk_placement));
-	}
-	// the workspace: first the temporaries of the schedule (the first refit of a scene; over when make_schedule returns), then
-	// those of the per-mesh tables (the first refit of some meshes), then the staged positions and placements
-	const size_t schedule_bytes = rs.ready ? 0 : schedule_tmp(ds->view.num_nodes).bytes;
-	const size_t tables_bytes = listed && !ds->partial.ready ? tables_tmp(v.num_tris).bytes : 0;
-	size_t borrow = schedule_bytes > upload_bytes ? schedule_bytes : upload_bytes;
-	if (tables_bytes > borrow) borrow = tables_bytes;
+	RefitSource &src = c.src;
+	const size_t borrow = plan_borrow(ds->refit.ready, schedule_tmp(v.num_nodes, rtk_sort_scratch_words(v.num_nodes)),
+		c.listed && !ds->partial.ready, tables_tmp(v.num_tris, rtk_sort_scratch_words(v.num_tris)), src.upload_bytes);
 	if (borrow && !loan.take(ds->device, borrow)) return RTK_AMD_ERR_OOM;
-	rc = make_schedule(ds, stream, loan.base);
+	int rc = make_schedule(ds, c.stream, loan.base);
+	if (rc == RTK_AMD_OK && c.listed) rc = make_partial_tables(ds, c.stream, loan.base);
 	if (rc != RTK_AMD_OK) return rc;
-	if (listed) {
-		rc = make_partial_tables(ds, stream, loan.base);
-		if (rc != RTK_AMD_OK) return rc;
+	for (size_t mi = 0; mi < src.staged.size(); mi++) {
+		if (!src.staged[mi]) continue;
+		RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(loan.base + src.staged_at[mi], src.table[mi].pos, src.staged[mi], hipMemcpyHostToDevice, c.stream));
+		src.table[mi].pos = loan.base + src.staged_at[mi];
 	}
-	const rtk_placement *d_places = nullptr;
-	if (upload_bytes) {
-		char *base = loan.base;
-		size_t off = 0;
-		for (size_t mi = 0; mi < num_meshes; mi++) {
-			if (!upload[mi]) continue;
-			RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(base + off, table[mi].pos, upload[mi], hipMemcpyHostToDevice, stream));
-			table[mi].pos = base + off;
-			off += rtk_padded(upload[mi]);
-		}
-		if (placements) {
-			RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(base + off, places.data(), places.size() * sizeof(rtk_placement), hipMemcpyHostToDevice, stream));
-			d_places = (const rtk_placement *)(base + off);
-		}
+	if (!src.places.empty()) {
+		RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(loan.base + src.places_at, src.places.data(), src.places.size() * sizeof(rtk_placement), hipMemcpyHostToDevice, c.stream));
+		c.d_places = (const rtk_placement *)(loan.base + src.places_at);
 	}
 	// a mesh in device memory was written by the caller's own work, possibly still in flight on the NULL stream (as in a build)
-	if (any_device && stream != nullptr) RTK_PASS_CHECK("rtk_dev_scene_refit", hipStreamSynchronize(nullptr));
-	if (num_meshes) RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(rs.d_meshes, table.data(), num_meshes * sizeof(RefitMesh), hipMemcpyHostToDevice, stream));
+	if (src.any_device && c.stream != nullptr) RTK_PASS_CHECK("rtk_dev_scene_refit", hipStreamSynchronize(nullptr));
+	if (!src.staged.empty()) RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(ds->refit.d_meshes, src.table.data(), src.staged.size() * sizeof(RefitMesh), hipMemcpyHostToDevice, c.stream));
+	return RTK_AMD_OK;
+}
 
-	// Until this call has succeeded nobody may take the boxes it leaves alone for exact unions.
-	const bool were_exact = ds->tree.boxes_exact;
-	ds->tree.boxes_exact = false;
-	// the dirty set pays while the listed meshes are a small part of the scene and the other boxes can be trusted
-	const bool dirty_set = listed && were_exact && (double)listed_tris <= partial_max_share() * (double)v.num_tris;
+// MODE, MARK and PLACED are compile-time variants, picked by the plan's mode and the call's flags: [!MARK][!PLACED][2 - MODE] and
+// [!PLACED][2 - MODE]. (The code object holds the instantiations in the order they are first named in, so the tables name them
+// in the order the launches always did: its bytes stay what they were.) The unplaced ones are what they were before there were
+// placements.
+typedef void (*RefitListedKernel)(DevTri *, uint32_t, const uint32_t *, const uint32_t *, const RefitMesh *, uint32_t, const uint32_t *, const uint32_t *, const RefitRange *, uint32_t,
+	uint32_t, const uint32_t *, uint32_t *, uint32_t, uint32_t, const rtk_placement *);
+typedef void (*RefitTrisKernel)(DevTri *, uint32_t, const uint32_t *, const uint32_t *, const RefitMesh *, uint32_t, const rtk_placement *);
+const RefitListedKernel LISTED_KERNELS[2][2][3] = {
+	{ { k_refit_tris_listed<2, true, true>, k_refit_tris_listed<1, true, true>, k_refit_tris_listed<0, true, true> },
+	  { k_refit_tris_listed<2, true, false>, k_refit_tris_listed<1, true, false>, k_refit_tris_listed<0, true, false> } },
+	{ { k_refit_tris_listed<2, false, true>, k_refit_tris_listed<1, false, true>, k_refit_tris_listed<0, false, true> },
+	  { k_refit_tris_listed<2, false, false>, k_refit_tris_listed<1, false, false>, k_refit_tris_listed<0, false, false> } } };
+const RefitTrisKernel TRIS_KERNELS[2][3] = {
+	{ k_refit_tris<2, true>, k_refit_tris<1, true>, k_refit_tris<0, true> }, { k_refit_tris<2, false>, k_refit_tris<1, false>, k_refit_tris<0, false> } };
 
-	// ---- triangles
+// The position bytes of the triangle records: of every slot, or of the listed meshes' slots, which also mark the dirty set.
+int gather_triangles(RefitCall &c)
+{
+	rtk_dev_scene *ds = c.ds;
+	const DevSceneView &v = ds->view;
+	DevTri *tris = const_cast<DevTri *>(v.tris);
+	const RefitMesh *dm = (const RefitMesh *)ds->refit.d_meshes;
+	const uint32_t num_meshes = (uint32_t)c.src.staged.size();
+	if (c.listed) {
+		RefitPartial &rp = ds->partial;
+		const RefitRuns runs = plan_runs(c.listed, ds->mesh_base, num_meshes);
+		RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(rp.d_ranges, runs.ranges.data(), runs.ranges.size() * sizeof(RefitRange), hipMemcpyHostToDevice, c.stream));
+		const EpochStep step = next_epoch(rp.epoch);
+		if (step.clear) RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemsetAsync(rp.d_dirty, 0, (size_t)v.num_nodes * 4, c.stream));
+		rp.epoch = step.epoch;                                     // (after the clear: one that fails is tried again by the next call)
+		const uint32_t total = (uint32_t)runs.threads;
+		hipLaunchKernelGGL(LISTED_KERNELS[!c.dirty_set][!c.d_places][2 - c.src.mode], dim3((total + 255u) / 256u), dim3(256), 0, c.stream, tris, v.num_tris, v.vertex_index,
+			v.slot_mesh, dm, num_meshes, rp.d_mesh_slots, rp.d_slot_node, (const RefitRange *)rp.d_ranges, (uint32_t)runs.ranges.size(), total, rp.d_parent, rp.d_dirty,
+			v.num_nodes, rp.epoch, c.d_places);
+	} else if (v.num_tris)
+		hipLaunchKernelGGL(TRIS_KERNELS[!c.d_places][2 - c.src.mode], dim3((v.num_tris + 255u) / 256u), dim3(256), 0, c.stream, tris, v.num_tris, v.vertex_index, v.slot_mesh, dm,
+			num_meshes, c.d_places);
+	RTK_PASS_CHECK("rtk_dev_scene_refit", hipGetLastError());
+	return RTK_AMD_OK;
+}
+
+// The child boxes, bottom-up by height: one walk over the launches the schedule's level starts give (plan_levels). The dirty-set
+// form first compacts the dirty nodes in the schedule's order and finds where each height begins among them (all of it stays on
+// the device); it then differs in the kernel of a large height, whose grid is capped because it strides, and in the node list and
+// starts k_refit_small is handed.
+int remake_boxes(RefitCall &c)
+{
+	rtk_dev_scene *ds = c.ds;
+	const DevSceneView &v = ds->view;
+	const RefitSchedule &rs = ds->refit;
+	const RefitPartial &rp = ds->partial;
 	DevTri *tris = const_cast<DevTri *>(v.tris);
 	DevNode *nodes = const_cast<DevNode *>(v.nodes);
-	const RefitMesh *dm = (const RefitMesh *)rs.d_meshes;
-	const int mode = any_f64 && any_f32 ? 2 : any_f64 ? 1 : 0;
-	if (listed) {
-		RefitPartial &rp = ds->partial;
-		// runs of listed meshes that are neighbours in mesh_slots, one thread per slot
-		std::vector<RefitRange> ranges;
-		uint64_t threads = 0, run_end = 0;
-		for (size_t mi = 0; mi < num_meshes; mi++) {
-			if (!listed[mi] || ds->mesh_base[mi + 1] == ds->mesh_base[mi]) continue;
-			if (ranges.empty() || run_end != ds->mesh_base[mi]) ranges.push_back(RefitRange{ (uint32_t)ds->mesh_base[mi], (uint32_t)threads });
-			threads += ds->mesh_base[mi + 1] - ds->mesh_base[mi];
-			run_end = ds->mesh_base[mi + 1];
-		}
-		RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(rp.d_ranges, ranges.data(), ranges.size() * sizeof(RefitRange), hipMemcpyHostToDevice, stream));
-		if (++rp.epoch == 0u) {                                  // (every 2^32 calls the flags start over)
-			RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemsetAsync(rp.d_dirty, 0, (size_t)v.num_nodes * 4, stream));
-			rp.epoch = 1u;
-		}
-		const uint32_t total = (uint32_t)threads;
-		const dim3 grid((total + 255u) / 256u), block(256);
-		const RefitRange *dr = (const RefitRange *)rp.d_ranges;
-		// (MODE and PLACED are compile-time variants: the unplaced instantiations are what they were before there were placements)
-#define LISTED_LAUNCH(MODE, MARK, PLACED) hipLaunchKernelGGL((k_refit_tris_listed<MODE, MARK, PLACED>), grid, block, 0, stream, tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, \
-	(uint32_t)num_meshes, rp.d_mesh_slots, rp.d_slot_node, dr, (uint32_t)ranges.size(), total, rp.d_parent, rp.d_dirty, v.num_nodes, rp.epoch, d_places)
-#define LISTED_MODES(MARK, PLACED) do { if (mode == 2) LISTED_LAUNCH(2, MARK, PLACED); else if (mode == 1) LISTED_LAUNCH(1, MARK, PLACED); else LISTED_LAUNCH(0, MARK, PLACED); } while (0)
-		if (dirty_set && d_places) LISTED_MODES(true, true);
-		else if (dirty_set) LISTED_MODES(true, false);
-		else if (d_places) LISTED_MODES(false, true);
-		else LISTED_MODES(false, false);
-#undef LISTED_MODES
-#undef LISTED_LAUNCH
-		RTK_PASS_CHECK("rtk_dev_scene_refit", hipGetLastError());
-	} else if (v.num_tris) {
-		const dim3 grid((v.num_tris + 255u) / 256u), block(256);
-#define TRIS_LAUNCH(MODE, PLACED) hipLaunchKernelGGL((k_refit_tris<MODE, PLACED>), grid, block, 0, stream, tris, v.num_tris, v.vertex_index, v.slot_mesh, dm, (uint32_t)num_meshes, d_places)
-#define TRIS_MODES(PLACED) do { if (mode == 2) TRIS_LAUNCH(2, PLACED); else if (mode == 1) TRIS_LAUNCH(1, PLACED); else TRIS_LAUNCH(0, PLACED); } while (0)
-		if (d_places) TRIS_MODES(true); else TRIS_MODES(false);
-#undef TRIS_MODES
-#undef TRIS_LAUNCH
-		RTK_PASS_CHECK("rtk_dev_scene_refit", hipGetLastError());
+	if (c.dirty_set) {
+		const uint32_t n = v.num_nodes, nb = (n + RTK_DIRTY_BLOCK - 1u) / RTK_DIRTY_BLOCK, heights = (uint32_t)rs.level_start.size() - 1u;
+		hipLaunchKernelGGL(k_dirty_count, dim3(nb), dim3(256), 0, c.stream, rs.d_order, n, rp.d_dirty, rp.epoch, rp.d_block);
+		hipLaunchKernelGGL(k_dirty_scan, dim3(1), dim3(1024), 0, c.stream, rp.d_block, nb, rs.d_order, n, rp.d_dirty, rp.epoch, rs.d_level_start, heights, rp.d_list_start);
+		hipLaunchKernelGGL(k_dirty_scatter, dim3(nb), dim3(256), 0, c.stream, rs.d_order, n, rp.d_dirty, rp.epoch, rp.d_block, rp.d_list);
 	}
+	const uint32_t *order = c.dirty_set ? rp.d_list : rs.d_order, *starts = c.dirty_set ? rp.d_list_start : rs.d_level_start;
+	for (const LevelStep &s : plan_levels(rs.level_start)) {
+		if (s.small) hipLaunchKernelGGL(k_refit_small, dim3(1), dim3(REFIT_SMALL_THREADS), 0, c.stream, nodes, tris, v.num_nodes, v.num_tris, order, starts, s.h, s.h1);
+		else if (c.dirty_set) hipLaunchKernelGGL(k_refit_level_list, dim3((unsigned)(s.blocks > 2048 ? 2048 : s.blocks)), dim3(256), 0, c.stream, nodes, tris, v.num_nodes, v.num_tris, order, starts, s.h);
+		else hipLaunchKernelGGL(k_refit_level, dim3((unsigned)s.blocks), dim3(256), 0, c.stream, nodes, tris, v.num_nodes, v.num_tris, order, s.begin, s.end);
+	}
+	RTK_PASS_CHECK("rtk_dev_scene_refit", hipGetLastError());
+	return RTK_AMD_OK;
+}
 
-	const uint32_t heights = (uint32_t)rs.level_start.size() - 1u;
+// Compressed nodes, order words and constants, and the host fields that follow from them.
+int finish_refit(RefitCall &c)
+{
+	rtk_dev_scene *ds = c.ds;
+	const DevSceneView &v = ds->view;
 	bool full_finish = true;
-	if (dirty_set) {
-		// ---- the dirty nodes in the schedule's order, and where each height begins among them (all of it stays on the device)
-		RefitPartial &rp = ds->partial;
-		const uint32_t n = v.num_nodes, nb = (n + RTK_DIRTY_BLOCK - 1u) / RTK_DIRTY_BLOCK;
-		hipLaunchKernelGGL(k_dirty_count, dim3(nb), dim3(256), 0, stream, rs.d_order, n, rp.d_dirty, rp.epoch, rp.d_block);
-		hipLaunchKernelGGL(k_dirty_scan, dim3(1), dim3(1024), 0, stream, rp.d_block, nb, rs.d_order, n, rp.d_dirty, rp.epoch, rs.d_level_start, heights, rp.d_list_start);
-		hipLaunchKernelGGL(k_dirty_scatter, dim3(nb), dim3(256), 0, stream, rs.d_order, n, rp.d_dirty, rp.epoch, rp.d_block, rp.d_list);
-		// ---- their boxes, height by height. Which heights get a launch of their own is the full schedule's decision (the host
-		// does not know the dirty counts): a height that is small there is small here.
-		for (uint32_t h = 0; h < heights;) {
-			const uint32_t begin = rs.level_start[h], end = rs.level_start[h + 1];
-			if (end - begin > REFIT_SMALL_LEVEL) {
-				size_t blocks = ((size_t)(end - begin) * 4 + 255) / 256;
-				if (blocks > 2048) blocks = 2048;
-				hipLaunchKernelGGL(k_refit_level_list, dim3((unsigned)blocks), dim3(256), 0, stream, nodes, tris, v.num_nodes, v.num_tris, rp.d_list, rp.d_list_start, h);
-				h++;
-			} else {
-				uint32_t h1 = h + 1;
-				while (h1 < heights && rs.level_start[h1 + 1] - rs.level_start[h1] <= REFIT_SMALL_LEVEL) h1++;
-				hipLaunchKernelGGL(k_refit_small, dim3(1), dim3(REFIT_SMALL_THREADS), 0, stream, nodes, tris, v.num_nodes, v.num_tris, rp.d_list, rp.d_list_start, h, h1);
-				h = h1;
-			}
-		}
-		RTK_PASS_CHECK("rtk_dev_scene_refit", hipGetLastError());
-		RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(&ds->partial_readback, rp.d_block + nb, 4, hipMemcpyDeviceToHost, stream));
-		// ---- compressed nodes and order words of the dirty nodes, the constants from the root (dirty whenever anything moved).
-		// The misfit count is one over ALL nodes: the list form is the whole answer only if the others have none (the scene is on
-		// its compressed nodes now) and none of the dirty ones has one either; else the full pass below.
+	if (c.dirty_set) {
+		const RefitPartial &rp = ds->partial;
+		const uint32_t nb = (v.num_nodes + RTK_DIRTY_BLOCK - 1u) / RTK_DIRTY_BLOCK;
+		RTK_PASS_CHECK("rtk_dev_scene_refit", hipMemcpyAsync(&ds->partial_readback, rp.d_block + nb, 4, hipMemcpyDeviceToHost, c.stream));
+		// Of the dirty nodes, the constants from the root (dirty whenever anything moved). The misfit count is one over ALL nodes:
+		// the list form is the whole answer only if the others have none (the scene is on its compressed nodes now) and none of
+		// the dirty ones has one either; else the full pass below.
 		if (v.qnodes && ds->tree.qnodes_mem) {
-			rc = rtk_quantize_node_list(ds, stream, rp.d_list, rp.d_block + nb);
+			const int rc = rtk_quantize_node_list(ds, c.stream, rp.d_list, rp.d_block + nb);
 			if (rc != RTK_AMD_OK) return rc;
-			RTK_PASS_CHECK("rtk_dev_scene_refit", hipStreamSynchronize(stream));
+			RTK_PASS_CHECK("rtk_dev_scene_refit", hipStreamSynchronize(c.stream));
 			full_finish = ds->tree.consts_readback.qnode_misfits != 0u;
 		}
-	} else {
-		// ---- boxes, height by height; runs of small heights share one launch of one workgroup
-		for (uint32_t h = 0; h < heights;) {
-			const uint32_t begin = rs.level_start[h], end = rs.level_start[h + 1];
-			if (end - begin > REFIT_SMALL_LEVEL) {
-				const unsigned blocks = (unsigned)(((size_t)(end - begin) * 4 + 255) / 256);
-				hipLaunchKernelGGL(k_refit_level, dim3(blocks), dim3(256), 0, stream, nodes, tris, v.num_nodes, v.num_tris, rs.d_order, begin, end);
-				h++;
-			} else {
-				uint32_t h1 = h + 1;
-				while (h1 < heights && rs.level_start[h1 + 1] - rs.level_start[h1] <= REFIT_SMALL_LEVEL) h1++;
-				hipLaunchKernelGGL(k_refit_small, dim3(1), dim3(REFIT_SMALL_THREADS), 0, stream, nodes, tris, v.num_nodes, v.num_tris, rs.d_order, rs.d_level_start, h, h1);
-				h = h1;
-			}
-		}
-		RTK_PASS_CHECK("rtk_dev_scene_refit", hipGetLastError());
 	}
-
 	if (full_finish) {
-		// ---- compressed nodes, order words, constants (the block is cleared first: the misfit count starts at zero); every box
-		// lies inside the root's now, so no bound is passed in
-		rc = rtk_quantize_nodes(ds, stream, nullptr, const_cast<DevNodeQ *>(ds->tree.qnodes_mem), 0.0f, 0xffffffffu, false, true);
+		// (the block is cleared first: the misfit count starts at zero); every box lies inside the root's now, so no bound is passed in
+		const int rc = rtk_quantize_nodes(ds, c.stream, nullptr, const_cast<DevNodeQ *>(ds->tree.qnodes_mem), 0.0f, 0xffffffffu, false, true);
 		if (rc != RTK_AMD_OK) return rc;
-		RTK_PASS_CHECK("rtk_dev_scene_refit", hipStreamSynchronize(stream));
+		RTK_PASS_CHECK("rtk_dev_scene_refit", hipStreamSynchronize(c.stream));
 	}
 	{
 		// (the trace path reads these host fields under the same mutex when it enqueues a launch)
@@ -774,8 +669,32 @@ int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, const rtk_pla
 	}
 	rtk_scene_forget_derived(ds, RTK_FORGET_BOXES);
 	ds->tree.boxes_exact = true;
-	ds->refit_nodes = dirty_set ? ds->partial_readback : v.num_nodes;
+	ds->refit_nodes = c.dirty_set ? ds->partial_readback : v.num_nodes;
 	return RTK_AMD_OK;
+}
+
+// everything behind the argument checks; the scene's device is current. placements: NULL, or one per mesh (the _placed entry
+// points; only the entries of meshes that are read are looked at).
+int refit_on_device(rtk_dev_scene *ds, const rtk_scene_desc *desc, const rtk_placement *placements, hipStream_t stream, WorkspaceLoan &loan, const uint8_t *listed, uint64_t listed_tris)
+{
+	int rc = rtk_scene_side_arrays(ds, stream);
+	if (rc != RTK_AMD_OK) return rc;
+	if (ds->view.num_nodes == 0u) { rtk_set_error("rtk_dev_scene_refit: scene without a root node"); return RTK_AMD_ERR_BAD_SCENE; }
+	RefitCall c{ ds, stream, listed, listed_tris, plan_source(desc, placements, listed, rtk_is_device_ptr, ds->refit.max_vertex_ready ? ds->refit.max_vertex.data() : nullptr) };
+	if (c.src.need_max_vertex) {
+		rc = make_max_vertex(ds, stream);
+		if (rc != RTK_AMD_OK) return rc;
+		c.src = plan_source(desc, placements, listed, rtk_is_device_ptr, ds->refit.max_vertex.data());
+	}
+	rc = stage_inputs(c, loan);
+	if (rc != RTK_AMD_OK) return rc;
+	// Until this call has succeeded nobody may take the boxes it leaves alone for exact unions.
+	c.dirty_set = plan_dirty_set(listed != nullptr, ds->tree.boxes_exact, listed_tris, ds->view.num_tris, partial_max_share());
+	ds->tree.boxes_exact = false;
+	rc = gather_triangles(c);
+	if (rc == RTK_AMD_OK) rc = remake_boxes(c);
+	if (rc == RTK_AMD_OK) rc = finish_refit(c);
+	return rc;
 }
 
 // what both entry points do once nothing can be refused any more
@@ -788,38 +707,6 @@ int refit_in_pass(ScenePass &pass, const rtk_scene_desc *desc, const rtk_placeme
 	loan.release();
 	if (rc == RTK_AMD_OK) pass.ds->refit_ms = pass.ms();
 	return rc;
-}
-
-// the rules for the positions of a mesh that is read
-int check_mesh_positions(const char *who, const rtk_mesh *m, size_t mi)
-{
-	if (m->position_cb) { rtk_set_error("%s: mesh %zu: position callbacks are not supported by a refit", who, mi); return RTK_AMD_ERR_UNSUPPORTED; }
-	if (m->num_triangles == 0) return RTK_AMD_OK;
-	if (m->position.type != RTK_TYPE_DEFAULT && m->position.type != RTK_TYPE_REAL && m->position.type != RTK_TYPE_F32 && m->position.type != RTK_TYPE_F64) {
-		rtk_set_error("%s: mesh %zu: bad position type %d", who, mi, (int)m->position.type);
-		return RTK_AMD_ERR_BAD_ARG;
-	}
-	if (!m->position.data) { rtk_set_error("%s: mesh %zu has no positions", who, mi); return RTK_AMD_ERR_BAD_ARG; }
-	return RTK_AMD_OK;
-}
-
-// the description against the scene it claims to describe
-int check_desc(const char *who, const rtk_dev_scene *ds, const rtk_scene_desc *desc)
-{
-	if (!desc->meshes && desc->num_meshes) { rtk_set_error("%s: NULL meshes", who); return RTK_AMD_ERR_BAD_ARG; }
-	const size_t scene_meshes = ds->mesh_base.empty() ? 0 : ds->mesh_base.size() - 1;
-	if (desc->num_meshes != scene_meshes) {
-		rtk_set_error("%s: %zu meshes, the scene was made from %zu", who, (size_t)desc->num_meshes, scene_meshes);
-		return RTK_AMD_ERR_BAD_ARG;
-	}
-	for (size_t mi = 0; mi < desc->num_meshes; mi++) {
-		const uint64_t have = ds->mesh_base[mi + 1] - ds->mesh_base[mi];
-		if ((uint64_t)desc->meshes[mi].num_triangles != have) {
-			rtk_set_error("%s: mesh %zu has %zu triangles, the scene's has %llu", who, mi, (size_t)desc->meshes[mi].num_triangles, (unsigned long long)have);
-			return RTK_AMD_ERR_BAD_ARG;
-		}
-	}
-	return RTK_AMD_OK;
 }
 
 } // namespace
@@ -842,16 +729,11 @@ void RefitPartial::reset(SceneMem &mem)
 }
 
 // Both full refits. who: the public function the error texts name; placements: NULL (rtk_dev_scene_refit) or one per mesh.
+// Everything that can be refused is refused by the check, before HIP is touched.
 static int refit_all(const char *who, rtk_dev_scene *ds, const rtk_scene_desc *desc, const rtk_placement *placements, bool placed, void *stream)
 {
-	// ---- everything that can be refused is refused here, before HIP is touched
-	if (!ds || !desc || (placed && !placements)) { rtk_set_error("%s: NULL argument", who); return RTK_AMD_ERR_BAD_ARG; }
-	int rc = check_desc(who, ds, desc);
-	if (rc != RTK_AMD_OK) return rc;
-	for (size_t mi = 0; mi < desc->num_meshes; mi++) {
-		rc = check_mesh_positions(who, &desc->meshes[mi], mi);
-		if (rc != RTK_AMD_OK) return rc;
-	}
+	const RefitScope scope = check_refit_all(rtk_set_error, who, ds ? &ds->mesh_base : nullptr, desc, placements, placed);
+	if (scope.rc != RTK_AMD_OK) return scope.rc;
 	ScenePass pass(ds, stream);
 	return refit_in_pass(pass, desc, placements, nullptr, 0);
 }
@@ -860,32 +742,15 @@ static int refit_all(const char *who, rtk_dev_scene *ds, const rtk_scene_desc *d
 static int refit_some(const char *who, rtk_dev_scene *ds, const rtk_scene_desc *desc, const rtk_placement *placements, bool placed, const uint32_t *mesh_ids,
 	size_t num_ids, void *stream)
 {
-	// ---- as above: every refusal before HIP is touched; only the listed meshes' positions (and placements) are looked at
-	if (!ds || !desc || (placed && !placements)) { rtk_set_error("%s: NULL argument", who); return RTK_AMD_ERR_BAD_ARG; }
-	if (!mesh_ids && num_ids) { rtk_set_error("%s: NULL mesh_ids with %zu ids", who, num_ids); return RTK_AMD_ERR_BAD_ARG; }
-	int rc = check_desc(who, ds, desc);
-	if (rc != RTK_AMD_OK) return rc;
-	std::vector<uint8_t> listed(desc->num_meshes ? desc->num_meshes : 1, 0);
-	for (size_t k = 0; k < num_ids; k++) {
-		if (mesh_ids[k] >= desc->num_meshes) { rtk_set_error("%s: mesh id %u, the scene has %zu meshes", who, mesh_ids[k], (size_t)desc->num_meshes); return RTK_AMD_ERR_BAD_ARG; }
-		listed[mesh_ids[k]] = 1;                                 // (an id that repeats counts once)
-	}
-	uint64_t listed_tris = 0;
-	for (size_t mi = 0; mi < desc->num_meshes; mi++) {
-		if (!listed[mi]) continue;
-		rc = check_mesh_positions(who, &desc->meshes[mi], mi);
-		if (rc != RTK_AMD_OK) return rc;
-		listed_tris += desc->meshes[mi].num_triangles;
-	}
+	const RefitScope scope = check_refit_some(rtk_set_error, who, ds ? &ds->mesh_base : nullptr, desc, placements, placed, mesh_ids, num_ids);
+	if (scope.rc != RTK_AMD_OK) return scope.rc;
 	ScenePass pass(ds, stream);
-	if (listed_tris == 0) {
-		// nothing moves: no bit changes, nothing is launched
+	if (scope.nothing) {
 		ds->refit_nodes = 0;
 		ds->refit_ms = 0.0;
 		return RTK_AMD_OK;
 	}
-	// every mesh that has a triangle is listed: that IS the full refit (no mesh it would read is one this call may not read)
-	return refit_in_pass(pass, desc, placements, listed_tris == ds->mesh_base.back() ? nullptr : listed.data(), listed_tris);
+	return refit_in_pass(pass, desc, placements, scope.listed(), scope.listed_tris);
 }
 
 extern "C" int rtk_dev_scene_refit(rtk_dev_scene *ds, const rtk_scene_desc *desc, void *stream)

@@ -217,6 +217,36 @@ def test_sizes(api, n, spread):
     assert _valid(tw.A)["content_hash"] == h0
 
 
+@pytest.mark.parametrize("share", [None, "0", "1"], ids=["default", "share0", "share1"])
+def test_first_call_ever_is_a_placed_refit_of_one_f64_host_mesh(api, monkeypatch, share):
+    """The first refit a scene sees lists one mesh, host-resident doubles, with a placement: the schedule's temporaries, those of
+    the per-mesh tables, the staged positions and the placement table all take their turn in ONE loan of the workspace. With the
+    dirty set (the default share, and 1) and with the full passes (0) the scene is, byte for byte, what the full placed refit of
+    a twin makes of the same inputs. 10 000 triangles: heights with a launch of their own and a run of small ones. (Both scenes
+    are built through the identity, so every other mesh has gone through the one rule on both sides.)"""
+    from tests.test_gpu_placed import ROT_TRANS
+    if share is None:
+        monkeypatch.delenv("RTK_AMD_REFIT_MESHES_SHARE", raising=False)
+    else:
+        monkeypatch.setenv("RTK_AMD_REFIT_MESHES_SHARE", share)
+    parts = by_slab(synth.triangle_soup(10_000, 0.05, seed=17), 16)
+    meshes = [dict(positions=p) for p in parts]
+    placements = np.tile(np.eye(3, 4, dtype=np.float32), (16, 1, 1))
+    A, B = api.DeviceScene.build(meshes, placements=placements), api.DeviceScene.build(meshes, placements=placements)
+    assert A.last_refit_nodes() == 0 and A.export_blob().tobytes() == B.export_blob().tobytes()
+    num_nodes = A.info()["num_nodes"]
+    moved = dict(positions=deform(parts[5], 1, extent(parts)).astype(np.float64))
+    placements[5] = ROT_TRANS
+    given = np.full_like(placements, np.nan)                    # (entries of unlisted meshes are not read)
+    given[5] = ROT_TRANS
+    A.refit([moved if m == 5 else None for m in range(16)], only=[5], placements=given)
+    B.refit([moved if m == 5 else meshes[m] for m in range(16)], placements=placements)
+    assert A.export_blob().tobytes() == B.export_blob().tobytes()
+    assert _valid(A) == _valid(B)
+    assert B.last_refit_nodes() == num_nodes
+    assert A.last_refit_nodes() == num_nodes if share == "0" else 0 < A.last_refit_nodes() < num_nodes
+
+
 def test_nothing_to_move(api):
     """A scene without triangles, and a listed mesh without triangles: fine, and no bit changes."""
     none = np.zeros((0, 3), np.float32)
