@@ -10,7 +10,7 @@ the fixtures therefore come from the reference's code, not from the restatement.
 
 Fixtures hold data only: seeds/inputs (or their SHA-256) and expected hit records.
 
-    python3 oracle/gen_golden.py [--only cfg1,edge,...] [--cfg5-rays N]
+    python3 oracle/gen_golden.py [--only cfg1,edge,...,group_redo] [--cfg5-rays N]
 """
 import argparse
 import hashlib
@@ -338,6 +338,147 @@ def gen_tiny_t(tris, thresh=1e-6):
     save("tiny_t.npz", scene_sha256=sha(tris), thresh=np.float64(thresh), **out)
 
 
+GROUP_REDO_RAYS = 252          # per case: 3 vertices of X x 3 targets x 28
+
+
+def group_redo_cases():
+    """(name, leaf size, slots of the zero-triangles in P, slots they are swapped to in Q, control, X in a mesh of its own).
+    A leaf of n triangles has n // 4 full groups and, if n % 4, one padded group (rtk.c:212). Per size: slot 0 and slot 3 of the
+    first full group, a middle group, the last full group and the padded group, where the size has them."""
+    C = []
+
+    def case(n, slot, what, q=None, **kw):
+        control = slot // 4 >= n // 4
+        if q is None and not control and n > 4:
+            q = n - 1 if (n - 1) // 4 != slot // 4 else 0       # X changes places with a triangle of another group
+        C.append(dict(name="n%02d_%s" % (n, what), n=n, slots=[slot], q_slots=None if q is None else [q], control=control,
+                      own_mesh=kw.get("own_mesh", False)))
+    case(4, 0, "first0"); case(4, 3, "first3")
+    case(5, 0, "first0"); case(5, 3, "first3"); case(5, 4, "padded")
+    case(8, 0, "first0"); case(8, 3, "first3"); case(8, 5, "last")
+    case(11, 0, "first0"); case(11, 3, "first3"); case(11, 6, "last"); case(11, 9, "padded")
+    case(12, 0, "first0"); case(12, 3, "first3"); case(12, 5, "middle"); case(12, 10, "last")
+    case(63, 0, "first0"); case(63, 3, "first3"); case(63, 29, "middle"); case(63, 58, "last"); case(63, 61, "padded")
+    # two zero-triangles that share a vertex, in the first and the last full group; Q puts both into the middle one
+    C.append(dict(name="n12_two", n=12, slots=[1, 9], q_slots=[4, 5], control=False, own_mesh=False))
+    case(8, 1, "ownmesh", own_mesh=True)
+    return C
+
+
+def group_redo_leaf(c, seed):
+    """Triangles, the two leaf orders and the rays of one case. Triangle ids are the soup's; X is id 0 (and 1). The three
+    triangles nearest to an X share its group in P (in the control: the first full group), so that rays from X's vertices
+    towards them mostly arrive. Returns P and Q as (tris[m,3,3], triangle_index[m], mesh_index[m]) in slot order, and rays."""
+    n, nx = c["n"], len(c["slots"])
+    tv = synth.triangle_soup(n, 0.6, seed=seed).reshape(n, 3, 3).copy()
+    if nx == 2:
+        tv[1, 0] = tv[0, 0]                                      # one ray origin with exact zeros in two groups
+    cen = tv.astype(np.float64).mean(axis=1)
+    free = list(range(nx, n))
+    mates = []
+    for x in range(nx):
+        near = sorted(free, key=lambda i: (float(((cen[i] - cen[x]) ** 2).sum()), i))[:3]
+        mates.append(near)
+        free = [i for i in free if i not in near]
+    p = [-1] * n
+    for x, s in enumerate(c["slots"]):
+        p[s] = x
+    for x, s in enumerate(c["slots"]):
+        g = 0 if c["control"] else s // 4
+        holes = [k for k in range(4 * g, 4 * g + 4) if p[k] < 0]
+        for k, m in zip(holes, mates[x]):
+            p[k] = m
+    rest = iter(free)
+    p = [i if i >= 0 else next(rest) for i in p]
+    assert sorted(p) == list(range(n))
+    tris, q = tv, list(p)
+    if c["control"]:
+        full = 4 * (n // 4)
+        q[:full] = q[:full][::-1]                                # X stays padded; the float groups are merely re-ordered
+    elif n == 4:
+        # a lone full group has no other group: a fifth triangle far behind every ray takes X's slot and X becomes a padded group of one
+        far = np.array([[-50, 60, -70], [-50.01, 60, -70], [-50, 60.01, -70.005]], np.float32)
+        tris = np.concatenate([tv, far[None]])
+        q[c["slots"][0]] = n
+        q.append(0)
+    else:
+        for s, t in zip(c["slots"], c["q_slots"]):
+            assert s // 4 != t // 4
+            q[s], q[t] = q[t], q[s]
+    mesh_of = np.zeros(len(tris), np.uint32)
+    if c["own_mesh"]:
+        mesh_of[0] = 1
+    p, q = np.array(p), np.array(q)
+    k = GROUP_REDO_RAYS
+    u = synth.u01(seed, 1 << 20, 2 * k).reshape(k, 2)
+    i = np.arange(k)
+    x = (i // 9) % nx
+    corner = i % 3 if nx == 1 else np.zeros(k, np.int64)         # two Xs: the shared vertex only
+    target = np.array(mates)[x, (i // 3) % 3]
+    a, b = u[:, 0], u[:, 1]
+    flip = a + b > np.float32(1.0)
+    a = np.where(flip, np.float32(1.0) - a, a).astype(np.float32)
+    b = np.where(flip, np.float32(1.0) - b, b).astype(np.float32)
+    v = tv[target]
+    point = v[:, 0] + a[:, None] * (v[:, 1] - v[:, 0]) + b[:, None] * (v[:, 2] - v[:, 0])
+    rays = np.zeros(k, RAY_DTYPE)
+    rays["origin"] = tv[x, corner]
+    rays["direction"] = (point - rays["origin"]).astype(np.float32)
+    rays["min_t"] = 0
+    rays["max_t"] = np.float32(3e38)
+    return (tris[p], p.astype(np.uint32), mesh_of[p]), (tris[q], q.astype(np.uint32), mesh_of[q]), rays
+
+
+def save_reproducible(name, **kw):
+    """np.savez_compressed with fixed member dates, so that the same arrays give the same file."""
+    import io
+    import zipfile
+    path = os.path.join(GOLDEN, name)
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for key in sorted(kw):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(kw[key]), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+    print("wrote %s (%.1f KB)" % (path, os.path.getsize(path) / 1024.0))
+
+
+def gen_group_redo():
+    """tests/golden/group_redo.npz: single leaves of 4 .. 63 triangles and rays that start bit-exactly on a vertex of one of them
+    (X), so that X's group of four has an exactly-zero edge function and is redone in double precision (rtk.c:302-336) while
+    the other full groups stay float. Each case holds the REAL rtk.c's answers on the leaf in order P and on the same triangles
+    (same ids) in order Q, where X sits in another group: where the two differ in the bits of t, u, v, equality with P shows that
+    a traversal redid the right group. In the control cases X is in the padded group, which is double anyway, and P equals Q."""
+    out = dict(cases=np.array([c["name"] for c in group_redo_cases()]), control=np.array([c["control"] for c in group_redo_cases()]))
+    for ci, c in enumerate(group_redo_cases()):
+        P, Q, rays = group_redo_leaf(c, seed=7700 + ci)
+        res = []
+        for tris, tri_index, mesh_index in (P, Q):
+            blobs = po.leaf_chain_blobs(tris, mesh_index, tri_index, chunk=63)
+            assert len(blobs) == 1
+            hits, mask = po.ref_trace_chain(blobs, rays, threads=1)
+            assert not (mask & (hits["triangle_index"] >= c["n"])).any()           # nothing reaches the n = 4 filler
+            res.append(compact(hits, mask))
+        hp, hq = res
+        same = hp["hit_mask"].astype(bool) & hq["hit_mask"].astype(bool) & (hp["hit_tri"] == hq["hit_tri"])
+        differ = same & ((hp["hit_t"].view(np.uint32) != hq["hit_t"].view(np.uint32)) | (hp["hit_u"].view(np.uint32) != hq["hit_u"].view(np.uint32)) |
+                         (hp["hit_v"].view(np.uint32) != hq["hit_v"].view(np.uint32)))
+        print("  %-12s hits P %3d Q %3d, same triangle %3d, of those t/u/v bits differ on %3d (%.0f %%)"
+              % (c["name"], int(hp["hit_mask"].sum()), int(hq["hit_mask"].sum()), int(same.sum()), int(differ.sum()), 100.0 * differ.sum() / max(1, same.sum())))
+        n = c["name"]
+        out[n + "_x"] = np.arange(len(c["slots"]), dtype=np.uint32)
+        out[n + "_rays"] = rays.view(np.float32).reshape(-1, 8)
+        for tag, (tris, tri_index, mesh_index), h in (("p", P, hp), ("q", Q, hq)):
+            out["%s_%s_tris" % (n, tag)] = tris
+            out["%s_%s_tri" % (n, tag)] = tri_index
+            out["%s_%s_mesh" % (n, tag)] = mesh_index
+            for k, v in h.items():
+                out["%s_%s_%s" % (n, tag, k)] = v
+    save_reproducible("group_redo.npz", **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="edge,cfg1,cfg2,cfg3,cfg5")
@@ -367,6 +508,8 @@ def main():
             gen_cfg3(tris)
     if "cfg5" in only:
         gen_cfg5(a.cfg5_rays)
+    if "group_redo" in only:
+        gen_group_redo()
 
 
 if __name__ == "__main__":

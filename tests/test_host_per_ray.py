@@ -78,6 +78,32 @@ def test_exotic_rays_bit_exact_with_the_reference(host_lib, oracle, golden_dir):
         assert (hits[f][mask].view(np.uint32) == g[k][gm].view(np.uint32)).all(), f
 
 
+def test_exact_zeros_in_full_groups_bit_exact_with_the_reference(host_lib, oracle, golden_dir):
+    """tests/golden/group_redo.npz: leaves of 4 .. 63 triangles, rays that start on a vertex of one triangle X, so that X's full group
+    of four -- and no other -- is redone with the double-precision edge functions (rtk.c:302-336). rtk_trace_ray on the host carries
+    its own copy of that rule: the REAL rtk.c's hit / miss, ids and t, u, v bits on the leaf in order P and in order Q (X in another
+    group), and every byte of the oracle's rtk_hit. Precondition, asserted: where X is in a full group at least a quarter of the rays
+    that hit one triangle on both orders differ in those bits between P and Q, so equality with P is evidence of the redo."""
+    from tests.util import GROUP_REDO_MIN_SHARE, group_redo_cases
+    caught = 0
+    for c in group_redo_cases(golden_dir):
+        same, differ = c.same_triangle(), c.bits_differ()
+        assert c.control or differ.sum() >= GROUP_REDO_MIN_SHARE * same.sum(), c.name
+        assert not (c.control and differ.any()), c.name
+        caught += int(differ.sum())
+        for order, want in (("p", c.p), ("q", c.q)):
+            blob = c.blob(oracle, order)
+            hits, mask = _per_ray(host_lib, blob.ptr, c.rays)
+            gm = want["hit_mask"].astype(bool)
+            assert (mask == gm).all(), (c.name, order)
+            assert (hits["triangle_index"][mask] == want["hit_tri"][gm]).all() and (hits["mesh_index"][mask] == want["hit_mesh"][gm]).all(), (c.name, order)
+            for f, k in (("t", "hit_t"), ("u", "hit_u"), ("v", "hit_v")):
+                assert (hits[f][mask].view(np.uint32) == want[k][gm].view(np.uint32)).all(), (c.name, order, f)
+            oh, om = oracle.trace(blob, c.rays, ties=oracle.TIES_REFERENCE, threads=1)
+            assert (om == mask).all() and hits[mask].tobytes() == oh[om].tobytes(), (c.name, order)
+    assert caught > 3000                                                  # rays on which a missing redo would have shown
+
+
 def test_config1_full_on_a_bvh4_blob(host_lib, oracle, golden_dir):
     """All 65 536 rays of config 1 on the oracle's SAH blob: the fixture's ids (real rtk.c), and every byte of (mesh, triangle, t,
     u, v, the three vertices) the oracle returns on the same blob."""

@@ -137,3 +137,73 @@ def test_exotic_rays_chain_bit_exact(oracle, golden_dir, scene1):
     assert (hits["triangle_index"][mask] == g["hit_tri"][gm]).all()
     for f, k in (("t", "hit_t"), ("u", "hit_u"), ("v", "hit_v")):
         assert (hits[f][mask].view(np.uint32) == g[k][gm].view(np.uint32)).all(), f
+
+
+def _group_redo_ids():
+    import os
+    from tests.util import group_redo_cases
+    return [c.name for c in group_redo_cases(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))]
+
+
+@pytest.mark.parametrize("name", _group_redo_ids())
+def test_group_redo_oracle_equals_the_reference_on_both_orders(oracle, golden_dir, name):
+    """tests/golden/group_redo.npz: a ray that starts bit-exactly on a vertex of triangle X has exactly-zero edge functions for X,
+    which switches X's whole group of four -- and no other full group -- to the double-precision edge functions (rtk.c:302-336).
+    The oracle must return the REAL rtk.c's hit / miss, ids and t, u, v bits on the leaf in order P and on the same triangles in
+    order Q (X in another group): that pins its switch for the other three members of a group, which near_ties.npz (four copies
+    of one triangle) does not. The precondition every later user of the fixture relies on is asserted here as a condition: with X
+    in a full group, at least a quarter of the rays that hit one triangle on P and on Q differ in the bits of t, u or v, so an
+    answer equal to P's cannot come from a traversal that grouped differently; with X in the padded group (double anyway) P
+    equals Q although Q's float groups are in another order."""
+    from tests.util import GROUP_REDO_MIN_SHARE, group_redo_cases
+    c = [k for k in group_redo_cases(golden_dir) if k.name == name][0]
+    for order, want in (("p", c.p), ("q", c.q)):
+        hits, mask = oracle.trace_chain([c.blob(oracle, order)], c.rays, threads=1)
+        gm = want["hit_mask"].astype(bool)
+        assert (mask == gm).all(), order
+        assert (hits["triangle_index"][mask] == want["hit_tri"][gm]).all() and (hits["mesh_index"][mask] == want["hit_mesh"][gm]).all(), order
+        for f, k in (("t", "hit_t"), ("u", "hit_u"), ("v", "hit_v")):
+            assert (hits[f][mask].view(np.uint32) == want[k][gm].view(np.uint32)).all(), (order, f)
+    # rays start on a vertex of X: all three in turn, or the vertex two Xs share
+    xs = c.p["tris"][np.isin(c.p["tri"], c.x)]
+    on_vertex = (c.rays["origin"][:, None, None, :].view(np.uint32) == xs[None].view(np.uint32)).all(axis=3)
+    assert on_vertex.any(axis=(1, 2)).all() and (on_vertex.any(axis=(0, 1)).sum() == 3 or len(c.x) == 2)
+    same, differ = c.same_triangle(), c.bits_differ()
+    assert same.sum() > len(c.rays) // 2
+    if c.control:
+        slot = int(np.nonzero(c.p["tri"] == c.x[0])[0][0])
+        assert slot // 4 == c.n // 4 and c.n % 4                    # X really is in the padded group
+        assert (c.p["tri"] != c.q["tri"]).any()
+        assert same.all() or (same == c.p["hit_mask"].astype(bool)).all()
+        assert not differ.any() and (c.p["hit_mask"] == c.q["hit_mask"]).all()
+    else:
+        for x in c.x:
+            slot = int(np.nonzero(c.p["tri"] == x)[0][0])
+            assert slot // 4 < c.n // 4                              # X is in a full group of P ...
+            qslot = int(np.nonzero(c.q["tri"] == x)[0][0])
+            mates = set(c.p["tri"][4 * (slot // 4):4 * (slot // 4) + 4]) - {x}
+            assert not mates & set(c.q["tri"][4 * (qslot // 4):4 * (qslot // 4) + 4])      # ... and has other company in Q
+        assert differ.sum() >= GROUP_REDO_MIN_SHARE * same.sum(), (int(differ.sum()), int(same.sum()))
+
+
+def test_group_redo_fixture_covers_what_it_says(golden_dir):
+    """Leaf sizes 4, 5, 8, 11, 12, 63; X in slot 0 and slot 3 of the first full group, in a middle group, in the last full group and
+    in the padded group; two Xs in two full groups of one leaf; X in a mesh of its own."""
+    from tests.util import group_redo_cases
+    cases = group_redo_cases(golden_dir)
+    where = {}
+    for c in cases:
+        if len(c.x) == 1 and not c.p["mesh"].any():
+            slot = int(np.nonzero(c.p["tri"] == c.x[0])[0][0])
+            full = c.n // 4
+            kind = "padded" if slot // 4 == full else ("slot%d" % slot if slot in (0, 3) else ("last" if slot // 4 == full - 1 else "middle"))
+            where.setdefault(c.n, set()).add(kind)
+    assert where == {4: {"slot0", "slot3"}, 5: {"slot0", "slot3", "padded"}, 8: {"slot0", "slot3", "last"},
+                     11: {"slot0", "slot3", "last", "padded"}, 12: {"slot0", "slot3", "middle", "last"},
+                     63: {"slot0", "slot3", "middle", "last", "padded"}}
+    two = [c for c in cases if len(c.x) == 2]
+    assert len(two) == 1
+    g = [int(np.nonzero(two[0].p["tri"] == x)[0][0]) // 4 for x in two[0].x]
+    assert g[0] != g[1] and max(g) < two[0].n // 4
+    own = [c for c in cases if c.p["mesh"].any()]
+    assert len(own) == 1 and (own[0].p["mesh"] == (own[0].p["tri"] == own[0].x[0])).all()

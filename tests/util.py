@@ -47,6 +47,48 @@ def compare_hits_struct(hits, mask, g, what=""):
                         g["hit_mask"], g["hit_mesh"], g["hit_tri"], g["hit_t"], g["hit_u"], g["hit_v"], what)
 
 
+class GroupRedoCase:
+    """One case of tests/golden/group_redo.npz (oracle/gen_golden.py, gen_group_redo): a single leaf in two orders, P and Q, rays
+    that start on a vertex of the leaf's zero-triangle X, and what the REAL rtk.c returned for them on either order.
+    p / q: dicts with the leaf in slot order (tris, tri, mesh) and the answers (hit_mask, hit_mesh, hit_tri, hit_t, hit_u, hit_v)."""
+
+    def __init__(self, g, name, control):
+        from rtk_amd.types import RAY_DTYPE
+        self.name, self.control = name, bool(control)
+        self.rays = np.ascontiguousarray(g[name + "_rays"]).view(RAY_DTYPE).reshape(-1)
+        self.x = g[name + "_x"]
+        self.p, self.q = ({k: g["%s_%s_%s" % (name, tag, k)] for k in ("tris", "tri", "mesh", "hit_mask", "hit_mesh", "hit_tri", "hit_t", "hit_u", "hit_v")}
+                          for tag in ("p", "q"))
+        self.n = len(self.p["tri"])
+
+    def blob(self, oracle, order="p"):
+        o = self.p if order == "p" else self.q
+        blobs = oracle.leaf_chain_blobs(o["tris"], o["mesh"], o["tri"], chunk=63)
+        assert len(blobs) == 1
+        return blobs[0]
+
+    def same_triangle(self):
+        """rays that hit the same triangle on P and on Q"""
+        return self.p["hit_mask"].astype(bool) & self.q["hit_mask"].astype(bool) & (self.p["hit_tri"] == self.q["hit_tri"]) & (self.p["hit_mesh"] == self.q["hit_mesh"])
+
+    def bits_differ(self):
+        """of those, the rays whose t, u or v differ in their bits between P and Q: the rays on which an answer equal to P's shows
+        that X's group, and no other, took the double-precision edge functions"""
+        d = np.zeros(len(self.rays), bool)
+        for k in ("hit_t", "hit_u", "hit_v"):
+            d |= self.p[k].view(np.uint32) != self.q[k].view(np.uint32)
+        return d & self.same_triangle()
+
+
+def group_redo_cases(golden_dir):
+    g = load_golden(golden_dir, "group_redo.npz")
+    return [GroupRedoCase(g, str(n), c) for n, c in zip(g["cases"], g["control"])]
+
+
+# the least share of the rays that hit one triangle on P and on Q whose t, u, v bits must differ where X is in a full group
+GROUP_REDO_MIN_SHARE = 0.25
+
+
 def random_mixed_scene(seed):
     """A random scene of several meshes with mixed index types (implicit, u16, u32), float32 / float64 positions, strided
     buffers and callback meshes (<= 128 triangles per call, rtk.c:1141-1148). Returns (scene_desc, keepalive, tris[n,3,3],
