@@ -510,6 +510,60 @@ int rtk_dev_closest_points_counted(const rtk_dev_scene *ds, const rtk_point_quer
 /* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
 uint32_t rtk_amd_closest_stack_entries(void);
 
+/* ---- Every hit along a ray: how many triangles a ray crosses, and all of them (or the k closest) in one walk ----
+ * What transparency and alpha compositing, thickness and x-ray depth, visibility through several occluders and point-in-mesh by
+ * crossing parity ask. Until now the only route was the d_after loop of rtk_dev_trace_rays_filtered: one complete closest-hit
+ * walk per candidate per ray and a read-back per round.
+ *
+ * THE RULE. A CANDIDATE of a ray is a triangle that
+ *   - lies in a leaf that the walk enters,
+ *   - rtk's watertight test accepts: !(neg && pos) && t > min_t && t < max_t, with rtk's operation order and rtk's group-of-four
+ *     double-precision rule (rtk.c:302-336): a partial last group of a leaf is always evaluated in double; a full group is
+ *     scanned for an exactly-zero edge function first and then evaluated, in double if it has one (what is counted or written
+ *     is never undone),
+ *   - and every filter that is set lets through: d_mesh_mask, d_ignore_prim and d_after mean exactly what they mean in
+ *     rtk_dev_trace_rays_filtered (d_after makes paging possible: the candidates after a given (t, prim)).
+ * The walk ENTERS a child if its slot is not empty and the slab test of the exact 128-byte node passes WITH THE FAR BOUND FIXED
+ * AT THE RAY'S max_t: (plane - origin) * (1 / direction) per axis, near and far plane picked by the direction's sign bit,
+ * max(near.., min_t) <= min(far.., max_t), the arithmetic of the closest-hit kernels' exact-node branch (for a ray whose
+ * products can be NaN, with the reference's SSE operand order of min and max). The candidate set is therefore a FUNCTION OF THE
+ * SCENE'S BITS AND THE RAY: it does not depend on the order of the walk, and it is exactly what a rtk_filter_fn that rejects
+ * everything is offered, once each, by the reference's traversal (the oracle's ora_trace_rays_filter) on the exported blob.
+ * ONLY THE EXACT NODES are used, never the 64-byte compressed ones: those admit a superset of boxes, and the set would depend
+ * on the node format. RTK_TRACE_EXACT_NODES is implied.
+ *
+ * rtk_dev_trace_rays_count: d_counts[i] = the number of candidates of ray i, written for EVERY ray (0 for a ray without any);
+ *   nothing else is written.
+ * rtk_dev_trace_rays_all: ray i owns d_records[d_offsets[i] .. d_offsets[i + 1]); d_offsets has n + 1 entries, non-decreasing;
+ *   r = d_offsets[i + 1] - d_offsets[i] is its room and may be 0. Written are the min(count_i, r) CLOSEST candidates in ascending
+ *   (t, prim) order, each the rtk_hit_record the closest-hit call would write for that triangle (t, u * rcp, v * rcp, global
+ *   prim); d_written[i] (d_written may be NULL) is that number. Entries of the segment beyond it ARE NOT WRITTEN, entries
+ *   outside every segment are not written. The far bound of the walk stays at max_t also when a segment is full (a shrunk
+ *   bound would let the rounding of a box's entry distance against a triangle's t decide which of two near-equal candidates is
+ *   kept): the kept records are EXACTLY the first min(count_i, r) of the ray's full list. So one call serves two uses:
+ *     every hit      count, an inclusive prefix sum into uint64 offsets on the same stream (torch.cumsum into an int64 tensor is
+ *                    one as it stands, like rtk_ray_list.d_ids), then fill;
+ *     the k closest  d_offsets[i] = i * k, no count pass.
+ * DETERMINISTIC: the same inputs give the same bytes.
+ * Both calls are asynchronous on `stream`, need no host wait and read nothing back. The scene is only read, as it stands: built,
+ * uploaded, refitted, split or rebuilt, and rtk_mgpu_scene(m, i) as it is. They use the per-(scene, stream) scratch set like
+ * every other launch (queue heads; the part of the walk's stack that does not fit on chip), so the thread-safety rules of the
+ * batches hold unchanged; a dropped push (impossible for a tree) is reported by rtk_dev_trace_status.
+ * `opts` may be NULL; blocks_per_cu, refill_min and node_exit apply; image hints, RTK_TRACE_SORT_RAYS and every other flag are
+ * IGNORED: there is no packet form. `filter` may be NULL.
+ * Refused before anything is launched and before any HIP call, RTK_AMD_ERR_BAD_ARG: a NULL scene; NULL d_rays or d_counts, NULL
+ * d_offsets or d_records with n != 0; a filter whose struct_size is too small (or a mesh mask without mesh_mask_bits);
+ * n >= 2^32. The scene and device refusals are those of rtk_dev_trace_rays. n == 0 is RTK_AMD_OK with nothing launched.
+ * Offsets that run past the caller's buffer are the caller's error and, like a listed trace's ids, are NOT CHECKED (records
+ * are written out of range); a ray whose offsets decrease has no room and nothing is written for it. */
+int rtk_dev_trace_rays_count(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
+	uint32_t *d_counts, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream);
+int rtk_dev_trace_rays_all(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
+	const uint64_t *d_offsets, rtk_hit_record *d_records, uint32_t *d_written /* may be NULL */,
+	const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream);
+/* (4-byte stack entries per lane the walk keeps on chip before it uses the spill area, for tests) */
+uint32_t rtk_amd_allhits_stack_entries(void);
+
 /* Waits for `stream` and reports whether a launch of this scene on it overflowed a traversal stack
  * (RTK_AMD_ERR_BAD_SCENE; impossible for a validated tree -- the push is dropped, never written out of bounds). */
 int rtk_dev_trace_status(const rtk_dev_scene *ds, void *stream);

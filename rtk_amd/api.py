@@ -156,7 +156,8 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_mgpu_build_placed", "rtk_mgpu_refit_placed", "rtk_mgpu_refit_meshes_placed",
                      "rtk_dev_trace_rays_listed", "rtk_dev_trace_rays_any_listed", "rtk_dev_select_rays",
                      "rtk_amd_select_block_items", "rtk_amd_select_scan_items",
-                     "rtk_dev_closest_points", "rtk_dev_closest_points_counted", "rtk_amd_closest_stack_entries"]
+                     "rtk_dev_closest_points", "rtk_dev_closest_points_counted", "rtk_amd_closest_stack_entries",
+                     "rtk_dev_trace_rays_count", "rtk_dev_trace_rays_all", "rtk_amd_allhits_stack_entries"]
 
 _lib = None
 
@@ -225,6 +226,12 @@ def lib():
     L.rtk_dev_closest_points_counted.restype = C.c_int
     L.rtk_amd_closest_stack_entries.argtypes = []
     L.rtk_amd_closest_stack_entries.restype = C.c_uint32
+    L.rtk_dev_trace_rays_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(DevFilter), C.POINTER(TraceOpts), C.c_void_p]
+    L.rtk_dev_trace_rays_count.restype = C.c_int
+    L.rtk_dev_trace_rays_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter), C.POINTER(TraceOpts), C.c_void_p]
+    L.rtk_dev_trace_rays_all.restype = C.c_int
+    L.rtk_amd_allhits_stack_entries.argtypes = []
+    L.rtk_amd_allhits_stack_entries.restype = C.c_uint32
     L.rtk_trace_rays_filter.restype = C.c_size_t
     L.rtk_trace_rays_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rtk_amd_shard_range.restype = None
@@ -631,6 +638,117 @@ class DeviceScene:
         d_rec, d_pts = self.closest_points_device(to_device(q), n)
         _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
         return d_rec.cpu().numpy().view(CLOSEST_RECORD_DTYPE), d_pts.cpu().numpy().view(np.float32).reshape(n, 3)
+
+    # -- every hit along a ray (rtk_dev_trace_rays_count / rtk_dev_trace_rays_all): asynchronous on the current stream --
+
+    def count_hits_device(self, d_rays, n, d_counts=None, filter=None, opts=None):
+        """The number of candidates of each of n rays (include/rtk_amd.h, "Every hit along a ray"): a cuda tensor of n uint32
+        words (d_counts: any cuda tensor of at least 4 n bytes; None: a new int32 tensor). Nothing waits for the stream."""
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        _check(lib().rtk_dev_trace_rays_count(self.handle, C.c_void_p(d_rays.data_ptr()), n, C.c_void_p(d_counts.data_ptr()),
+                                              C.byref(filter) if filter is not None else None, C.byref(opts) if opts is not None else None,
+                                              _stream_ptr()), "rtk_dev_trace_rays_count")
+        return d_counts
+
+    def trace_all_device(self, d_rays, n, d_offsets, d_records, d_written=None, filter=None, opts=None):
+        """Ray i's closest candidates, in (t, prim) order, into records d_offsets[i] .. d_offsets[i + 1] of d_records (16-byte
+        HIT_RECORD_DTYPE records): as many as the ray has or the segment holds. d_offsets: a cuda int64 tensor of n + 1 entries,
+        non-decreasing; d_written: None (a new int32 tensor of n entries) or a cuda tensor of 4 n bytes. Records beyond
+        written[i], and outside every segment, are not written. Returns d_written. Nothing waits for the stream."""
+        torch = _torch()
+        if d_written is None:
+            d_written = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        _check(lib().rtk_dev_trace_rays_all(self.handle, C.c_void_p(d_rays.data_ptr()), n, C.c_void_p(d_offsets.data_ptr()),
+                                            C.c_void_p(d_records.data_ptr()), C.c_void_p(d_written.data_ptr()),
+                                            C.byref(filter) if filter is not None else None, C.byref(opts) if opts is not None else None,
+                                            _stream_ptr()), "rtk_dev_trace_rays_all")
+        return d_written
+
+    def _device_filter(self, n, mesh_mask, ignore_prim, after):
+        """(DevFilter or None, the tensors it points into) for the numpy filters of trace_filtered"""
+        if mesh_mask is None and ignore_prim is None and after is None:
+            return None, []
+        f = DevFilter()
+        f.struct_size = C.sizeof(DevFilter)
+        keep = []
+        if mesh_mask is not None:
+            bits = np.asarray(mesh_mask, bool)
+            words = np.zeros((len(bits) + 31) // 32, np.uint32)
+            for m, b in enumerate(bits):
+                if b:
+                    words[m >> 5] |= np.uint32(1 << (m & 31))
+            d = to_device(words); keep.append(d)
+            f.d_mesh_mask, f.mesh_mask_bits = d.data_ptr(), len(bits)
+        if ignore_prim is not None:
+            a = np.ascontiguousarray(ignore_prim, np.uint32)
+            assert a.shape[0] == n
+            d = to_device(a); keep.append(d)
+            f.d_ignore_prim = d.data_ptr()
+        if after is not None:
+            a = np.ascontiguousarray(after)
+            assert a.dtype == HIT_RECORD_DTYPE and a.shape[0] == n
+            d = to_device(a); keep.append(d)
+            f.d_after = d.data_ptr()
+        return f, keep
+
+    def count_hits(self, rays, mesh_mask=None, ignore_prim=None, after=None, opts=None):
+        """rays: numpy RAY_DTYPE; filters as for trace_filtered. Returns the candidates per ray, uint32[n]."""
+        rays = np.ascontiguousarray(rays)
+        assert rays.dtype == RAY_DTYPE
+        n = rays.shape[0]
+        if n == 0:
+            return np.zeros(0, np.uint32)
+        f, _keep = self._device_filter(n, mesh_mask, ignore_prim, after)
+        d_counts = self.count_hits_device(to_device(rays), n, filter=f, opts=opts)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return d_counts.cpu().numpy().view(np.uint32)
+
+    def trace_all(self, rays, mesh_mask=None, ignore_prim=None, after=None, max_per_ray=None):
+        """Every candidate of every ray, or with max_per_ray=k the k closest. rays: numpy RAY_DTYPE; filters as for
+        trace_filtered. Returns (offsets int64[n + 1], records HIT_RECORD_DTYPE[offsets[n]], written uint32[n]): ray i's records
+        are records[offsets[i] : offsets[i] + written[i]], ascending in (t, prim). Without max_per_ray: a count, its prefix sum on
+        the device and the fill, enqueued without a host wait in between (only the size of the record buffer is read back,
+        to allocate it), and written[i] == offsets[i + 1] - offsets[i]. With it: offsets[i] = i * k, no count, and the records
+        of a segment beyond written[i] are zero."""
+        torch = _torch()
+        rays = np.ascontiguousarray(rays)
+        assert rays.dtype == RAY_DTYPE
+        n = rays.shape[0]
+        if n == 0:
+            return np.zeros(1, np.int64), np.zeros(0, HIT_RECORD_DTYPE), np.zeros(0, np.uint32)
+        d_rays = to_device(rays)
+        f, _keep = self._device_filter(n, mesh_mask, ignore_prim, after)
+        if max_per_ray is None:
+            d_counts = self.count_hits_device(d_rays, n, filter=f)
+            d_offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+            d_offsets[1:] = torch.cumsum(d_counts, 0, dtype=torch.int64)
+            total = int(d_offsets[n].item())                 # (the one read-back: how many records to allocate)
+        else:
+            k = int(max_per_ray)
+            if k < 0:
+                raise RtkError("trace_all: max_per_ray %r" % (max_per_ray,))
+            d_offsets = torch.arange(n + 1, dtype=torch.int64, device="cuda") * k
+            total = n * k
+        d_records = torch.zeros(max(total, 1) * 16, dtype=torch.uint8, device="cuda")
+        d_written = self.trace_all_device(d_rays, n, d_offsets, d_records, filter=f)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return (d_offsets.cpu().numpy(), d_records.cpu().numpy().view(HIT_RECORD_DTYPE)[:total], d_written.cpu().numpy().view(np.uint32))
+
+    def contains(self, points, direction=(0.5458, 0.3207, 0.7743)):
+        """Is each point inside the mesh? The parity (odd = inside) of count_hits for the rays from the points along `direction`
+        with min_t = 0 and max_t = RTK_INF. points: array-like (n, 3) float32; returns bool[n]. MEANINGFUL FOR CLOSED MESHES
+        ONLY (every ray that enters must leave). UNDEFINED for a point on the surface and for a ray that passes through an edge
+        or a vertex: rtk's watertight test accepts an exactly-zero edge function on BOTH sides of a shared edge, so such a
+        crossing counts twice (the default direction is generic on purpose: no component ratio is a small fraction)."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        rays = np.zeros(pts.shape[0], RAY_DTYPE)
+        rays["origin"] = pts
+        rays["direction"] = np.asarray(direction, np.float32)
+        rays["min_t"] = 0.0
+        rays["max_t"] = RTK_INF
+        return (self.count_hits(rays) & 1).astype(bool)
 
     def expand_device(self, d_records, n):
         torch = _torch()

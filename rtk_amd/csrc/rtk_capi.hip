@@ -198,6 +198,18 @@ extern "C" int rtk_dev_closest_points_counted(const rtk_dev_scene *ds, const rtk
 	return rtk_launch_closest(ds, d_queries, num_queries, nullptr, d_records, d_points, nullptr, out);
 }
 
+extern "C" int rtk_dev_trace_rays_count(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
+	uint32_t *d_counts, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream)
+{
+	return rtk_launch_allhits(ds, d_rays, n, d_counts, nullptr, nullptr, nullptr, false, filter, opts, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_trace_rays_all(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
+	const uint64_t *d_offsets, rtk_hit_record *d_records, uint32_t *d_written, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream)
+{
+	return rtk_launch_allhits(ds, d_rays, n, nullptr, d_offsets, d_records, d_written, true, filter, opts, (hipStream_t)stream);
+}
+
 extern "C" int rtk_dev_trace_rays_counted(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
 	rtk_hit_record *d_hits, const rtk_trace_opts *opts, rtk_trace_counters *out)
 {

@@ -322,6 +322,10 @@ unsigned long long *rtk_error_word(rtk_dev_scene *ds, hipStream_t stream);
 int rtk_debug_packet_entries(const rtk_dev_scene *ds, const rtk_ray *d_rays, uint32_t image_w, uint32_t image_h, uint32_t target, uint32_t max_levels, void *host_out);
 int rtk_trace_status(const rtk_dev_scene *ds, hipStream_t stream);
 void rtk_scene_drop_stream(rtk_dev_scene *ds, hipStream_t stream);   // the stream is about to be destroyed (and has been synchronised)
+// -- rtk_dev_trace_rays_count / rtk_dev_trace_rays_all (rtk_launch.hip; the kernel: rtk_allhits.hip) --
+// counts: the count form; else the fill form (offsets, records, written or NULL)
+int rtk_launch_allhits(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, uint32_t *d_counts, const uint64_t *d_offsets,
+	rtk_hit_record *d_records, uint32_t *d_written, bool fill, const rtk_dev_filter *filter, const rtk_trace_opts *opts, hipStream_t stream);
 // -- rtk_dev_select_rays (rtk_select.hip) --
 int rtk_launch_select(rtk_dev_scene *ds, const void *d_src, uint32_t kind, size_t num_rays, const rtk_ray_list *in, uint64_t *d_out_ids,
 	uint64_t *d_out_count, hipStream_t stream);

@@ -382,6 +382,76 @@ int rtk_launch_trace(const rtk_dev_scene *ds_c, const TraceCall &c)
 	return RTK_AMD_OK;
 }
 
+// rtk_dev_trace_rays_count / rtk_dev_trace_rays_all: every candidate of a ray (rtk_allhits.hip). No plan: one kernel family on the
+// exact nodes, no packets, no reordering; of the options blocks_per_cu, refill_min and node_exit apply.
+int rtk_launch_allhits(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, size_t n, uint32_t *d_counts, const uint64_t *d_offsets,
+	rtk_hit_record *d_records, uint32_t *d_written, bool fill, const rtk_dev_filter *filter, const rtk_trace_opts *opts, hipStream_t stream)
+{
+	rtk_dev_scene *ds = const_cast<rtk_dev_scene *>(ds_c);
+	const char *const who = fill ? "rtk_dev_trace_rays_all" : "rtk_dev_trace_rays_count";
+	// everything the host can see is refused here, before any HIP call
+	if (!ds) { rtk_set_error("%s: NULL scene", who); return RTK_AMD_ERR_BAD_ARG; }
+	if (n && (!d_rays || (fill ? (!d_offsets || !d_records) : !d_counts))) { rtk_set_error("%s: NULL rays or output", who); return RTK_AMD_ERR_BAD_ARG; }
+	if (filter && filter->struct_size < sizeof(rtk_dev_filter)) { rtk_set_error("%s: rtk_dev_filter.struct_size is too small", who); return RTK_AMD_ERR_BAD_ARG; }
+	if (filter && filter->d_mesh_mask && filter->mesh_mask_bits == 0) { rtk_set_error("%s: mesh mask without mesh_mask_bits", who); return RTK_AMD_ERR_BAD_ARG; }
+	if (n >= ((size_t)1 << 32)) { rtk_set_error("%s: %zu rays: a batch holds fewer than 2^32", who, n); return RTK_AMD_ERR_BAD_ARG; }
+	if (n == 0) return RTK_AMD_OK;
+	if (!rtk_on_scene_device(ds, who)) return RTK_AMD_ERR_BAD_ARG;
+
+	AllHitsParams p = {};
+	p.rays = d_rays;
+	p.n = (uint32_t)n;
+	p.counts = d_counts;
+	p.offsets = reinterpret_cast<const unsigned long long *>(d_offsets);
+	p.records = d_records;
+	p.written = d_written;
+	bool filtered = false;
+	if (filter) {
+		p.mesh_mask = filter->d_mesh_mask;
+		p.mesh_mask_bits = filter->mesh_mask_bits;
+		p.ignore_prim = filter->d_ignore_prim;
+		p.after = filter->d_after;
+		filtered = filter->d_mesh_mask || filter->d_ignore_prim || filter->d_after;
+	}
+	const int form = (fill ? 1 : 0) | (filtered ? 2 : 0);
+	const TraceOpts o = decode_opts(opts);
+	p.refill_min = o.refill_min ? o.refill_min : 8u;
+	p.node_exit = o.node_exit ? o.node_exit : 32u;
+	// a batch that fits one workgroup needs no work queue (and no counter reset)
+	p.dynamic = n > TRACE_BLOCK_THREADS ? 1u : 0u;
+	const uint32_t occ = (uint32_t)rtk_allhits_occupancy(ds->device, form);
+	const uint32_t blocks_per_cu = (o.blocks_per_cu == 0 || o.blocks_per_cu > occ) ? occ : o.blocks_per_cu;
+	const size_t blocks_needed = (n + TRACE_BLOCK_THREADS - 1) / TRACE_BLOCK_THREADS;
+	const size_t grid = std::min<size_t>(blocks_needed, (size_t)(ds->num_cus > 0 ? ds->num_cus : 1) * blocks_per_cu);
+
+	// the scratch set of (scene, stream), held until the launch is enqueued; the view and the tree record are read under the
+	// same lock a rebuild replaces them under
+	std::lock_guard<std::mutex> lock(ds->scratch_mutex);
+	if (!rtk_within_4gib(ds->view)) {
+		rtk_set_error("%s: scene exceeds 4 GiB of nodes or triangles (%u nodes, %u triangles)", who, ds->view.num_nodes, ds->view.num_tris);
+		return RTK_AMD_ERR_UNSUPPORTED;
+	}
+	p.nodes = ds->view.nodes; p.tris = ds->view.tris;
+	p.num_nodes = ds->view.num_tris != 0u ? ds->view.num_nodes : 0u;
+	const size_t entries = ds->tree.stack_entries();
+	const size_t spill_cap = entries > AH_LDS_STACK ? entries - AH_LDS_STACK : 0;
+	LaunchScratch *sc = ds->scratch.get(stream);
+	if (!sc) return RTK_AMD_ERR_OOM;
+	if (spill_cap) {
+		// (the area is shared with the kernels whose entries are 8 bytes, and remembered in their unit: two of this walk's entries each)
+		const int rc = sc->grow_spill(grid * TRACE_BLOCK_THREADS, (spill_cap + 1u) / 2u, sizeof(uint2));
+		if (rc != RTK_AMD_OK) return rc;
+	}
+	p.spill = sc->spill.as<uint32_t>();
+	p.spill_stride = (uint32_t)(spill_cap ? sc->spill.capacity : 0);
+	p.spill_cap = (uint32_t)spill_cap;
+	p.counter = sc->d_counter;
+	if (p.dynamic) RTK_HIP_CHECK(hipMemsetAsync(sc->d_counter, 0, RTK_COUNTER_WORDS * sizeof(unsigned long long), stream), RTK_AMD_ERR_HIP);
+	rtk_allhits_kernel_launch(form, p, (unsigned)grid, stream);
+	RTK_HIP_CHECK(hipGetLastError(), RTK_AMD_ERR_HIP);
+	return RTK_AMD_OK;
+}
+
 // rtk_dev_debug_packet_entries: the pre-pass of an image frame alone, on the null stream's scratch set, and its lists copied to the host
 int rtk_debug_packet_entries(const rtk_dev_scene *ds_c, const rtk_ray *d_rays, uint32_t image_w, uint32_t image_h, uint32_t target, uint32_t max_levels, void *host_out)
 {

@@ -113,6 +113,30 @@ struct LnHotListedParams {
 };
 static_assert(sizeof(LnHotListedParams) == 96 && offsetof(LnHotListedParams, count) == 88, "rtk_lane_hot.S reads this layout");
 
+// Kernel argument of rtk_allhits_kernel (rtk_allhits.hip): every candidate of a ray, counted or written to the ray's segment
+#define AH_LDS_STACK 30u           // 4-byte stack entries per lane held in LDS: 30 KB per workgroup, five workgroups share a CU's 160 KB
+struct AllHitsParams {
+	const DevNode *nodes;
+	const DevTri *tris;
+	uint32_t num_nodes;
+	uint32_t n;                    // rays, below 2^32
+	const rtk_ray *rays;
+	uint32_t *counts;              // count form: one word per ray
+	const unsigned long long *offsets;   // fill form: n + 1 entries; ray i owns records[offsets[i] .. offsets[i + 1])
+	rtk_hit_record *records;
+	uint32_t *written;             // fill form, optional: records kept per ray
+	unsigned long long *counter;   // the stream's counter words: queue heads, [RTK_ERROR_WORD] is set by a dropped push
+	uint32_t *spill;               // stack entries beyond a lane's LDS column: [entry][lane of the launch]
+	uint32_t spill_stride;         // lanes
+	uint32_t spill_cap;            // entries per lane
+	uint32_t refill_min, node_exit, dynamic;
+	// built-in candidate filters (rtk_dev_filter, FILT forms only); all optional
+	uint32_t mesh_mask_bits;
+	const uint32_t *mesh_mask;
+	const uint32_t *ignore_prim;
+	const rtk_hit_record *after;
+};
+
 // DevTri.flags: bit 0 = last triangle of its leaf, bits 8.. = mesh index (for the mesh-mask filter)
 #define RTK_TRI_MESH_SHIFT 8
 
@@ -159,6 +183,9 @@ inline bool rtk_within_4gib(const DevSceneView &v)
 // rtk_trace.hip: rtk_trace_kernel's variant (rtk_trace_plan.h). The occupancy query also answers for the C++ packet kernel's variants; cached per device
 int rtk_trace_occupancy(int device, int variant);
 void rtk_trace_kernel_launch(int variant, const TraceParams &p, unsigned blocks, hipStream_t stream);
+// rtk_allhits.hip: rtk_allhits_kernel's form (fill | filtered << 1); resident workgroups per CU, cached per device
+int rtk_allhits_occupancy(int device, int form);
+void rtk_allhits_kernel_launch(int form, const AllHitsParams &p, unsigned blocks, hipStream_t stream);
 // rtk_ray_sort.hip: the ray-reordering pre-pass; sc->sort holds rtk_ray_sort_bytes(n) for a capacity of n rays
 size_t rtk_ray_sort_bytes(size_t n);
 int rtk_ray_sort_launch(const rtk_dev_scene *ds, LaunchScratch *sc, const rtk_ray *d_rays, size_t n, const TraceKnobs &knobs, hipStream_t stream, const unsigned long long **perm);
