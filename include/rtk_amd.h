@@ -510,6 +510,63 @@ int rtk_dev_closest_points_counted(const rtk_dev_scene *ds, const rtk_point_quer
 /* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
 uint32_t rtk_amd_closest_stack_entries(void);
 
+/* ---- Triangles within a distance: how many triangles lie within r of a point, and all of them (or the k nearest) ----
+ * The question asked in the same breath as "which triangle is nearest": contact generation needs every triangle a sphere
+ * touches, robust normals and ICP with outlier rejection the k nearest, photon and sample gathering a radius query. Closest
+ * points has no "after": one call per answer cannot even be written. These calls are to closest points what "Every hit along
+ * a ray" is to the closest-hit trace, and they read the scene the same way: as it stands, changing no bit of it.
+ *
+ * THE RULE (rtk_amd/csrc/rtk_within_rule.h on top of rtk_closest_rule.h; INTEGRATION.md "Triangles within a distance"). dist2,
+ * u, v and the point q of a triangle are those of closest points, bit for bit. A triangle is a CANDIDATE of the query
+ * (p, max_dist2) iff dist2 < max_dist2 -- strictly; a NaN dist2 is never one. A query whose max_dist2 is NaN, zero or negative,
+ * or that has a non-finite coordinate, has no candidates; neither has any query of a scene without triangles; RTK_INF means no
+ * limit. The LIST of a query is its candidates in ascending (dist2, prim) order, THE LOWEST PRIMITIVE ID FIRST AMONG EQUAL dist2;
+ * its first entry is word for word what rtk_dev_closest_points writes for the query. THE RESULT DOES NOT DEPEND ON THE TREE OR
+ * ON THE ORDER OF THE WALK: a subtree is left out only if the bound b of its box has b >= max_dist2, or if the query's segment
+ * is full and b > worst.dist2 (the last kept entry; strictly, an equal bound can hide a lower id), and the box bound never
+ * exceeds the dist2 of a triangle inside the box, without a margin. Only the exact 128-byte nodes are used.
+ *
+ * rtk_dev_triangles_within_count: d_counts[i] = the number of candidates of query i, written for EVERY answered query (0 for a
+ *   query without any); nothing else is written.
+ * rtk_dev_triangles_within_all: query i owns d_records[d_offsets[i] .. d_offsets[i + 1]), and d_points[3 j ..] (d_points may be
+ *   NULL) belongs to record j; d_offsets has num_queries + 1 entries, indexed by query slot; r = d_offsets[i + 1] - d_offsets[i]
+ *   is its room and may be 0. Written are the first min(count_i, r) entries of the query's list, each the rtk_closest_record and
+ *   the point closest points would write for that triangle; d_written[i] (d_written may be NULL) is that number. Entries of the
+ *   segment beyond it ARE NOT WRITTEN, entries outside every segment are not written. A query whose offsets decrease has no
+ *   room and nothing is written for it (d_written[i] = 0). One call serves two uses:
+ *     every triangle within r   count, an inclusive prefix sum into uint64 offsets on the same stream (torch.cumsum into an int64
+ *                               tensor is one as it stands), then fill;
+ *     the k nearest             d_offsets[i] = i * k, no count pass; max_dist2 = RTK_INF if there is no limit. The walk is culled
+ *                               by the k-th best distance so far, as closest points culls by the best.
+ * `list` may be NULL: all num_queries queries are answered. Otherwise the words of closest points hold: m = min(*d_count,
+ * num_queries) entries are answered, the results of query r go to slot r of d_counts / d_written and to segment r, A SLOT THAT
+ * IS NOT LISTED IS NOT WRITTEN, an id may repeat (the query is answered once), the count is read when the work reaches it on
+ * `stream`, and an id >= num_queries is the caller's error.
+ * DETERMINISTIC: the same inputs give the same bytes. Asynchronous on `stream`: no host wait, nothing read back. The scene is
+ * only read, as it stands: built, uploaded, refitted, split or rebuilt, and rtk_mgpu_scene(m, i) as it is; the thread-safety
+ * rules of the batches hold. The part of the walk's stack that does not fit on chip (and one bit per query for a list with ids)
+ * lives in the per-(scene, stream) scratch set, and a dropped push (impossible for a tree) is reported by rtk_dev_trace_status
+ * like a trace's. Nothing they allocate counts toward the scene.
+ * Refused before anything is launched and before any HIP call, RTK_AMD_ERR_BAD_ARG, with a message that names the function: a
+ * NULL scene; NULL d_queries or d_counts, NULL d_offsets or d_records with num_queries != 0; a bad list (as for the listed
+ * traces); num_queries >= 2^32; a calling thread whose current device is not the scene's. num_queries == 0 is RTK_AMD_OK with
+ * nothing launched. Offsets that run past the caller's buffer are the caller's error and are NOT CHECKED.
+ * A scene with non-finite vertex coordinates: the calls terminate and write only inside their outputs; NOTHING ELSE IS PROMISED
+ * about their results. */
+int rtk_dev_triangles_within_count(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries,
+	const rtk_ray_list *list, uint32_t *d_counts, void *stream);
+int rtk_dev_triangles_within_all(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries,
+	const rtk_ray_list *list, const uint64_t *d_offsets, rtk_closest_record *d_records, float *d_points /* may be NULL */,
+	uint32_t *d_written /* may be NULL */, void *stream);
+/* The same results without a list, plus visit counts in the fields of rtk_dev_closest_points_counted (hits = queries with at least
+ * one candidate counted or kept). d_offsets == NULL: the count form, d_counts_or_written receives the counts (required);
+ * otherwise the fill form, d_points and d_counts_or_written may be NULL. Null stream, synchronous; not for timing. */
+int rtk_dev_triangles_within_counted(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries,
+	const uint64_t *d_offsets, rtk_closest_record *d_records, float *d_points, uint32_t *d_counts_or_written,
+	rtk_trace_counters *out);
+/* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
+uint32_t rtk_amd_within_stack_entries(void);
+
 /* ---- Every hit along a ray: how many triangles a ray crosses, and all of them (or the k closest) in one walk ----
  * What transparency and alpha compositing, thickness and x-ray depth, visibility through several occluders and point-in-mesh by
  * crossing parity ask. Until now the only route was the d_after loop of rtk_dev_trace_rays_filtered: one complete closest-hit

@@ -157,7 +157,9 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_dev_trace_rays_listed", "rtk_dev_trace_rays_any_listed", "rtk_dev_select_rays",
                      "rtk_amd_select_block_items", "rtk_amd_select_scan_items",
                      "rtk_dev_closest_points", "rtk_dev_closest_points_counted", "rtk_amd_closest_stack_entries",
-                     "rtk_dev_trace_rays_count", "rtk_dev_trace_rays_all", "rtk_amd_allhits_stack_entries"]
+                     "rtk_dev_trace_rays_count", "rtk_dev_trace_rays_all", "rtk_amd_allhits_stack_entries",
+                     "rtk_dev_triangles_within_count", "rtk_dev_triangles_within_all", "rtk_dev_triangles_within_counted",
+                     "rtk_amd_within_stack_entries"]
 
 _lib = None
 
@@ -226,6 +228,16 @@ def lib():
     L.rtk_dev_closest_points_counted.restype = C.c_int
     L.rtk_amd_closest_stack_entries.argtypes = []
     L.rtk_amd_closest_stack_entries.restype = C.c_uint32
+    L.rtk_dev_triangles_within_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p]
+    L.rtk_dev_triangles_within_count.restype = C.c_int
+    L.rtk_dev_triangles_within_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]
+    L.rtk_dev_triangles_within_all.restype = C.c_int
+    L.rtk_dev_triangles_within_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(TraceCounters)]
+    L.rtk_dev_triangles_within_counted.restype = C.c_int
+    L.rtk_amd_within_stack_entries.argtypes = []
+    L.rtk_amd_within_stack_entries.restype = C.c_uint32
     L.rtk_dev_trace_rays_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(DevFilter), C.POINTER(TraceOpts), C.c_void_p]
     L.rtk_dev_trace_rays_count.restype = C.c_int
     L.rtk_dev_trace_rays_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter), C.POINTER(TraceOpts), C.c_void_p]
@@ -638,6 +650,108 @@ class DeviceScene:
         d_rec, d_pts = self.closest_points_device(to_device(q), n)
         _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
         return d_rec.cpu().numpy().view(CLOSEST_RECORD_DTYPE), d_pts.cpu().numpy().view(np.float32).reshape(n, 3)
+
+    # -- triangles within a distance (rtk_dev_triangles_within_count / _all): asynchronous on the current stream --
+
+    def count_within_device(self, d_queries, n, d_counts=None, count=None, ids=None):
+        """The number of triangles nearer than its max_dist2 to each of n queries (POINT_QUERY_DTYPE bytes on the device;
+        include/rtk_amd.h, "Triangles within a distance"): a cuda tensor of n uint32 words (d_counts: any cuda tensor of at
+        least 4 n bytes; None: a new int32 tensor). count / ids: cuda int64 tensors naming the queries to answer, as for
+        closest_points_device; slots that are not listed are not written. Nothing waits for the stream."""
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        if ids is not None and count is None:
+            raise RtkError("count_within_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        _check(lib().rtk_dev_triangles_within_count(self.handle, C.c_void_p(d_queries.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                    C.c_void_p(d_counts.data_ptr()), _stream_ptr()), "rtk_dev_triangles_within_count")
+        return d_counts
+
+    def within_all_device(self, d_queries, n, d_offsets, d_records, d_points=None, d_written=None, count=None, ids=None):
+        """Query i's nearest triangles within its max_dist2, ascending in (dist2, prim), into records d_offsets[i] ..
+        d_offsets[i + 1] of d_records (16-byte CLOSEST_RECORD_DTYPE records) and, if d_points is given, their points into the
+        same entries of d_points (3 floats each): as many as the query has or the segment holds. d_offsets: a cuda int64 tensor
+        of n + 1 entries. d_written: a cuda tensor of 4 n bytes, or None (the call gets NULL). Records beyond written[i], and
+        outside every segment, are not written. count / ids as for count_within_device. Nothing waits for the stream."""
+        if ids is not None and count is None:
+            raise RtkError("within_all_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        _check(lib().rtk_dev_triangles_within_all(self.handle, C.c_void_p(d_queries.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                  C.c_void_p(d_offsets.data_ptr()), C.c_void_p(d_records.data_ptr()),
+                                                  C.c_void_p(d_points.data_ptr()) if d_points is not None else None,
+                                                  C.c_void_p(d_written.data_ptr()) if d_written is not None else None,
+                                                  _stream_ptr()), "rtk_dev_triangles_within_all")
+        return d_written
+
+    def triangles_within_counted(self, d_queries, n, d_offsets=None, d_records=None, d_points=None, d_counts=None):
+        """count_within_device (d_offsets None) or within_all_device of all n queries on the null stream, synchronous, with the
+        visit counts of rtk_dev_triangles_within_counted: returns (d_counts -- the counts, or the written numbers --, counts dict)."""
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        ctr = TraceCounters()
+        torch.cuda.synchronize()
+        _check(lib().rtk_dev_triangles_within_counted(self.handle, C.c_void_p(d_queries.data_ptr()), n,
+                                                      C.c_void_p(d_offsets.data_ptr()) if d_offsets is not None else None,
+                                                      C.c_void_p(d_records.data_ptr()) if d_records is not None else None,
+                                                      C.c_void_p(d_points.data_ptr()) if d_points is not None else None,
+                                                      C.c_void_p(d_counts.data_ptr()), C.byref(ctr)), "rtk_dev_triangles_within_counted")
+        return d_counts, ctr.as_dict()
+
+    def _within_queries(self, points, max_dist):
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        q = np.zeros(pts.shape[0], POINT_QUERY_DTYPE)
+        q["point"] = pts
+        if max_dist is None:
+            q["max_dist2"] = RTK_INF
+        else:
+            d = np.broadcast_to(np.asarray(max_dist, np.float32), (pts.shape[0],))
+            with np.errstate(over="ignore", invalid="ignore"):
+                q["max_dist2"] = d * d
+        return q
+
+    def triangles_within(self, points, max_dist, max_per_point=None):
+        """Every triangle nearer than max_dist to each point, or with max_per_point=k the k nearest of them. points: array-like
+        (n, 3) float32; max_dist: a distance (scalar or one per point), squared in float32; None = no limit (RTK_INF). Returns
+        (offsets int64[n + 1], records CLOSEST_RECORD_DTYPE[offsets[n]], points (offsets[n], 3) float32, written uint32[n]):
+        point i's triangles are records[offsets[i] : offsets[i] + written[i]], ascending in (dist2, prim), and points[j] is the
+        point on the triangle of records[j]. Without max_per_point: a count, its prefix sum on the device and the fill, enqueued
+        without a host wait in between (only the size of the buffers is read back, to allocate them), and written[i] ==
+        offsets[i + 1] - offsets[i]. With it: offsets[i] = i * k, no count, and the entries of a segment beyond written[i] are zero."""
+        torch = _torch()
+        q = self._within_queries(points, max_dist)
+        n = q.shape[0]
+        if n == 0:
+            return np.zeros(1, np.int64), np.zeros(0, CLOSEST_RECORD_DTYPE), np.zeros((0, 3), np.float32), np.zeros(0, np.uint32)
+        d_q = to_device(q)
+        if max_per_point is None:
+            d_counts = self.count_within_device(d_q, n)
+            d_offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+            d_offsets[1:] = torch.cumsum(d_counts, 0, dtype=torch.int64)
+            total = int(d_offsets[n].item())                 # (the one read-back: how many records to allocate)
+        else:
+            k = int(max_per_point)
+            if k < 0:
+                raise RtkError("triangles_within: max_per_point %r" % (max_per_point,))
+            d_offsets = torch.arange(n + 1, dtype=torch.int64, device="cuda") * k
+            total = n * k
+        d_records = torch.zeros(max(total, 1) * 16, dtype=torch.uint8, device="cuda")
+        d_points = torch.zeros(max(total, 1) * 12, dtype=torch.uint8, device="cuda")
+        d_written = torch.empty(n, dtype=torch.int32, device="cuda")
+        self.within_all_device(d_q, n, d_offsets, d_records, d_points, d_written)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return (d_offsets.cpu().numpy(), d_records.cpu().numpy().view(CLOSEST_RECORD_DTYPE)[:total],
+                d_points.cpu().numpy().view(np.float32).reshape(-1, 3)[:total], d_written.cpu().numpy().view(np.uint32))
+
+    def nearest_triangles(self, points, k, max_dist=None):
+        """The k nearest triangles to each point (nearer than max_dist, if given). Returns (records CLOSEST_RECORD_DTYPE (n, k),
+        points (n, k, 3) float32, written uint32[n]): row i holds written[i] entries, ascending in (dist2, prim); the rest of
+        the row is zero."""
+        k = int(k)
+        n = np.ascontiguousarray(points, np.float32).reshape(-1, 3).shape[0]
+        _, rec, pts, written = self.triangles_within(points, max_dist, max_per_point=k)
+        return rec.reshape(n, k), pts.reshape(n, k, 3), written
 
     # -- every hit along a ray (rtk_dev_trace_rays_count / rtk_dev_trace_rays_all): asynchronous on the current stream --
 

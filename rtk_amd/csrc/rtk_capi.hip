@@ -198,6 +198,25 @@ extern "C" int rtk_dev_closest_points_counted(const rtk_dev_scene *ds, const rtk
 	return rtk_launch_closest(ds, d_queries, num_queries, nullptr, d_records, d_points, nullptr, out);
 }
 
+extern "C" int rtk_dev_triangles_within_count(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries,
+	const rtk_ray_list *list, uint32_t *d_counts, void *stream)
+{
+	return rtk_launch_within(ds, d_queries, num_queries, list, d_counts, nullptr, nullptr, nullptr, false, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_triangles_within_all(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries,
+	const rtk_ray_list *list, const uint64_t *d_offsets, rtk_closest_record *d_records, float *d_points, uint32_t *d_written, void *stream)
+{
+	return rtk_launch_within(ds, d_queries, num_queries, list, d_written, d_offsets, d_records, d_points, true, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_triangles_within_counted(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries,
+	const uint64_t *d_offsets, rtk_closest_record *d_records, float *d_points, uint32_t *d_counts_or_written, rtk_trace_counters *out)
+{
+	if (!out) { rtk_set_error("rtk_dev_triangles_within_counted: NULL counters"); return RTK_AMD_ERR_BAD_ARG; }
+	return rtk_launch_within(ds, d_queries, num_queries, nullptr, d_counts_or_written, d_offsets, d_records, d_points, d_offsets != nullptr, nullptr, out);
+}
+
 extern "C" int rtk_dev_trace_rays_count(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
 	uint32_t *d_counts, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream)
 {

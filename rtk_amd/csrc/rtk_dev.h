@@ -332,6 +332,11 @@ int rtk_launch_select(rtk_dev_scene *ds, const void *d_src, uint32_t kind, size_
 // -- rtk_dev_closest_points (rtk_closest.hip) --
 int rtk_launch_closest(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries, const rtk_ray_list *list,
 	rtk_closest_record *d_records, float *d_points, hipStream_t stream, rtk_trace_counters *counted = nullptr);   // counted: synchronises the stream
+// -- rtk_dev_triangles_within_count / rtk_dev_triangles_within_all (rtk_within.hip) --
+// fill: offsets, records, points or NULL, d_counts the written numbers or NULL; else d_counts the counts. counted: synchronises the stream
+int rtk_launch_within(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries, const rtk_ray_list *list,
+	uint32_t *d_counts, const uint64_t *d_offsets, rtk_closest_record *d_records, float *d_points, bool fill, hipStream_t stream,
+	rtk_trace_counters *counted = nullptr);
 // -- the look for an image nobody announced (rtk_detect.hip) --
 int rtk_detect_image(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, hipStream_t stream, uint32_t *w_out, uint32_t *h_out);
 // -- hit records to full hits, and rtk_trace_ray's one-ray launch (rtk_expand.hip) --
