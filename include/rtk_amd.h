@@ -567,6 +567,65 @@ int rtk_dev_triangles_within_counted(const rtk_dev_scene *ds, const rtk_point_qu
 /* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
 uint32_t rtk_amd_within_stack_entries(void);
 
+/* ---- Triangles that touch a box: how many triangles touch an axis-aligned box, and which ----
+ * The region question of the family: voxelisation and occupancy grids, broad-phase collision against a body's bounds, "select
+ * everything in this region", tiling a scene for out-of-core work. A sphere around the box's centre through
+ * rtk_dev_triangles_within_* over-reports by up to the corner distance, pays a closest-point evaluation with a division per
+ * triangle and still leaves the caller to run a box test of their own. This walk is the cheapest the tree offers: box against
+ * box, comparisons only, no arithmetic in the skip. The calls read the scene as it stands, changing no bit of it.
+ *
+ * THE RULE (rtk_amd/csrc/rtk_box_rule.h; INTEGRATION.md "Triangles that touch a box"). All arithmetic is float32, every
+ * operation rounded on its own, no FMA. A query is LIVE iff its six numbers are finite and lo[a] <= hi[a] on every axis; lo == hi
+ * on one, two or three axes is legal (a rectangle, a segment, a point). A query that is not live has no candidates; neither has
+ * any query of a scene without triangles. A triangle is a CANDIDATE of a live query iff its own box (componentwise min / max of
+ * its vertices) has tlo[a] <= hi[a] && thi[a] >= lo[a] on all three axes -- CLOSED: touching counts -- and none of the other
+ * ten axes of Akenine-Moller's test (the nine unit_i x e_j and the triangle's plane, about the box's centre (lo + hi) * 0.5f with
+ * the half extent (hi - lo) * 0.5f) separates the two; a comparison with a NaN never separates. It is a FLOAT RULE and the
+ * candidate set is DEFINED BY IT; on inputs whose intermediates are exact it is the exact answer. The LIST of a query is its
+ * candidates in ASCENDING PRIMITIVE ID. THE RESULT DOES NOT DEPEND ON THE TREE OR ON THE ORDER OF THE WALK: a child box [clo, chi]
+ * is left out only if clo[a] > hi[a] || chi[a] < lo[a] on some axis, exact without a margin because every box above a triangle
+ * contains the triangle's own box. Only the exact 128-byte nodes are used.
+ *
+ * rtk_dev_triangles_in_box_count: d_counts[i] = the number of candidates of query i, written for EVERY answered query (0 for a
+ *   query without any); nothing else is written.
+ * rtk_dev_triangles_in_box_all: query i owns d_prims[d_offsets[i] .. d_offsets[i + 1]); d_offsets has num_queries + 1 entries,
+ *   indexed by query slot; r = d_offsets[i + 1] - d_offsets[i] is its room and may be 0. Written are the first min(count_i, r)
+ *   entries of the query's list, each one global primitive id; d_written[i] (d_written may be NULL) is that number. Entries of
+ *   the segment beyond it ARE NOT WRITTEN, entries outside every segment are not written. A query whose offsets decrease has
+ *   no room and nothing is written for it (d_written[i] = 0). One call serves two uses:
+ *     every triangle in the box   count, an inclusive prefix sum into uint64 offsets on the same stream (torch.cumsum into an
+ *                                 int64 tensor is one as it stands), then fill;
+ *     at most k, deterministic    d_offsets[i] = i * k, no count pass: the k LOWEST ids among the candidates. THAT WALK CANNOT BE
+ *                                 CULLED BY WHAT IT HAS KEPT, since the tree is not ordered by id: it visits what the count
+ *                                 visits, and a candidate that does not get in costs no memory access.
+ * `list` may be NULL: all num_queries queries are answered. Otherwise the words of closest points hold: m = min(*d_count,
+ * num_queries) entries are answered, the results of query r go to slot r of d_counts / d_written and to segment r, A SLOT THAT
+ * IS NOT LISTED IS NOT WRITTEN, an id may repeat (the query is answered once), the count is read when the work reaches it on
+ * `stream`, and an id >= num_queries is the caller's error.
+ * DETERMINISTIC: the same inputs give the same bytes. Asynchronous on `stream`: no host wait, nothing read back. The scene is
+ * only read, as it stands: built, uploaded, refitted, split or rebuilt, and rtk_mgpu_scene(m, i) as it is; the thread-safety
+ * rules of the batches hold. The part of the walk's stack that does not fit on chip (and one bit per query for a list with ids)
+ * lives in the per-(scene, stream) scratch set, and a dropped push (impossible for a tree) is reported by rtk_dev_trace_status
+ * like a trace's. Nothing they allocate counts toward the scene.
+ * Refused before anything is launched and before any HIP call, RTK_AMD_ERR_BAD_ARG, with a message that names the function: a
+ * NULL scene; NULL d_boxes or d_counts, NULL d_offsets or d_prims with num_queries != 0; a bad list (as for the listed
+ * traces); num_queries >= 2^32; a calling thread whose current device is not the scene's. num_queries == 0 is RTK_AMD_OK with
+ * nothing launched. Offsets that run past the caller's buffer are the caller's error and are NOT CHECKED.
+ * A scene with non-finite vertex coordinates: the calls terminate and write only inside their outputs; NOTHING ELSE IS PROMISED
+ * about their results. */
+typedef struct rtk_box_query { float lo[3], hi[3]; } rtk_box_query;      /* 24 bytes; a torch float32 [n, 6] tensor is one */
+int rtk_dev_triangles_in_box_count(const rtk_dev_scene *ds, const rtk_box_query *d_boxes, size_t num_queries,
+	const rtk_ray_list *list, uint32_t *d_counts, void *stream);
+int rtk_dev_triangles_in_box_all(const rtk_dev_scene *ds, const rtk_box_query *d_boxes, size_t num_queries,
+	const rtk_ray_list *list, const uint64_t *d_offsets, uint32_t *d_prims, uint32_t *d_written /* may be NULL */, void *stream);
+/* The same results without a list, plus visit counts in the fields of rtk_dev_closest_points_counted (hits = queries with at least
+ * one candidate counted or kept). d_offsets == NULL: the count form, d_counts_or_written receives the counts (required);
+ * otherwise the fill form, d_counts_or_written may be NULL. Null stream, synchronous; not for timing. */
+int rtk_dev_triangles_in_box_counted(const rtk_dev_scene *ds, const rtk_box_query *d_boxes, size_t num_queries,
+	const uint64_t *d_offsets, uint32_t *d_prims, uint32_t *d_counts_or_written, rtk_trace_counters *out);
+/* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
+uint32_t rtk_amd_box_stack_entries(void);
+
 /* ---- Every hit along a ray: how many triangles a ray crosses, and all of them (or the k closest) in one walk ----
  * What transparency and alpha compositing, thickness and x-ray depth, visibility through several occluders and point-in-mesh by
  * crossing parity ask. Until now the only route was the d_after loop of rtk_dev_trace_rays_filtered: one complete closest-hit

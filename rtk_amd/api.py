@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from .types import (CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, MeshSet, Placement, SceneDesc, SceneHeader, placement_array)
+from .types import (BOX_QUERY_DTYPE, CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, MeshSet, Placement, SceneDesc, SceneHeader, placement_array)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RTK_AMD_LIB") or os.path.join(HERE, "librtk_amd.so")   # RTK_AMD_LIB: kernel A/B builds only
@@ -159,7 +159,9 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_dev_closest_points", "rtk_dev_closest_points_counted", "rtk_amd_closest_stack_entries",
                      "rtk_dev_trace_rays_count", "rtk_dev_trace_rays_all", "rtk_amd_allhits_stack_entries",
                      "rtk_dev_triangles_within_count", "rtk_dev_triangles_within_all", "rtk_dev_triangles_within_counted",
-                     "rtk_amd_within_stack_entries"]
+                     "rtk_amd_within_stack_entries",
+                     "rtk_dev_triangles_in_box_count", "rtk_dev_triangles_in_box_all", "rtk_dev_triangles_in_box_counted",
+                     "rtk_amd_box_stack_entries"]
 
 _lib = None
 
@@ -238,6 +240,14 @@ def lib():
     L.rtk_dev_triangles_within_counted.restype = C.c_int
     L.rtk_amd_within_stack_entries.argtypes = []
     L.rtk_amd_within_stack_entries.restype = C.c_uint32
+    L.rtk_dev_triangles_in_box_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p]
+    L.rtk_dev_triangles_in_box_count.restype = C.c_int
+    L.rtk_dev_triangles_in_box_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtk_dev_triangles_in_box_all.restype = C.c_int
+    L.rtk_dev_triangles_in_box_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
+    L.rtk_dev_triangles_in_box_counted.restype = C.c_int
+    L.rtk_amd_box_stack_entries.argtypes = []
+    L.rtk_amd_box_stack_entries.restype = C.c_uint32
     L.rtk_dev_trace_rays_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(DevFilter), C.POINTER(TraceOpts), C.c_void_p]
     L.rtk_dev_trace_rays_count.restype = C.c_int
     L.rtk_dev_trace_rays_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter), C.POINTER(TraceOpts), C.c_void_p]
@@ -752,6 +762,99 @@ class DeviceScene:
         n = np.ascontiguousarray(points, np.float32).reshape(-1, 3).shape[0]
         _, rec, pts, written = self.triangles_within(points, max_dist, max_per_point=k)
         return rec.reshape(n, k), pts.reshape(n, k, 3), written
+
+    # -- triangles that touch a box (rtk_dev_triangles_in_box_count / _all): asynchronous on the current stream --
+
+    def count_in_boxes_device(self, d_boxes, n, d_counts=None, count=None, ids=None):
+        """The number of triangles that touch each of n boxes (BOX_QUERY_DTYPE bytes on the device, or a float32 [n, 6] cuda
+        tensor of lo, hi; include/rtk_amd.h, "Triangles that touch a box"): a cuda tensor of n uint32 words (d_counts: any
+        cuda tensor of at least 4 n bytes; None: a new int32 tensor). count / ids: cuda int64 tensors naming the queries to
+        answer, as for closest_points_device; slots that are not listed are not written. Nothing waits for the stream."""
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        if ids is not None and count is None:
+            raise RtkError("count_in_boxes_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        _check(lib().rtk_dev_triangles_in_box_count(self.handle, C.c_void_p(d_boxes.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                    C.c_void_p(d_counts.data_ptr()), _stream_ptr()), "rtk_dev_triangles_in_box_count")
+        return d_counts
+
+    def in_boxes_all_device(self, d_boxes, n, d_offsets, d_prims, d_written=None, count=None, ids=None):
+        """Box i's triangles, ascending global primitive ids (uint32), into entries d_offsets[i] .. d_offsets[i + 1] of d_prims:
+        as many as the box has or the segment holds, the lowest ids first. d_offsets: a cuda int64 tensor of n + 1 entries.
+        d_written: a cuda tensor of 4 n bytes, or None (the call gets NULL). Entries beyond written[i], and outside every
+        segment, are not written. count / ids as for count_in_boxes_device. Nothing waits for the stream."""
+        if ids is not None and count is None:
+            raise RtkError("in_boxes_all_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        _check(lib().rtk_dev_triangles_in_box_all(self.handle, C.c_void_p(d_boxes.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                  C.c_void_p(d_offsets.data_ptr()), C.c_void_p(d_prims.data_ptr()),
+                                                  C.c_void_p(d_written.data_ptr()) if d_written is not None else None,
+                                                  _stream_ptr()), "rtk_dev_triangles_in_box_all")
+        return d_written
+
+    def triangles_in_boxes_counted(self, d_boxes, n, d_offsets=None, d_prims=None, d_counts=None):
+        """count_in_boxes_device (d_offsets None) or in_boxes_all_device of all n boxes on the null stream, synchronous, with the
+        visit counts of rtk_dev_triangles_in_box_counted: returns (d_counts -- the counts, or the written numbers --, counts dict)."""
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        ctr = TraceCounters()
+        torch.cuda.synchronize()
+        _check(lib().rtk_dev_triangles_in_box_counted(self.handle, C.c_void_p(d_boxes.data_ptr()), n,
+                                                      C.c_void_p(d_offsets.data_ptr()) if d_offsets is not None else None,
+                                                      C.c_void_p(d_prims.data_ptr()) if d_prims is not None else None,
+                                                      C.c_void_p(d_counts.data_ptr()), C.byref(ctr)), "rtk_dev_triangles_in_box_counted")
+        return d_counts, ctr.as_dict()
+
+    def triangles_in_boxes(self, boxes, max_per_box=None):
+        """Every triangle that touches each box, or with max_per_box=k the k lowest ids of them. boxes: array-like (n, 6) float32
+        of lo, hi, or BOX_QUERY_DTYPE records. Returns (offsets int64[n + 1], prims uint32[offsets[n]], written uint32[n]): box
+        i's triangles are prims[offsets[i] : offsets[i] + written[i]], ascending. Without max_per_box: a count, its prefix sum on
+        the device and the fill, enqueued without a host wait in between (only the size of the buffer is read back, to allocate
+        it), and written[i] == offsets[i + 1] - offsets[i]. With it: offsets[i] = i * k, no count, and the entries of a segment
+        beyond written[i] are zero."""
+        torch = _torch()
+        boxes = np.asarray(boxes)
+        q = np.ascontiguousarray(boxes if boxes.dtype == BOX_QUERY_DTYPE else np.asarray(boxes, np.float32).reshape(-1, 6))
+        n = q.shape[0]
+        if n == 0:
+            return np.zeros(1, np.int64), np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+        d_q = to_device(q)
+        if max_per_box is None:
+            d_counts = self.count_in_boxes_device(d_q, n)
+            d_offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+            d_offsets[1:] = torch.cumsum(d_counts, 0, dtype=torch.int64)
+            total = int(d_offsets[n].item())                 # (the one read-back: how many ids to allocate)
+        else:
+            k = int(max_per_box)
+            if k < 0:
+                raise RtkError("triangles_in_boxes: max_per_box %r" % (max_per_box,))
+            d_offsets = torch.arange(n + 1, dtype=torch.int64, device="cuda") * k
+            total = n * k
+        d_prims = torch.zeros(max(total, 1), dtype=torch.int32, device="cuda")
+        d_written = torch.empty(n, dtype=torch.int32, device="cuda")
+        self.in_boxes_all_device(d_q, n, d_offsets, d_prims, d_written)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return d_offsets.cpu().numpy(), d_prims.cpu().numpy().view(np.uint32)[:total], d_written.cpu().numpy().view(np.uint32)
+
+    def occupancy(self, lo, hi, shape):
+        """A bool cuda tensor of `shape` (nx, ny, nz): true where at least one triangle touches the voxel. The voxel faces are
+        one float32 torch.linspace(lo[a], hi[a], shape[a] + 1) per axis (made on the host, so its bits do not depend on the
+        device), so neighbours share their face bits and a triangle that touches a shared face is in both. One count over
+        nx * ny * nz boxes on the current stream; the result is not waited for."""
+        torch = _torch()
+        shape = tuple(int(s) for s in shape)
+        if len(shape) != 3 or min(shape) < 1:
+            raise RtkError("occupancy: shape %r" % (shape,))
+        faces = [torch.linspace(float(lo[a]), float(hi[a]), shape[a] + 1, dtype=torch.float32).cuda() for a in range(3)]
+        lows = torch.stack(torch.meshgrid(faces[0][:-1], faces[1][:-1], faces[2][:-1], indexing="ij"), -1)
+        highs = torch.stack(torch.meshgrid(faces[0][1:], faces[1][1:], faces[2][1:], indexing="ij"), -1)
+        d_boxes = torch.cat([lows, highs], -1).reshape(-1, 6).contiguous()
+        n = d_boxes.shape[0]
+        d_counts = self.count_in_boxes_device(d_boxes, n)
+        return (d_counts != 0).reshape(shape)
 
     # -- every hit along a ray (rtk_dev_trace_rays_count / rtk_dev_trace_rays_all): asynchronous on the current stream --
 

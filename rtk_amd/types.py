@@ -22,8 +22,10 @@ HIT_RECORD_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", 
 # rtk_point_query and rtk_closest_record of include/rtk_amd.h (rtk_dev_closest_points): the record has the shape of the hit record
 POINT_QUERY_DTYPE = np.dtype([("point", "<f4", (3,)), ("max_dist2", "<f4")])
 CLOSEST_RECORD_DTYPE = np.dtype([("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4")])
+# rtk_box_query of include/rtk_amd.h (rtk_dev_triangles_in_box_count / _all): a float32 [n, 6] array is one
+BOX_QUERY_DTYPE = np.dtype([("lo", "<f4", (3,)), ("hi", "<f4", (3,))])
 
-assert POINT_QUERY_DTYPE.itemsize == 16 and CLOSEST_RECORD_DTYPE.itemsize == 16
+assert POINT_QUERY_DTYPE.itemsize == 16 and CLOSEST_RECORD_DTYPE.itemsize == 16 and BOX_QUERY_DTYPE.itemsize == 24
 assert VERTEX_DTYPE.itemsize == 16 and RAY_DTYPE.itemsize == 32
 assert HIT_DTYPE.itemsize == 68 and HIT_RECORD_DTYPE.itemsize == 16
 
