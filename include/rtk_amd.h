@@ -626,6 +626,80 @@ int rtk_dev_triangles_in_box_counted(const rtk_dev_scene *ds, const rtk_box_quer
 /* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
 uint32_t rtk_amd_box_stack_entries(void);
 
+/* ---- Triangles that touch a triangle: which triangles of the scene a given triangle meets ----
+ * The narrow phase that the box query (a body's bounds) and the distance query (contact generation) lead up to: mesh-against-mesh
+ * collision, one body's triangles against another body's scene; self-intersection checks of a deforming mesh after a refit;
+ * cutting and boolean pre-passes; "does this swept quad hit anything". A box query over-reports by everything that lies in the
+ * triangle's box but not on the triangle, and a ray or a distance query cannot put the question at all. The calls read the scene
+ * as it stands, changing no bit of it.
+ *
+ * THE RULE (rtk_amd/csrc/rtk_touch_rule.h; INTEGRATION.md "Triangles that touch a triangle"). All arithmetic is float32, every
+ * operation rounded on its own, no FMA. The query A = (v0, v1, v2) is LIVE iff its nine numbers are finite; a query without area
+ * (a segment, a point) is live. A query that is not live has no candidates; neither has any query of a scene without triangles.
+ * A record B of the scene is a CANDIDATE of a live query iff B's own box (componentwise min / max of its vertices) and A's have
+ * tlo[a] <= ahi[a] && thi[a] >= alo[a] on all three axes -- CLOSED: touching counts --, none of the SEVENTEEN AXES separates the
+ * two -- the two normals, the nine cross products of an edge of A with an edge of B, and the six in-plane edge normals nA x ea_i,
+ * nB x eb_j, all always evaluated; an axis separates iff every projection of B is above every projection of A or every one
+ * below, and a comparison with a NaN never separates --, and the filter lets it through. It is a FLOAT RULE and the candidate
+ * set is DEFINED BY IT. A separating axis proves disjointness in exact arithmetic, so on inputs whose intermediates are exact
+ * the rule never loses a pair that meets, and for two triangles of non-zero area it is then the exact answer; if A or B has no
+ * area it may keep a pair that does not meet (a segment in B's plane that passes beside B). The LIST of a query is its
+ * candidates in ASCENDING PRIMITIVE ID. THE RESULT DOES NOT DEPEND ON THE TREE OR ON THE ORDER OF THE WALK: a child box is left
+ * out only if it is disjoint from A's box by comparison, exact without a margin because every box above a triangle contains the
+ * triangle's own box. Only the exact 128-byte nodes are used.
+ *
+ * THE FILTER is part of the rule and is applied to the record's global primitive id and stored positions. filter == NULL: none.
+ *   d_first_prim (may be NULL)      indexed by query slot, like the per-ray filter arrays: a candidate of query i has
+ *                                   prim >= d_first_prim[i].
+ *   RTK_TOUCH_SKIP_SHARED_VERTEX    a record is not a candidate if one of its vertices equals one of the query's on all three
+ *                                   coordinates by float ==. Neighbours in a mesh share positions bit for bit, and a triangle
+ *                                   shares them with itself: the flag plus d_first_prim[i] = (the query's own id) + 1 gives each
+ *                                   self-intersecting pair of a scene once.
+ *
+ * rtk_dev_triangles_touching_count: d_counts[i] = the number of candidates of query i, written for EVERY answered query (0 for
+ *   a query without any); nothing else is written.
+ * rtk_dev_triangles_touching_all: query i owns d_prims[d_offsets[i] .. d_offsets[i + 1]); d_offsets has num_queries + 1 entries,
+ *   indexed by query slot; r = d_offsets[i + 1] - d_offsets[i] is its room and may be 0. Written are the first min(count_i, r)
+ *   entries of the query's list, each one global primitive id; d_written[i] (d_written may be NULL) is that number. Entries of
+ *   the segment beyond it ARE NOT WRITTEN, entries outside every segment are not written. A query whose offsets decrease has
+ *   no room and nothing is written for it (d_written[i] = 0). One call serves two uses:
+ *     every triangle it meets     count, an inclusive prefix sum into uint64 offsets on the same stream (torch.cumsum into an
+ *                                 int64 tensor is one as it stands), then fill;
+ *     at most k, deterministic    d_offsets[i] = i * k, no count pass: the k LOWEST ids among the candidates. THAT WALK CANNOT BE
+ *                                 CULLED BY WHAT IT HAS KEPT, since the tree is not ordered by id: it visits what the count
+ *                                 visits, and a candidate that does not get in costs no memory access.
+ * `list` may be NULL: all num_queries queries are answered. Otherwise the words of closest points hold: m = min(*d_count,
+ * num_queries) entries are answered, the results of query r go to slot r of d_counts / d_written and to segment r, A SLOT THAT
+ * IS NOT LISTED IS NOT WRITTEN, an id may repeat (the query is answered once), the count is read when the work reaches it on
+ * `stream`, and an id >= num_queries is the caller's error.
+ * DETERMINISTIC: the same inputs give the same bytes. Asynchronous on `stream`: no host wait, nothing read back. The scene is
+ * only read, as it stands: built, uploaded, refitted, split or rebuilt, and rtk_mgpu_scene(m, i) as it is; the thread-safety
+ * rules of the batches hold. The part of the walk's stack that does not fit on chip (and one bit per query for a list with ids)
+ * lives in the per-(scene, stream) scratch set, and a dropped push (impossible for a tree) is reported by rtk_dev_trace_status
+ * like a trace's. Nothing they allocate counts toward the scene.
+ * Refused before anything is launched and before any HIP call, RTK_AMD_ERR_BAD_ARG, with a message that names the function: a
+ * NULL scene; NULL d_tris or d_counts, NULL d_offsets or d_prims with num_queries != 0; a bad list (as for the listed
+ * traces); a filter whose struct_size is too small or whose flags hold an unknown bit; num_queries >= 2^32; a calling thread
+ * whose current device is not the scene's. num_queries == 0 is RTK_AMD_OK with nothing launched. Offsets that run past the
+ * caller's buffer are the caller's error and are NOT CHECKED.
+ * A scene with non-finite vertex coordinates: the calls terminate and write only inside their outputs; NOTHING ELSE IS PROMISED
+ * about their results. */
+typedef struct rtk_tri_query { float v0[3], v1[3], v2[3]; } rtk_tri_query;     /* 36 bytes; a torch float32 [n, 9] tensor is one */
+enum { RTK_TOUCH_SKIP_SHARED_VERTEX = 1u };
+typedef struct rtk_touch_filter { uint32_t struct_size; uint32_t flags; const uint32_t *d_first_prim; /* device, per query slot; may be NULL */ } rtk_touch_filter;
+int rtk_dev_triangles_touching_count(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_ray_list *list, const rtk_touch_filter *filter, uint32_t *d_counts, void *stream);
+int rtk_dev_triangles_touching_all(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_ray_list *list, const rtk_touch_filter *filter, const uint64_t *d_offsets, uint32_t *d_prims,
+	uint32_t *d_written /* may be NULL */, void *stream);
+/* The same results without a list, plus visit counts in the fields of rtk_dev_closest_points_counted (hits = queries with at least
+ * one candidate counted or kept). d_offsets == NULL: the count form, d_counts_or_written receives the counts (required);
+ * otherwise the fill form, d_counts_or_written may be NULL. Null stream, synchronous; not for timing. */
+int rtk_dev_triangles_touching_counted(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_touch_filter *filter, const uint64_t *d_offsets, uint32_t *d_prims, uint32_t *d_counts_or_written, rtk_trace_counters *out);
+/* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
+uint32_t rtk_amd_touch_stack_entries(void);
+
 /* ---- Every hit along a ray: how many triangles a ray crosses, and all of them (or the k closest) in one walk ----
  * What transparency and alpha compositing, thickness and x-ray depth, visibility through several occluders and point-in-mesh by
  * crossing parity ask. Until now the only route was the d_after loop of rtk_dev_trace_rays_filtered: one complete closest-hit

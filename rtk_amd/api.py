@@ -12,7 +12,8 @@ import os
 
 import numpy as np
 
-from .types import (BOX_QUERY_DTYPE, CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, MeshSet, Placement, SceneDesc, SceneHeader, placement_array)
+from .types import (BOX_QUERY_DTYPE, CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, TRI_QUERY_DTYPE, MeshSet, Placement, SceneDesc, SceneHeader,
+                    placement_array)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RTK_AMD_LIB") or os.path.join(HERE, "librtk_amd.so")   # RTK_AMD_LIB: kernel A/B builds only
@@ -93,6 +94,26 @@ class RayList(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("d_ids", C.c_void_p), ("d_count", C.c_void_p)]
 
 
+class TouchFilter(C.Structure):
+    """rtk_touch_filter: the filter of the touching calls (include/rtk_amd.h, "Triangles that touch a triangle")."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("d_first_prim", C.c_void_p)]
+
+
+TOUCH_SKIP_SHARED_VERTEX = 1
+
+
+def make_touch_filter(first_prim=None, skip_shared=False):
+    """first_prim: a cuda tensor of one 32-bit word per query slot, or None; it must outlive the calls that read it. Returns None
+    when there is nothing to filter (the calls then get NULL)."""
+    if first_prim is None and not skip_shared:
+        return None
+    f = TouchFilter()
+    f.struct_size = C.sizeof(TouchFilter)
+    f.flags = TOUCH_SKIP_SHARED_VERTEX if skip_shared else 0
+    f.d_first_prim = first_prim.data_ptr() if first_prim is not None else None
+    return f
+
+
 # rtk_dev_select_rays kinds
 SELECT_RECORD_HIT, SELECT_RECORD_MISS, SELECT_BYTE_NONZERO, SELECT_BYTE_ZERO = 0, 1, 2, 3
 
@@ -161,7 +182,9 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_dev_triangles_within_count", "rtk_dev_triangles_within_all", "rtk_dev_triangles_within_counted",
                      "rtk_amd_within_stack_entries",
                      "rtk_dev_triangles_in_box_count", "rtk_dev_triangles_in_box_all", "rtk_dev_triangles_in_box_counted",
-                     "rtk_amd_box_stack_entries"]
+                     "rtk_amd_box_stack_entries",
+                     "rtk_dev_triangles_touching_count", "rtk_dev_triangles_touching_all", "rtk_dev_triangles_touching_counted",
+                     "rtk_amd_touch_stack_entries"]
 
 _lib = None
 
@@ -248,6 +271,14 @@ def lib():
     L.rtk_dev_triangles_in_box_counted.restype = C.c_int
     L.rtk_amd_box_stack_entries.argtypes = []
     L.rtk_amd_box_stack_entries.restype = C.c_uint32
+    L.rtk_dev_triangles_touching_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(TouchFilter), C.c_void_p, C.c_void_p]
+    L.rtk_dev_triangles_touching_count.restype = C.c_int
+    L.rtk_dev_triangles_touching_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(TouchFilter), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtk_dev_triangles_touching_all.restype = C.c_int
+    L.rtk_dev_triangles_touching_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TouchFilter), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
+    L.rtk_dev_triangles_touching_counted.restype = C.c_int
+    L.rtk_amd_touch_stack_entries.argtypes = []
+    L.rtk_amd_touch_stack_entries.restype = C.c_uint32
     L.rtk_dev_trace_rays_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(DevFilter), C.POINTER(TraceOpts), C.c_void_p]
     L.rtk_dev_trace_rays_count.restype = C.c_int
     L.rtk_dev_trace_rays_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter), C.POINTER(TraceOpts), C.c_void_p]
@@ -855,6 +886,139 @@ class DeviceScene:
         n = d_boxes.shape[0]
         d_counts = self.count_in_boxes_device(d_boxes, n)
         return (d_counts != 0).reshape(shape)
+
+    # -- triangles that touch a triangle (rtk_dev_triangles_touching_count / _all): asynchronous on the current stream --
+
+    def count_touching_device(self, d_tris, n, d_counts=None, count=None, ids=None, first_prim=None, skip_shared=False):
+        """The number of the scene's triangles that each of n query triangles meets (TRI_QUERY_DTYPE bytes on the device, or a
+        float32 [n, 9] or [n, 3, 3] cuda tensor; include/rtk_amd.h, "Triangles that touch a triangle"): a cuda tensor of n
+        uint32 words (d_counts: any cuda tensor of at least 4 n bytes; None: a new int32 tensor). count / ids: cuda int64
+        tensors naming the queries to answer, as for closest_points_device; slots that are not listed are not written.
+        first_prim: a cuda tensor of n 32-bit words, query i keeps ids >= first_prim[i]; skip_shared: records that share a
+        vertex position with the query are left out. Nothing waits for the stream."""
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        if ids is not None and count is None:
+            raise RtkError("count_touching_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        f = make_touch_filter(first_prim, skip_shared)
+        _check(lib().rtk_dev_triangles_touching_count(self.handle, C.c_void_p(d_tris.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                      C.byref(f) if f is not None else None, C.c_void_p(d_counts.data_ptr()), _stream_ptr()),
+               "rtk_dev_triangles_touching_count")
+        return d_counts
+
+    def touching_all_device(self, d_tris, n, d_offsets, d_prims, d_written=None, count=None, ids=None, first_prim=None, skip_shared=False):
+        """Query i's triangles, ascending global primitive ids (uint32), into entries d_offsets[i] .. d_offsets[i + 1] of d_prims:
+        as many as it meets or the segment holds, the lowest ids first. d_offsets: a cuda int64 tensor of n + 1 entries.
+        d_written: a cuda tensor of 4 n bytes, or None (the call gets NULL). Entries beyond written[i], and outside every
+        segment, are not written. The other arguments as for count_touching_device. Nothing waits for the stream."""
+        if ids is not None and count is None:
+            raise RtkError("touching_all_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        f = make_touch_filter(first_prim, skip_shared)
+        _check(lib().rtk_dev_triangles_touching_all(self.handle, C.c_void_p(d_tris.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                    C.byref(f) if f is not None else None, C.c_void_p(d_offsets.data_ptr()),
+                                                    C.c_void_p(d_prims.data_ptr()), C.c_void_p(d_written.data_ptr()) if d_written is not None else None,
+                                                    _stream_ptr()), "rtk_dev_triangles_touching_all")
+        return d_written
+
+    def triangles_touching_counted(self, d_tris, n, d_offsets=None, d_prims=None, d_counts=None, first_prim=None, skip_shared=False):
+        """count_touching_device (d_offsets None) or touching_all_device of all n queries on the null stream, synchronous, with the
+        visit counts of rtk_dev_triangles_touching_counted: returns (d_counts -- the counts, or the written numbers --, counts dict)."""
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        ctr = TraceCounters()
+        f = make_touch_filter(first_prim, skip_shared)
+        torch.cuda.synchronize()
+        _check(lib().rtk_dev_triangles_touching_counted(self.handle, C.c_void_p(d_tris.data_ptr()), n, C.byref(f) if f is not None else None,
+                                                        C.c_void_p(d_offsets.data_ptr()) if d_offsets is not None else None,
+                                                        C.c_void_p(d_prims.data_ptr()) if d_prims is not None else None,
+                                                        C.c_void_p(d_counts.data_ptr()), C.byref(ctr)), "rtk_dev_triangles_touching_counted")
+        return d_counts, ctr.as_dict()
+
+    def _touching_on_device(self, d_q, n, k, d_first, skip_shared):
+        """count, prefix sum and fill (or, with k, offsets i * k and the fill) on the current stream -> (d_offsets int64 [n + 1],
+        d_prims int32 [max(total, 1)], d_written int32 [n], total). Only the size of the buffer is read back."""
+        torch = _torch()
+        if k is None:
+            d_counts = self.count_touching_device(d_q, n, first_prim=d_first, skip_shared=skip_shared)
+            d_offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+            d_offsets[1:] = torch.cumsum(d_counts, 0, dtype=torch.int64)
+            total = int(d_offsets[n].item())                 # (the one read-back: how many ids to allocate)
+        else:
+            d_offsets = torch.arange(n + 1, dtype=torch.int64, device="cuda") * k
+            total = n * k
+        d_prims = torch.zeros(max(total, 1), dtype=torch.int32, device="cuda")
+        d_written = torch.empty(n, dtype=torch.int32, device="cuda")
+        self.touching_all_device(d_q, n, d_offsets, d_prims, d_written, first_prim=d_first, skip_shared=skip_shared)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return d_offsets, d_prims, d_written, total
+
+    def triangles_touching(self, tris, max_per_tri=None, first_prim=None, skip_shared=False):
+        """Every triangle of the scene that each query triangle meets, or with max_per_tri=k the k lowest ids of them. tris:
+        array-like (n, 9) or (n, 3, 3) float32, or TRI_QUERY_DTYPE records; first_prim: array-like of n ids or None. Returns
+        (offsets int64[n + 1], prims uint32[offsets[n]], written uint32[n]): query i's triangles are
+        prims[offsets[i] : offsets[i] + written[i]], ascending. Without max_per_tri: a count, its prefix sum on the device and
+        the fill, enqueued without a host wait in between (only the size of the buffer is read back, to allocate it), and
+        written[i] == offsets[i + 1] - offsets[i]. With it: offsets[i] = i * k, no count, and the entries of a segment beyond
+        written[i] are zero."""
+        torch = _torch()
+        tris = np.asarray(tris)
+        q = np.ascontiguousarray(tris if tris.dtype == TRI_QUERY_DTYPE else np.asarray(tris, np.float32).reshape(-1, 9))
+        n = q.shape[0]
+        if n == 0:
+            return np.zeros(1, np.int64), np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+        k = None
+        if max_per_tri is not None:
+            k = int(max_per_tri)
+            if k < 0:
+                raise RtkError("triangles_touching: max_per_tri %r" % (max_per_tri,))
+        d_first = None
+        if first_prim is not None:
+            first = np.ascontiguousarray(first_prim, np.uint32)
+            if first.shape != (n,):
+                raise RtkError("triangles_touching: first_prim of shape %r for %d queries" % (first.shape, n))
+            d_first = torch.from_numpy(first.view(np.int32)).cuda()
+        d_offsets, d_prims, d_written, total = self._touching_on_device(to_device(q), n, k, d_first, skip_shared)
+        return d_offsets.cpu().numpy(), d_prims.cpu().numpy().view(np.uint32)[:total], d_written.cpu().numpy().view(np.uint32)
+
+    def triangles(self):
+        """The scene's current positions by primitive id: a float32 cuda tensor [T, 3, 3], through rtk_dev_expand_hits of one
+        made-up record per primitive, on the current stream. A batch of queries as it stands."""
+        torch = _torch()
+        n = self.info()["num_triangles"]
+        if n == 0:
+            return torch.zeros((0, 3, 3), dtype=torch.float32, device="cuda")
+        rec = torch.zeros((n, 4), dtype=torch.int32, device="cuda")
+        rec[:, 3] = torch.arange(n, dtype=torch.int32, device="cuda")
+        d_hits, _ = self.expand_device(rec, n)
+        # (rtk_hit: t u v, then three vertices of position[3] and index, then mesh and triangle: 17 words)
+        return d_hits.view(torch.float32).reshape(n, 17)[:, 3:15].reshape(n, 3, 4)[:, :, :3].contiguous()
+
+    def _pairs(self, d_q, d_first, skip_shared):
+        torch = _torch()
+        n = d_q.shape[0]
+        if n == 0 or self.info()["num_triangles"] == 0:
+            return torch.zeros((0, 2), dtype=torch.int64, device="cuda")
+        d_offsets, d_prims, d_written, total = self._touching_on_device(d_q, n, None, d_first, skip_shared)
+        who = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device="cuda"), d_written.to(torch.int64), output_size=total)
+        return torch.stack([who, d_prims[:total].to(torch.int64) & 0xffffffff], 1)
+
+    def intersections(self, other):
+        """The pairs (primitive of other, primitive of self) whose triangles meet by the rule, other.triangles() being the
+        queries: an int64 cuda tensor [m, 2], ascending in both columns. Count, prefix sum and fill on the current stream."""
+        return self._pairs(other.triangles(), None, False)
+
+    def self_intersections(self):
+        """The pairs (i, j), i < j, of the scene's own triangles that meet by the rule and share no vertex position (neighbours in
+        a mesh share positions bit for bit and always touch): an int64 cuda tensor [m, 2], ascending in both columns. The
+        queries are self.triangles(), with skip_shared and first_prim = own id + 1."""
+        torch = _torch()
+        d_q = self.triangles()
+        d_first = torch.arange(1, d_q.shape[0] + 1, dtype=torch.int32, device="cuda")
+        return self._pairs(d_q, d_first, True)
 
     # -- every hit along a ray (rtk_dev_trace_rays_count / rtk_dev_trace_rays_all): asynchronous on the current stream --
 

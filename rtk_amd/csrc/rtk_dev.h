@@ -341,6 +341,11 @@ int rtk_launch_within(const rtk_dev_scene *ds, const rtk_point_query *d_queries,
 // fill: offsets, prims, d_counts the written numbers or NULL; else d_counts the counts. counted: synchronises the stream
 int rtk_launch_box(const rtk_dev_scene *ds, const rtk_box_query *d_boxes, size_t num_queries, const rtk_ray_list *list,
 	uint32_t *d_counts, const uint64_t *d_offsets, uint32_t *d_prims, bool fill, hipStream_t stream, rtk_trace_counters *counted = nullptr);
+// -- rtk_dev_triangles_touching_count / rtk_dev_triangles_touching_all (rtk_touch.hip) --
+// as rtk_launch_box, with the filter (or NULL)
+int rtk_launch_touch(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries, const rtk_ray_list *list,
+	const rtk_touch_filter *filter, uint32_t *d_counts, const uint64_t *d_offsets, uint32_t *d_prims, bool fill, hipStream_t stream,
+	rtk_trace_counters *counted = nullptr);
 // -- the look for an image nobody announced (rtk_detect.hip) --
 int rtk_detect_image(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, hipStream_t stream, uint32_t *w_out, uint32_t *h_out);
 // -- hit records to full hits, and rtk_trace_ray's one-ray launch (rtk_expand.hip) --

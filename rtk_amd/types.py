@@ -24,8 +24,11 @@ POINT_QUERY_DTYPE = np.dtype([("point", "<f4", (3,)), ("max_dist2", "<f4")])
 CLOSEST_RECORD_DTYPE = np.dtype([("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4")])
 # rtk_box_query of include/rtk_amd.h (rtk_dev_triangles_in_box_count / _all): a float32 [n, 6] array is one
 BOX_QUERY_DTYPE = np.dtype([("lo", "<f4", (3,)), ("hi", "<f4", (3,))])
+# rtk_tri_query of include/rtk_amd.h (rtk_dev_triangles_touching_count / _all): a float32 [n, 9] array is one
+TRI_QUERY_DTYPE = np.dtype([("v0", "<f4", (3,)), ("v1", "<f4", (3,)), ("v2", "<f4", (3,))])
 
 assert POINT_QUERY_DTYPE.itemsize == 16 and CLOSEST_RECORD_DTYPE.itemsize == 16 and BOX_QUERY_DTYPE.itemsize == 24
+assert TRI_QUERY_DTYPE.itemsize == 36
 assert VERTEX_DTYPE.itemsize == 16 and RAY_DTYPE.itemsize == 32
 assert HIT_DTYPE.itemsize == 68 and HIT_RECORD_DTYPE.itemsize == 16
 
