@@ -700,6 +700,69 @@ int rtk_dev_triangles_touching_counted(const rtk_dev_scene *ds, const rtk_tri_qu
 /* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
 uint32_t rtk_amd_touch_stack_entries(void);
 
+/* ---- Closest triangles: how far a triangle (or a segment, or a point) is from the scene, and where the two nearest points are ----
+ * The distance query that stands next to "collide": clearance and minimum separation between two meshes, the distance term of
+ * contact models (which need edge-edge as well as point-triangle distances), thickness and self-proximity of a deforming mesh
+ * after a refit, safe step sizes. Sampling points for rtk_dev_closest_points misses every edge-edge closest pair, and
+ * rtk_dev_triangles_touching_* says "0 or not 0" and nothing more. The call reads the scene as it stands, changing no bit of it.
+ *
+ * THE RULE (rtk_amd/csrc/rtk_pair_rule.h; INTEGRATION.md "Closest triangles"). All arithmetic is float32, every operation
+ * rounded on its own, no FMA. The query A = (v0, v1, v2) is LIVE iff its nine numbers are finite; a query without area (a segment,
+ * a point) is live and is a supported use. For a record B of the scene, FIFTEEN FEATURE PAIRS in a fixed order -- A's three
+ * vertices against B and B's three against A through the point rule of closest points as it is, then the nine pairs of an edge
+ * of A with an edge of B by a segment-segment routine whose parallel and zero-length cases are selects, never 0 / 0, without an
+ * epsilon -- each give a point qa on A and a point qb on B; qa IS CLAMPED TO A'S OWN BOX AND qb TO B'S OWN BOX, and dist2 is the
+ * squared difference of the two clamped points. The pair's result is the feature with the smallest dist2, the first in the order
+ * among equal ones; a NaN never wins. PIERCING: if the two triangles' own boxes touch (closed) and an edge of one goes through the
+ * other -- its end points strictly on opposite sides of the plane, the three scalar triple products of one sign, zero as either
+ * sign but not all three zero --, dist2 = 0 and qa = qb = the crossing point, clamped to the boxes' intersection; the first of
+ * the six edges in the order decides. The seventeen axes of the touching calls are not used: a segment beside a triangle gets its
+ * true distance. It is a FLOAT RULE and the result is DEFINED BY IT. The answer to (A, max_dist2) is, over all records that the
+ * filter lets through and whose dist2 < max_dist2 -- strictly --, the smallest dist2, THE LOWEST PRIMITIVE ID AMONG EQUAL dist2,
+ * or a miss. THE RESULT DOES NOT DEPEND ON THE TREE OR ON THE ORDER OF THE WALK: a subtree is left out only if the bound b of its
+ * box against A's box (per axis the gap max(lo - ahi, alo - hi, 0), squared and summed in dist2's order) has b > best dist2 so
+ * far -- strictly, an equal bound can hide a lower id -- or b >= max_dist2, and that bound never exceeds the dist2 of a record
+ * inside the box, without a margin, because qa lies in A's box and qb in a box inside the node's. Only the exact 128-byte nodes
+ * are used.
+ *   hit    dist2, u and v (the weights of B's vertex 0 and vertex 1 at qb) and the global primitive id;
+ *          d_points_query[3 i ..] = qa, d_points_scene[3 i ..] = qb
+ *   miss   dist2 = max_dist2 as given (RTK_INF with a NULL array), u = v = 0, prim = RTK_PRIM_NONE; both points = the query's
+ *          vertex 0 as given
+ * The record is rtk_closest_record: rtk_dev_select_rays (RTK_SELECT_RECORD_HIT / _MISS) and rtk_dev_expand_hits take it as it
+ * is. A query that is not live is a miss; so is one whose max_dist2 is NaN, zero or negative, and any query of a scene without
+ * triangles. d_max_dist2 is indexed by query slot; NULL means RTK_INF, no limit, for every query.
+ *
+ * THE FILTER is part of the rule: rtk_touch_filter as for the touching calls (d_first_prim indexed by query slot, and
+ * RTK_TOUCH_SKIP_SHARED_VERTEX), applied to the record's global primitive id and stored positions. The flag together with
+ * d_first_prim[i] = (the query's own id) + 1 gives each triangle of a mesh its nearest non-adjacent triangle of a higher id:
+ * the minimum over the mesh is its self-clearance.
+ *
+ * `list` may be NULL: all num_queries queries are answered. Otherwise the words of closest points hold: m = min(*d_count,
+ * num_queries) entries are answered, the result of query r goes to slot r of d_records (and of the point arrays), A SLOT THAT IS
+ * NOT LISTED IS NOT WRITTEN, an id may repeat, the count is read when the work reaches it on `stream`, and an id >= num_queries
+ * is the caller's error. d_points_query and d_points_scene may each be NULL.
+ * DETERMINISTIC: the same inputs give the same bytes. Asynchronous on `stream`: no host wait, nothing read back. The scene is
+ * only read, as it stands: built, uploaded, refitted, split or rebuilt, and rtk_mgpu_scene(m, i) as it is; the thread-safety
+ * rules of the batches hold. The part of the walk's stack that does not fit on chip lives in the per-(scene, stream) scratch
+ * set, and a dropped push (impossible for a tree) is reported by rtk_dev_trace_status like a trace's. Nothing it allocates
+ * counts toward the scene.
+ * Refused before anything is launched and before any HIP call, RTK_AMD_ERR_BAD_ARG, with a message that names the function: a
+ * NULL scene; NULL d_tris or d_records with num_queries != 0; a bad list (as for the listed traces); a filter whose struct_size
+ * is too small or whose flags hold an unknown bit; num_queries >= 2^32; a calling thread whose current device is not the
+ * scene's. num_queries == 0 is RTK_AMD_OK with nothing launched.
+ * A scene with non-finite vertex coordinates: the call terminates and writes only inside its outputs; NOTHING ELSE IS PROMISED
+ * about its results. */
+int rtk_dev_closest_triangles(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_ray_list *list, const rtk_touch_filter *filter, const float *d_max_dist2 /* per query slot; NULL = RTK_INF */,
+	rtk_closest_record *d_records, float *d_points_query /* may be NULL */, float *d_points_scene /* may be NULL */, void *stream);
+/* The same results without a list, plus visit counts in the fields of rtk_dev_closest_points_counted (triangles = records
+ * fetched, of which those that their own box rules out are not evaluated). Null stream, synchronous; not for timing. */
+int rtk_dev_closest_triangles_counted(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_touch_filter *filter, const float *d_max_dist2, rtk_closest_record *d_records, float *d_points_query,
+	float *d_points_scene, rtk_trace_counters *out);
+/* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
+uint32_t rtk_amd_pair_stack_entries(void);
+
 /* ---- Every hit along a ray: how many triangles a ray crosses, and all of them (or the k closest) in one walk ----
  * What transparency and alpha compositing, thickness and x-ray depth, visibility through several occluders and point-in-mesh by
  * crossing parity ask. Until now the only route was the d_after loop of rtk_dev_trace_rays_filtered: one complete closest-hit

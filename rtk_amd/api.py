@@ -184,7 +184,8 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_dev_triangles_in_box_count", "rtk_dev_triangles_in_box_all", "rtk_dev_triangles_in_box_counted",
                      "rtk_amd_box_stack_entries",
                      "rtk_dev_triangles_touching_count", "rtk_dev_triangles_touching_all", "rtk_dev_triangles_touching_counted",
-                     "rtk_amd_touch_stack_entries"]
+                     "rtk_amd_touch_stack_entries",
+                     "rtk_dev_closest_triangles", "rtk_dev_closest_triangles_counted", "rtk_amd_pair_stack_entries"]
 
 _lib = None
 
@@ -279,6 +280,12 @@ def lib():
     L.rtk_dev_triangles_touching_counted.restype = C.c_int
     L.rtk_amd_touch_stack_entries.argtypes = []
     L.rtk_amd_touch_stack_entries.restype = C.c_uint32
+    L.rtk_dev_closest_triangles.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(TouchFilter), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtk_dev_closest_triangles.restype = C.c_int
+    L.rtk_dev_closest_triangles_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TouchFilter), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
+    L.rtk_dev_closest_triangles_counted.restype = C.c_int
+    L.rtk_amd_pair_stack_entries.argtypes = []
+    L.rtk_amd_pair_stack_entries.restype = C.c_uint32
     L.rtk_dev_trace_rays_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(DevFilter), C.POINTER(TraceOpts), C.c_void_p]
     L.rtk_dev_trace_rays_count.restype = C.c_int
     L.rtk_dev_trace_rays_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter), C.POINTER(TraceOpts), C.c_void_p]
@@ -1019,6 +1026,120 @@ class DeviceScene:
         d_q = self.triangles()
         d_first = torch.arange(1, d_q.shape[0] + 1, dtype=torch.int32, device="cuda")
         return self._pairs(d_q, d_first, True)
+
+    # -- closest triangles (rtk_dev_closest_triangles): asynchronous on the current stream, nothing here waits for it --
+
+    def closest_triangles_device(self, d_tris, n, d_records=None, d_points_query=None, d_points_scene=None, max_dist2=None, count=None, ids=None,
+                                 first_prim=None, skip_shared=False):
+        """The nearest triangle of the scene to each of n query triangles, segments or points (TRI_QUERY_DTYPE bytes on the
+        device, or a float32 [n, 9] or [n, 3, 3] cuda tensor; include/rtk_amd.h, "Closest triangles"): returns (d_records,
+        d_points_query, d_points_scene), uint8 cuda tensors of CLOSEST_RECORD_DTYPE records and of 3 floats per query each (any
+        cuda tensors of enough bytes may be passed in; None: new ones). max_dist2: a cuda float32 tensor of one squared limit per query slot, or
+        None (no limit). count / ids: cuda int64 tensors naming the queries to answer, as for closest_points_device; slots that
+        are not listed are not written. first_prim / skip_shared: the filter of count_touching_device."""
+        torch = _torch()
+        if d_records is None:
+            d_records = torch.empty(max(n, 1) * 16, dtype=torch.uint8, device="cuda")[:n * 16]
+        if d_points_query is None:
+            d_points_query = torch.empty(max(n, 1) * 12, dtype=torch.uint8, device="cuda")[:n * 12]
+        if d_points_scene is None:
+            d_points_scene = torch.empty(max(n, 1) * 12, dtype=torch.uint8, device="cuda")[:n * 12]
+        if ids is not None and count is None:
+            raise RtkError("closest_triangles_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        f = make_touch_filter(first_prim, skip_shared)
+        _check(lib().rtk_dev_closest_triangles(self.handle, C.c_void_p(d_tris.data_ptr()), n, C.byref(l) if l is not None else None,
+                                               C.byref(f) if f is not None else None,
+                                               C.c_void_p(max_dist2.data_ptr()) if max_dist2 is not None else None, C.c_void_p(d_records.data_ptr()),
+                                               C.c_void_p(d_points_query.data_ptr()), C.c_void_p(d_points_scene.data_ptr()),
+                                               _stream_ptr()), "rtk_dev_closest_triangles")
+        return d_records, d_points_query, d_points_scene
+
+    def closest_triangles_counted(self, d_tris, n, max_dist2=None, first_prim=None, skip_shared=False):
+        """closest_triangles_device of all n queries on the null stream, synchronous, with the visit counts of
+        rtk_dev_closest_triangles_counted: returns (d_records, d_points_query, d_points_scene, counts dict)."""
+        torch = _torch()
+        d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        d_pq = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        d_ps = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        ctr = TraceCounters()
+        f = make_touch_filter(first_prim, skip_shared)
+        torch.cuda.synchronize()
+        _check(lib().rtk_dev_closest_triangles_counted(self.handle, C.c_void_p(d_tris.data_ptr()), n, C.byref(f) if f is not None else None,
+                                                       C.c_void_p(max_dist2.data_ptr()) if max_dist2 is not None else None,
+                                                       C.c_void_p(d_records.data_ptr()), C.c_void_p(d_pq.data_ptr()), C.c_void_p(d_ps.data_ptr()),
+                                                       C.byref(ctr)), "rtk_dev_closest_triangles_counted")
+        return d_records, d_pq, d_ps, ctr.as_dict()
+
+    def closest_triangles(self, tris, max_dist=None, first_prim=None, skip_shared=False):
+        """The nearest triangle of the scene to each query. tris: array-like (n, 9) or (n, 3, 3) float32, or TRI_QUERY_DTYPE
+        records (a segment or a point is a triangle with equal vertices); max_dist: a distance (scalar or one per query) at
+        or beyond which a triangle does not count, squared in float32, None = no limit; first_prim: array-like of n ids or
+        None. Returns (dist float32[n] -- the square root of dist2 --, prim uint32[n], u, v float32[n], points on the query
+        (n, 3), points on the scene (n, 3)): prim == 0xFFFFFFFF is a miss, whose points are the query's vertex 0."""
+        torch = _torch()
+        tris = np.asarray(tris)
+        q = np.ascontiguousarray(tris if tris.dtype == TRI_QUERY_DTYPE else np.asarray(tris, np.float32).reshape(-1, 9))
+        n = q.shape[0]
+        if n == 0:
+            z = np.zeros(0, np.float32)
+            return z, np.zeros(0, np.uint32), z.copy(), z.copy(), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
+        d_max = None
+        if max_dist is not None:
+            d = np.broadcast_to(np.asarray(max_dist, np.float32), (n,))
+            with np.errstate(over="ignore", invalid="ignore"):
+                d_max = torch.from_numpy(np.ascontiguousarray(d * d)).cuda()
+        d_first = None
+        if first_prim is not None:
+            first = np.ascontiguousarray(first_prim, np.uint32)
+            if first.shape != (n,):
+                raise RtkError("closest_triangles: first_prim of shape %r for %d queries" % (first.shape, n))
+            d_first = torch.from_numpy(first.view(np.int32)).cuda()
+        d_rec, d_pq, d_ps = self.closest_triangles_device(to_device(q), n, max_dist2=d_max, first_prim=d_first, skip_shared=skip_shared)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        rec = d_rec.cpu().numpy().view(CLOSEST_RECORD_DTYPE)
+        with np.errstate(invalid="ignore"):
+            dist = np.sqrt(rec["dist2"])
+        return (dist, rec["prim"].copy(), rec["u"].copy(), rec["v"].copy(), d_pq.cpu().numpy().view(np.float32).reshape(n, 3),
+                d_ps.cpu().numpy().view(np.float32).reshape(n, 3))
+
+    def _nearest_pair(self, d_q, d_first, skip_shared):
+        """The smallest (dist2, query index) over the queries d_q [n, 3, 3], reduced on the device: (distance, query index,
+        primitive of self, point on the query, point on self), or None if no query found a triangle."""
+        torch = _torch()
+        n = d_q.shape[0]
+        if n == 0 or self.info()["num_triangles"] == 0:
+            return None
+        d_rec, d_pq, d_ps = self.closest_triangles_device(d_q, n, first_prim=d_first, skip_shared=skip_shared)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        rec = d_rec.view(torch.int32).reshape(n, 4)
+        hit = rec[:, 3] != -1
+        # (dist2 >= +0: its bits order like its value; the query index breaks ties, the lowest first)
+        key = torch.where(hit, (rec[:, 0].to(torch.int64) << 32) | torch.arange(n, dtype=torch.int64, device="cuda"),
+                          torch.full((n,), 2 ** 63 - 1, dtype=torch.int64, device="cuda"))
+        best = int(torch.argmin(key).item())                 # (the one read-back, with the row below)
+        row = torch.cat([rec[best].view(torch.float32), d_pq.view(torch.float32).reshape(n, 3)[best], d_ps.view(torch.float32).reshape(n, 3)[best]]).cpu().numpy()
+        prim = int(row[3:4].view(np.uint32)[0])
+        if prim == 0xFFFFFFFF:
+            return None
+        return float(np.sqrt(row[0])), best, prim, row[4:7].copy(), row[7:10].copy()
+
+    def distance(self, other):
+        """The distance between this scene and `other` by the rule of "Closest triangles", other.triangles() being the
+        queries against this scene, reduced on the device to the smallest (dist2, primitive of other): (distance, primitive of
+        other, primitive of self, point on other, point on self), or None if either scene has no triangles."""
+        return self._nearest_pair(other.triangles(), None, False)
+
+    def self_clearance(self):
+        """The smallest distance between two of the scene's own triangles that share no vertex position: the queries are
+        self.triangles() with skip_shared and first_prim = own id + 1. Returns (distance, i, j, point on i, point on j), i < j,
+        or None if there is no such pair. The rule's known weakness applies (rtk_amd/csrc/rtk_pair_rule.h): two triangles that
+        lie in one plane up to rounding and whose boxes touch can be called pierced by rounding errors, so a flat part of a
+        mesh that is not axis-aligned can make this return 0 although nothing meets."""
+        torch = _torch()
+        d_q = self.triangles()
+        d_first = torch.arange(1, d_q.shape[0] + 1, dtype=torch.int32, device="cuda")
+        return self._nearest_pair(d_q, d_first, True)
 
     # -- every hit along a ray (rtk_dev_trace_rays_count / rtk_dev_trace_rays_all): asynchronous on the current stream --
 
