@@ -763,6 +763,75 @@ int rtk_dev_closest_triangles_counted(const rtk_dev_scene *ds, const rtk_tri_que
 /* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
 uint32_t rtk_amd_pair_stack_entries(void);
 
+/* ---- Triangles near a triangle: how many triangles lie within a distance of a triangle, and all of them (or the k nearest) ----
+ * The last cell of the proximity family: mesh-against-mesh contact generation needs EVERY scene triangle within a contact margin
+ * of a body's triangle, with the two nearest points of each pair. rtk_dev_closest_triangles returns one pair per query and has
+ * no "after" -- one call per answer cannot be written --, rtk_dev_triangles_touching_* says "0 or not 0" and gives no points,
+ * and sampling points for rtk_dev_triangles_within_* misses every edge-edge pair. These calls are to closest triangles what
+ * "Triangles within a distance" is to closest points, and they read the scene the same way: as it stands, changing no bit of it.
+ *
+ * THE RULE (rtk_amd/csrc/rtk_near_rule.h on top of rtk_pair_rule.h; INTEGRATION.md "Triangles near a triangle"). dist2, u, v and
+ * the two points qa, qb of a (query, record) pair are those of closest triangles, bit for bit (rtk_pair_evaluate): the fifteen
+ * feature pairs, PIERCING (dist2 = 0, qa = qb) and both box clamps included. THE FILTER is rtk_touch_filter as for the touching
+ * calls (d_first_prim indexed by query slot, and RTK_TOUCH_SKIP_SHARED_VERTEX), applied to the record's global primitive id and
+ * stored positions. A record is a CANDIDATE of the query (A, max_dist2) iff the query is live (its nine numbers finite; a segment
+ * or a point is live), max_dist2 > 0, the filter passes and dist2 < max_dist2 -- strictly; a NaN dist2 is never one. A query
+ * that is not live or whose max_dist2 is NaN, zero or negative has no candidates; neither has any query of a scene without
+ * triangles. d_max_dist2 is indexed by query slot; NULL means RTK_INF, no limit, for every query. The LIST of a query is its
+ * candidates in ascending (dist2, prim) order, THE LOWEST PRIMITIVE ID FIRST AMONG EQUAL dist2: pierced pairs all have dist2 = 0
+ * and come first, by id. Its first entry, with its two points, is word for word what rtk_dev_closest_triangles writes for the
+ * query. THE RESULT DOES NOT DEPEND ON THE TREE OR ON THE ORDER OF THE WALK: a subtree -- or a record, by its own box -- is left
+ * out only if the bound b of its box against A's box has b >= max_dist2, or if the query's segment is full and b > worst.dist2
+ * (the last kept entry; strictly, an equal bound can hide a lower id), and that bound never exceeds the dist2 of a record inside
+ * the box, without a margin. Only the exact 128-byte nodes are used.
+ *
+ * rtk_dev_triangles_near_count: d_counts[i] = the number of candidates of query i, written for EVERY answered query (0 for a
+ *   query without any); nothing else is written.
+ * rtk_dev_triangles_near_all: query i owns d_records[d_offsets[i] .. d_offsets[i + 1]), and d_points_query[3 j ..] and
+ *   d_points_scene[3 j ..] (each may be NULL) belong to record j; d_offsets has num_queries + 1 entries, indexed by query slot;
+ *   r = d_offsets[i + 1] - d_offsets[i] is its room and may be 0. Written are the first min(count_i, r) entries of the query's
+ *   list, each the rtk_closest_record and the points qa (on the query) and qb (on the scene) closest triangles would write for
+ *   that record; d_written[i] (d_written may be NULL) is that number. Entries of the segment beyond it ARE NOT WRITTEN, entries
+ *   outside every segment are not written. A query whose offsets decrease has no room and nothing is written for it
+ *   (d_written[i] = 0). One call serves two uses:
+ *     every triangle within r   count, an inclusive prefix sum into uint64 offsets on the same stream (torch.cumsum into an int64
+ *                               tensor is one as it stands), then fill with the same limits and filter;
+ *     the k nearest             d_offsets[i] = i * k, no count pass; d_max_dist2 = NULL if there is no limit. The walk is culled
+ *                               by the k-th best distance so far, as closest triangles culls by the best.
+ * `list` may be NULL: all num_queries queries are answered. Otherwise the words of the within calls hold: m = min(*d_count,
+ * num_queries) entries are answered, the results of query r go to slot r of d_counts / d_written and to segment r, A SLOT THAT
+ * IS NOT LISTED IS NOT WRITTEN, an id may repeat (the query is answered once), the count is read when the work reaches it on
+ * `stream`, and an id >= num_queries is the caller's error.
+ * DETERMINISTIC: the same inputs give the same bytes. Asynchronous on `stream`: no host wait, nothing read back. The scene is
+ * only read, as it stands: built, uploaded, refitted, split or rebuilt, and rtk_mgpu_scene(m, i) as it is; the thread-safety
+ * rules of the batches hold. The part of the walk's stack that does not fit on chip (and one bit per query for a list with ids)
+ * lives in the per-(scene, stream) scratch set, and a dropped push (impossible for a tree) is reported by rtk_dev_trace_status
+ * like a trace's. Nothing they allocate counts toward the scene.
+ * Refused before anything is launched and before any HIP call, RTK_AMD_ERR_BAD_ARG, with a message that names the function: a
+ * NULL scene; NULL d_tris or d_counts, NULL d_offsets or d_records with num_queries != 0; a bad list (as for the listed
+ * traces); a filter whose struct_size is too small or whose flags hold an unknown bit; num_queries >= 2^32; a calling thread
+ * whose current device is not the scene's. num_queries == 0 is RTK_AMD_OK with nothing launched. Offsets that run past the
+ * caller's buffer are the caller's error and are NOT CHECKED.
+ * The weakness of the pair rule holds here as well: two triangles in one plane up to rounding whose boxes touch can be called
+ * pierced by rounding errors. A scene with non-finite vertex coordinates: the calls terminate and write only inside their
+ * outputs; NOTHING ELSE IS PROMISED about their results. */
+int rtk_dev_triangles_near_count(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_ray_list *list, const rtk_touch_filter *filter, const float *d_max_dist2 /* per query slot; NULL = RTK_INF */,
+	uint32_t *d_counts, void *stream);
+int rtk_dev_triangles_near_all(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_ray_list *list, const rtk_touch_filter *filter, const float *d_max_dist2, const uint64_t *d_offsets,
+	rtk_closest_record *d_records, float *d_points_query /* may be NULL */, float *d_points_scene /* may be NULL */,
+	uint32_t *d_written /* may be NULL */, void *stream);
+/* The same results without a list, plus visit counts in the fields of rtk_dev_closest_points_counted (triangles = records
+ * fetched, of which those that the filter or their own box rules out are not evaluated; hits = queries with at least one
+ * candidate counted or kept). d_offsets == NULL: the count form, d_counts_or_written receives the counts (required); otherwise
+ * the fill form, the point arrays and d_counts_or_written may be NULL. Null stream, synchronous; not for timing. */
+int rtk_dev_triangles_near_counted(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_touch_filter *filter, const float *d_max_dist2, const uint64_t *d_offsets, rtk_closest_record *d_records,
+	float *d_points_query, float *d_points_scene, uint32_t *d_counts_or_written, rtk_trace_counters *out);
+/* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
+uint32_t rtk_amd_near_stack_entries(void);
+
 /* ---- Every hit along a ray: how many triangles a ray crosses, and all of them (or the k closest) in one walk ----
  * What transparency and alpha compositing, thickness and x-ray depth, visibility through several occluders and point-in-mesh by
  * crossing parity ask. Until now the only route was the d_after loop of rtk_dev_trace_rays_filtered: one complete closest-hit

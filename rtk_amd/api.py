@@ -185,7 +185,9 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_amd_box_stack_entries",
                      "rtk_dev_triangles_touching_count", "rtk_dev_triangles_touching_all", "rtk_dev_triangles_touching_counted",
                      "rtk_amd_touch_stack_entries",
-                     "rtk_dev_closest_triangles", "rtk_dev_closest_triangles_counted", "rtk_amd_pair_stack_entries"]
+                     "rtk_dev_closest_triangles", "rtk_dev_closest_triangles_counted", "rtk_amd_pair_stack_entries",
+                     "rtk_dev_triangles_near_count", "rtk_dev_triangles_near_all", "rtk_dev_triangles_near_counted",
+                     "rtk_amd_near_stack_entries"]
 
 _lib = None
 
@@ -286,6 +288,16 @@ def lib():
     L.rtk_dev_closest_triangles_counted.restype = C.c_int
     L.rtk_amd_pair_stack_entries.argtypes = []
     L.rtk_amd_pair_stack_entries.restype = C.c_uint32
+    L.rtk_dev_triangles_near_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(TouchFilter), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtk_dev_triangles_near_count.restype = C.c_int
+    L.rtk_dev_triangles_near_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(TouchFilter), C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtk_dev_triangles_near_all.restype = C.c_int
+    L.rtk_dev_triangles_near_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TouchFilter), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
+    L.rtk_dev_triangles_near_counted.restype = C.c_int
+    L.rtk_amd_near_stack_entries.argtypes = []
+    L.rtk_amd_near_stack_entries.restype = C.c_uint32
     L.rtk_dev_trace_rays_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(DevFilter), C.POINTER(TraceOpts), C.c_void_p]
     L.rtk_dev_trace_rays_count.restype = C.c_int
     L.rtk_dev_trace_rays_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter), C.POINTER(TraceOpts), C.c_void_p]
@@ -1140,6 +1152,163 @@ class DeviceScene:
         d_q = self.triangles()
         d_first = torch.arange(1, d_q.shape[0] + 1, dtype=torch.int32, device="cuda")
         return self._nearest_pair(d_q, d_first, True)
+
+    # -- triangles near a triangle (rtk_dev_triangles_near_count / _all): asynchronous on the current stream --
+
+    def count_near_device(self, d_tris, n, d_counts=None, max_dist2=None, count=None, ids=None, first_prim=None, skip_shared=False):
+        """The number of the scene's triangles nearer than its limit to each of n query triangles, segments or points
+        (TRI_QUERY_DTYPE bytes on the device, or a float32 [n, 9] or [n, 3, 3] cuda tensor; include/rtk_amd.h, "Triangles near a
+        triangle"): a cuda tensor of n uint32 words (d_counts: any cuda tensor of at least 4 n bytes; None: a new int32
+        tensor). max_dist2: a cuda float32 tensor of one squared limit per query slot, or None (no limit: the whole filtered
+        scene). count / ids: cuda int64 tensors naming the queries to answer, as for closest_points_device; slots that are not
+        listed are not written. first_prim / skip_shared: the filter of count_touching_device. Nothing waits for the stream."""
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        if ids is not None and count is None:
+            raise RtkError("count_near_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        f = make_touch_filter(first_prim, skip_shared)
+        _check(lib().rtk_dev_triangles_near_count(self.handle, C.c_void_p(d_tris.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                  C.byref(f) if f is not None else None,
+                                                  C.c_void_p(max_dist2.data_ptr()) if max_dist2 is not None else None,
+                                                  C.c_void_p(d_counts.data_ptr()), _stream_ptr()), "rtk_dev_triangles_near_count")
+        return d_counts
+
+    def near_all_device(self, d_tris, n, d_offsets, d_records, d_points_query=None, d_points_scene=None, d_written=None, max_dist2=None,
+                        count=None, ids=None, first_prim=None, skip_shared=False):
+        """Query i's nearest triangles within its limit, ascending in (dist2, prim), into records d_offsets[i] ..
+        d_offsets[i + 1] of d_records (16-byte CLOSEST_RECORD_DTYPE records) and, where given, the nearest point on the query
+        and on the scene's triangle into the same entries of d_points_query and d_points_scene (3 floats each): as many as the
+        query has or the segment holds. d_offsets: a cuda int64 tensor of n + 1 entries. d_written: a cuda tensor of 4 n bytes,
+        or None (the call gets NULL). Records beyond written[i], and outside every segment, are not written. The other
+        arguments as for count_near_device. Nothing waits for the stream."""
+        if ids is not None and count is None:
+            raise RtkError("near_all_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        f = make_touch_filter(first_prim, skip_shared)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+        _check(lib().rtk_dev_triangles_near_all(self.handle, ptr(d_tris), n, C.byref(l) if l is not None else None,
+                                                C.byref(f) if f is not None else None, ptr(max_dist2), ptr(d_offsets), ptr(d_records),
+                                                ptr(d_points_query), ptr(d_points_scene), ptr(d_written), _stream_ptr()),
+               "rtk_dev_triangles_near_all")
+        return d_written
+
+    def near_counted(self, d_tris, n, d_offsets=None, d_records=None, d_points_query=None, d_points_scene=None, d_counts=None, max_dist2=None,
+                     first_prim=None, skip_shared=False):
+        """count_near_device (d_offsets None) or near_all_device of all n queries on the null stream, synchronous, with the visit
+        counts of rtk_dev_triangles_near_counted: returns (d_counts -- the counts, or the written numbers --, counts dict)."""
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        ctr = TraceCounters()
+        f = make_touch_filter(first_prim, skip_shared)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+        torch.cuda.synchronize()
+        _check(lib().rtk_dev_triangles_near_counted(self.handle, ptr(d_tris), n, C.byref(f) if f is not None else None, ptr(max_dist2),
+                                                    ptr(d_offsets), ptr(d_records), ptr(d_points_query), ptr(d_points_scene), ptr(d_counts),
+                                                    C.byref(ctr)), "rtk_dev_triangles_near_counted")
+        return d_counts, ctr.as_dict()
+
+    def _near_on_device(self, d_q, n, k, d_max, d_first, skip_shared):
+        """count, prefix sum and fill (or, with k, offsets i * k and the fill) on the current stream -> (d_offsets int64 [n + 1],
+        d_records uint8, d_points_query uint8, d_points_scene uint8, d_written int32 [n], total). Only the size of the buffers is
+        read back."""
+        torch = _torch()
+        if k is None:
+            d_counts = self.count_near_device(d_q, n, max_dist2=d_max, first_prim=d_first, skip_shared=skip_shared)
+            d_offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+            d_offsets[1:] = torch.cumsum(d_counts, 0, dtype=torch.int64)
+            total = int(d_offsets[n].item())                 # (the one read-back: how many records to allocate)
+        else:
+            d_offsets = torch.arange(n + 1, dtype=torch.int64, device="cuda") * k
+            total = n * k
+        d_records = torch.zeros(max(total, 1) * 16, dtype=torch.uint8, device="cuda")
+        d_pq = torch.zeros(max(total, 1) * 12, dtype=torch.uint8, device="cuda")
+        d_ps = torch.zeros(max(total, 1) * 12, dtype=torch.uint8, device="cuda")
+        d_written = torch.empty(n, dtype=torch.int32, device="cuda")
+        self.near_all_device(d_q, n, d_offsets, d_records, d_pq, d_ps, d_written, max_dist2=d_max, first_prim=d_first, skip_shared=skip_shared)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return d_offsets, d_records, d_pq, d_ps, d_written, total
+
+    def triangles_near(self, tris, max_dist, max_per_query=None, first_prim=None, skip_shared=False):
+        """Every triangle of the scene nearer than max_dist to each query triangle, or with max_per_query=k the k nearest of
+        them. tris: array-like (n, 9) or (n, 3, 3) float32, or TRI_QUERY_DTYPE records (a segment or a point is a triangle
+        with equal vertices); max_dist: a distance (scalar or one per query), squared in float32; None = no limit (RTK_INF);
+        first_prim: array-like of n ids or None. Returns (offsets int64[n + 1], records CLOSEST_RECORD_DTYPE[offsets[n]],
+        points on the query (offsets[n], 3) float32, points on the scene (offsets[n], 3) float32, written uint32[n]): query i's
+        triangles are records[offsets[i] : offsets[i] + written[i]], ascending in (dist2, prim). Without max_per_query: a
+        count, its prefix sum on the device and the fill, enqueued without a host wait in between (only the size of the buffers
+        is read back, to allocate them), and written[i] == offsets[i + 1] - offsets[i]. With it: offsets[i] = i * k, no count,
+        and the entries of a segment beyond written[i] are zero."""
+        torch = _torch()
+        tris = np.asarray(tris)
+        q = np.ascontiguousarray(tris if tris.dtype == TRI_QUERY_DTYPE else np.asarray(tris, np.float32).reshape(-1, 9))
+        n = q.shape[0]
+        if n == 0:
+            return (np.zeros(1, np.int64), np.zeros(0, CLOSEST_RECORD_DTYPE), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32),
+                    np.zeros(0, np.uint32))
+        k = None
+        if max_per_query is not None:
+            k = int(max_per_query)
+            if k < 0:
+                raise RtkError("triangles_near: max_per_query %r" % (max_per_query,))
+        d_max = None
+        if max_dist is not None:
+            d = np.broadcast_to(np.asarray(max_dist, np.float32), (n,))
+            with np.errstate(over="ignore", invalid="ignore"):
+                d_max = torch.from_numpy(np.ascontiguousarray(d * d)).cuda()
+        d_first = None
+        if first_prim is not None:
+            first = np.ascontiguousarray(first_prim, np.uint32)
+            if first.shape != (n,):
+                raise RtkError("triangles_near: first_prim of shape %r for %d queries" % (first.shape, n))
+            d_first = torch.from_numpy(first.view(np.int32)).cuda()
+        d_offsets, d_rec, d_pq, d_ps, d_written, total = self._near_on_device(to_device(q), n, k, d_max, d_first, skip_shared)
+        return (d_offsets.cpu().numpy(), d_rec.cpu().numpy().view(CLOSEST_RECORD_DTYPE)[:total],
+                d_pq.cpu().numpy().view(np.float32).reshape(-1, 3)[:total], d_ps.cpu().numpy().view(np.float32).reshape(-1, 3)[:total],
+                d_written.cpu().numpy().view(np.uint32))
+
+    def nearest_triangles_to(self, tris, k, max_dist=None):
+        """The k nearest triangles of the scene to each query triangle (nearer than max_dist, if given). Returns (records
+        CLOSEST_RECORD_DTYPE (n, k), points on the query (n, k, 3) float32, points on the scene (n, k, 3) float32, written
+        uint32[n]): row i holds written[i] entries, ascending in (dist2, prim); the rest of the row is zero."""
+        k = int(k)
+        _, rec, pq, ps, written = self.triangles_near(tris, max_dist, max_per_query=k)
+        n = len(written)
+        return rec.reshape(n, k), pq.reshape(n, k, 3), ps.reshape(n, k, 3), written
+
+    def _contacts(self, d_q, margin, d_first, skip_shared):
+        torch = _torch()
+        n = d_q.shape[0]
+        if n == 0 or self.info()["num_triangles"] == 0:
+            z = torch.zeros((0, 3), dtype=torch.float32, device="cuda")
+            return torch.zeros((0, 2), dtype=torch.int64, device="cuda"), torch.zeros(0, dtype=torch.float32, device="cuda"), z, z.clone()
+        m = np.float32(margin)
+        with np.errstate(over="ignore", invalid="ignore"):
+            d_max = torch.full((n,), float(m * m), dtype=torch.float32, device="cuda")
+        d_offsets, d_rec, d_pq, d_ps, d_written, total = self._near_on_device(d_q, n, None, d_max, d_first, skip_shared)
+        who = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device="cuda"), d_written.to(torch.int64), output_size=total)
+        rec = d_rec.view(torch.int32).reshape(-1, 4)[:total]
+        pairs = torch.stack([who, rec[:, 3].to(torch.int64) & 0xffffffff], 1)
+        return (pairs, torch.sqrt(rec[:, 0].contiguous().view(torch.float32)), d_pq.view(torch.float32).reshape(-1, 3)[:total],
+                d_ps.view(torch.float32).reshape(-1, 3)[:total])
+
+    def contacts(self, other, margin):
+        """Every pair (primitive of other, primitive of self) whose triangles are nearer than `margin` by the rule of "Triangles
+        near a triangle", other.triangles() being the queries: cuda tensors (pairs int64 [m, 2], distance float32 [m], point on
+        other [m, 3], point on self [m, 3]), ascending in the primitive of other, then in (distance, primitive of self). Count,
+        prefix sum and fill on the current stream; only the number of pairs is read back."""
+        return self._contacts(other.triangles(), margin, None, False)
+
+    def self_contacts(self, margin):
+        """The pairs (i, j), i < j, of the scene's own triangles that are nearer than `margin` and share no vertex position, each
+        once: the queries are self.triangles() with skip_shared and first_prim = own id + 1. Returns what contacts returns. The
+        weakness stated under self_clearance applies."""
+        torch = _torch()
+        d_q = self.triangles()
+        d_first = torch.arange(1, d_q.shape[0] + 1, dtype=torch.int32, device="cuda")
+        return self._contacts(d_q, margin, d_first, True)
 
     # -- every hit along a ray (rtk_dev_trace_rays_count / rtk_dev_trace_rays_all): asynchronous on the current stream --
 

@@ -270,6 +270,29 @@ extern "C" int rtk_dev_closest_triangles_counted(const rtk_dev_scene *ds, const 
 	return rtk_launch_pair(ds, d_tris, num_queries, nullptr, filter, d_max_dist2, d_records, d_points_query, d_points_scene, nullptr, out);
 }
 
+extern "C" int rtk_dev_triangles_near_count(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_ray_list *list, const rtk_touch_filter *filter, const float *d_max_dist2, uint32_t *d_counts, void *stream)
+{
+	return rtk_launch_near(ds, d_tris, num_queries, list, filter, d_max_dist2, d_counts, nullptr, nullptr, nullptr, nullptr, false, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_triangles_near_all(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_ray_list *list, const rtk_touch_filter *filter, const float *d_max_dist2, const uint64_t *d_offsets, rtk_closest_record *d_records,
+	float *d_points_query, float *d_points_scene, uint32_t *d_written, void *stream)
+{
+	return rtk_launch_near(ds, d_tris, num_queries, list, filter, d_max_dist2, d_written, d_offsets, d_records, d_points_query, d_points_scene, true,
+		(hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_triangles_near_counted(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_touch_filter *filter, const float *d_max_dist2, const uint64_t *d_offsets, rtk_closest_record *d_records, float *d_points_query,
+	float *d_points_scene, uint32_t *d_counts_or_written, rtk_trace_counters *out)
+{
+	if (!out) { rtk_set_error("rtk_dev_triangles_near_counted: NULL counters"); return RTK_AMD_ERR_BAD_ARG; }
+	return rtk_launch_near(ds, d_tris, num_queries, nullptr, filter, d_max_dist2, d_counts_or_written, d_offsets, d_records, d_points_query,
+		d_points_scene, d_offsets != nullptr, nullptr, out);
+}
+
 extern "C" int rtk_dev_trace_rays_count(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
 	uint32_t *d_counts, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream)
 {

@@ -351,6 +351,11 @@ int rtk_launch_touch(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_
 int rtk_launch_pair(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries, const rtk_ray_list *list,
 	const rtk_touch_filter *filter, const float *d_max_dist2, rtk_closest_record *d_records, float *d_points_query, float *d_points_scene,
 	hipStream_t stream, rtk_trace_counters *counted = nullptr);
+// -- rtk_dev_triangles_near_count / rtk_dev_triangles_near_all (rtk_near.hip) --
+// as rtk_launch_within, with the filter (or NULL), the limits (or NULL) and two point arrays (each or NULL)
+int rtk_launch_near(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries, const rtk_ray_list *list,
+	const rtk_touch_filter *filter, const float *d_max_dist2, uint32_t *d_counts, const uint64_t *d_offsets, rtk_closest_record *d_records,
+	float *d_points_query, float *d_points_scene, bool fill, hipStream_t stream, rtk_trace_counters *counted = nullptr);
 // -- the look for an image nobody announced (rtk_detect.hip) --
 int rtk_detect_image(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, hipStream_t stream, uint32_t *w_out, uint32_t *h_out);
 // -- hit records to full hits, and rtk_trace_ray's one-ray launch (rtk_expand.hip) --
