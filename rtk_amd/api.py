@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from .types import (BOX_QUERY_DTYPE, CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, TRI_QUERY_DTYPE, MeshSet, Placement, SceneDesc, SceneHeader,
+from .types import (BOX_QUERY_DTYPE, CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, SPHERE_SWEEP_DTYPE, TRI_QUERY_DTYPE, MeshSet, Placement, SceneDesc, SceneHeader,
                     placement_array)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -187,7 +187,9 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_amd_touch_stack_entries",
                      "rtk_dev_closest_triangles", "rtk_dev_closest_triangles_counted", "rtk_amd_pair_stack_entries",
                      "rtk_dev_triangles_near_count", "rtk_dev_triangles_near_all", "rtk_dev_triangles_near_counted",
-                     "rtk_amd_near_stack_entries"]
+                     "rtk_amd_near_stack_entries",
+                     "rtk_dev_sweep_spheres", "rtk_dev_sweep_spheres_any", "rtk_dev_sweep_spheres_counted",
+                     "rtk_amd_sweep_stack_entries"]
 
 _lib = None
 
@@ -256,6 +258,16 @@ def lib():
     L.rtk_dev_closest_points_counted.restype = C.c_int
     L.rtk_amd_closest_stack_entries.argtypes = []
     L.rtk_amd_closest_stack_entries.restype = C.c_uint32
+    L.rtk_dev_sweep_spheres.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(DevFilter), C.c_void_p]
+    L.rtk_dev_sweep_spheres.restype = C.c_int
+    L.rtk_dev_sweep_spheres_any.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.POINTER(DevFilter), C.c_void_p]
+    L.rtk_dev_sweep_spheres_any.restype = C.c_int
+    L.rtk_dev_sweep_spheres_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter),
+                                                C.POINTER(TraceCounters)]
+    L.rtk_dev_sweep_spheres_counted.restype = C.c_int
+    L.rtk_amd_sweep_stack_entries.argtypes = []
+    L.rtk_amd_sweep_stack_entries.restype = C.c_uint32
     L.rtk_dev_triangles_within_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p]
     L.rtk_dev_triangles_within_count.restype = C.c_int
     L.rtk_dev_triangles_within_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
@@ -710,6 +722,108 @@ class DeviceScene:
         d_rec, d_pts = self.closest_points_device(to_device(q), n)
         _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
         return d_rec.cpu().numpy().view(CLOSEST_RECORD_DTYPE), d_pts.cpu().numpy().view(np.float32).reshape(n, 3)
+
+    # -- sphere sweeps (rtk_dev_sweep_spheres / _any): asynchronous on the current stream, nothing here waits for it --
+
+    def _sweep_filter(self, n, mesh_mask, ignore_prim):
+        """(DevFilter or None, the tensors it points into). mesh_mask: bools per mesh; ignore_prim: a cuda tensor of n 32-bit
+        words (used as it is) or array-like of n ids, one per query slot."""
+        if ignore_prim is not None and hasattr(ignore_prim, "data_ptr"):
+            f, keep = self._device_filter(n, mesh_mask, None, None)
+            if f is None:
+                f = DevFilter()
+                f.struct_size = C.sizeof(DevFilter)
+            f.d_ignore_prim = ignore_prim.data_ptr()
+            return f, keep + [ignore_prim]
+        return self._device_filter(n, mesh_mask, ignore_prim, None)
+
+    def sweep_spheres_device(self, d_sweeps, n, d_records=None, d_points=None, d_centres=None, count=None, ids=None, mesh_mask=None,
+                             ignore_prim=None):
+        """The first contact of each of n moving balls (SPHERE_SWEEP_DTYPE bytes on the device; include/rtk_amd.h, "Sphere
+        sweeps") with the scene: returns (d_records, d_points, d_centres), uint8 cuda tensors of HIT_RECORD_DTYPE records and of 3
+        floats per query each (the contact point on the triangle, the ball's centre at the contact). count / ids: cuda int64
+        tensors naming the queries to answer, as for closest_points_device; slots that are not listed are not written. mesh_mask:
+        bools per mesh; ignore_prim: one id per query slot (a cuda tensor, or array-like)."""
+        torch = _torch()
+        if d_records is None:
+            d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        if d_points is None:
+            d_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        if d_centres is None:
+            d_centres = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        if ids is not None and count is None:
+            raise RtkError("sweep_spheres_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
+        _check(lib().rtk_dev_sweep_spheres(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
+                                           C.c_void_p(d_records.data_ptr()), C.c_void_p(d_points.data_ptr()), C.c_void_p(d_centres.data_ptr()),
+                                           C.byref(f) if f is not None else None, _stream_ptr()), "rtk_dev_sweep_spheres")
+        return d_records, d_points, d_centres
+
+    def sweep_spheres_any_device(self, d_sweeps, n, d_blocked=None, count=None, ids=None, mesh_mask=None, ignore_prim=None):
+        """The any-hit form of sweep_spheres_device: one byte per query, 1 where the path is blocked, in the queries' own slots."""
+        torch = _torch()
+        if d_blocked is None:
+            d_blocked = torch.empty(n, dtype=torch.uint8, device="cuda")
+        if ids is not None and count is None:
+            raise RtkError("sweep_spheres_any_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
+        _check(lib().rtk_dev_sweep_spheres_any(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
+                                               C.c_void_p(d_blocked.data_ptr()), C.byref(f) if f is not None else None, _stream_ptr()),
+               "rtk_dev_sweep_spheres_any")
+        return d_blocked
+
+    def sweep_spheres_counted(self, d_sweeps, n, mesh_mask=None, ignore_prim=None):
+        """sweep_spheres_device of all n queries on the null stream, synchronous, with the visit counts of
+        rtk_dev_sweep_spheres_counted: returns (d_records, d_points, d_centres, counts dict)."""
+        torch = _torch()
+        d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        d_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        d_centres = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        ctr = TraceCounters()
+        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
+        torch.cuda.synchronize()
+        _check(lib().rtk_dev_sweep_spheres_counted(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.c_void_p(d_records.data_ptr()),
+                                                   C.c_void_p(d_points.data_ptr()), C.c_void_p(d_centres.data_ptr()),
+                                                   C.byref(f) if f is not None else None, C.byref(ctr)), "rtk_dev_sweep_spheres_counted")
+        return d_records, d_points, d_centres, ctr.as_dict()
+
+    @staticmethod
+    def _sweep_array(origins, directions, radius, max_t, min_t):
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        s = np.zeros(n, SPHERE_SWEEP_DTYPE)
+        s["origin"] = o
+        s["direction"] = np.broadcast_to(np.asarray(directions, np.float32), (n, 3))
+        s["min_t"] = np.broadcast_to(np.asarray(min_t, np.float32), (n,))
+        s["max_t"] = RTK_INF if max_t is None else np.broadcast_to(np.asarray(max_t, np.float32), (n,))
+        s["radius"] = np.broadcast_to(np.asarray(radius, np.float32), (n,))
+        return s
+
+    def sweep_spheres(self, origins, directions, radius, max_t=None, min_t=0.0, mesh_mask=None, ignore_prim=None):
+        """origins: array-like (n, 3) float32; directions (n, 3) or (3,), not necessarily normalised: t is in their units;
+        radius, max_t, min_t: scalars or one per query; max_t None = no limit (RTK_INF). Returns (records HIT_RECORD_DTYPE,
+        contact points (n, 3) float32, centres at the contact (n, 3) float32): prim == 0xFFFFFFFF is a miss, whose t is max_t and
+        whose two points are the origin."""
+        s = self._sweep_array(origins, directions, radius, max_t, min_t)
+        n = s.shape[0]
+        if n == 0:
+            return np.zeros(0, HIT_RECORD_DTYPE), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
+        d_rec, d_pts, d_ctr = self.sweep_spheres_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return (d_rec.cpu().numpy().view(HIT_RECORD_DTYPE), d_pts.cpu().numpy().view(np.float32).reshape(n, 3),
+                d_ctr.cpu().numpy().view(np.float32).reshape(n, 3))
+
+    def path_blocked(self, origins, directions, radius, max_t=None, min_t=0.0, mesh_mask=None, ignore_prim=None):
+        """The any-hit form of sweep_spheres: a bool array, True where the ball touches the scene somewhere in [min_t, max_t]."""
+        s = self._sweep_array(origins, directions, radius, max_t, min_t)
+        n = s.shape[0]
+        if n == 0:
+            return np.zeros(0, bool)
+        d_blocked = self.sweep_spheres_any_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return d_blocked.cpu().numpy() != 0
 
     # -- triangles within a distance (rtk_dev_triangles_within_count / _all): asynchronous on the current stream --
 

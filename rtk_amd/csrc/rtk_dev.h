@@ -356,6 +356,12 @@ int rtk_launch_pair(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t
 int rtk_launch_near(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries, const rtk_ray_list *list,
 	const rtk_touch_filter *filter, const float *d_max_dist2, uint32_t *d_counts, const uint64_t *d_offsets, rtk_closest_record *d_records,
 	float *d_points_query, float *d_points_scene, bool fill, hipStream_t stream, rtk_trace_counters *counted = nullptr);
+// -- rtk_dev_sweep_spheres / rtk_dev_sweep_spheres_any (rtk_sweep.hip) --
+// the closest form writes d_records (d_points, d_centres: each or NULL), the any-hit form d_blocked; a non-null `counted` makes
+// it the counting form of the closest one
+int rtk_launch_sweep(const rtk_dev_scene *ds, const rtk_sphere_sweep *d_sweeps, size_t num_sweeps, const rtk_ray_list *list,
+	rtk_hit_record *d_records, float *d_points, float *d_centres, uint8_t *d_blocked, bool any_hit, const rtk_dev_filter *filter,
+	hipStream_t stream, rtk_trace_counters *counted = nullptr);
 // -- the look for an image nobody announced (rtk_detect.hip) --
 int rtk_detect_image(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, hipStream_t stream, uint32_t *w_out, uint32_t *h_out);
 // -- hit records to full hits, and rtk_trace_ray's one-ray launch (rtk_expand.hip) --

@@ -25,5 +25,8 @@ static_assert(sizeof(rtk_dev_split_info) == 48 && offsetof(rtk_dev_split_info, l
 static_assert(sizeof(rtk_placement) == 48 && offsetof(rtk_placement, m) == 0, "rtk_placement");
 static_assert(sizeof(rtk_point_query) == 16 && offsetof(rtk_point_query, max_dist2) == 12, "rtk_point_query");
 static_assert(sizeof(rtk_closest_record) == 16 && offsetof(rtk_closest_record, prim) == 12, "rtk_closest_record");
+static_assert(sizeof(rtk_sphere_sweep) == 36 && offsetof(rtk_sphere_sweep, direction) == 12 && offsetof(rtk_sphere_sweep, min_t) == 24 &&
+	offsetof(rtk_sphere_sweep, radius) == 32, "rtk_sphere_sweep");
+static_assert(sizeof(rtk_dev_filter) == 32 && offsetof(rtk_dev_filter, d_ignore_prim) == 16 && offsetof(rtk_dev_filter, d_after) == 24, "rtk_dev_filter");
 static_assert(sizeof(rtk_dev_rebuild_info) == 40 && offsetof(rtk_dev_rebuild_info, nodes_before) == 8 && offsetof(rtk_dev_rebuild_info, max_depth_before) == 24 &&
 	offsetof(rtk_dev_rebuild_info, rebuild_ms) == 32, "rtk_dev_rebuild_info");

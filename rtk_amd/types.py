@@ -26,7 +26,10 @@ CLOSEST_RECORD_DTYPE = np.dtype([("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), (
 BOX_QUERY_DTYPE = np.dtype([("lo", "<f4", (3,)), ("hi", "<f4", (3,))])
 # rtk_tri_query of include/rtk_amd.h (rtk_dev_triangles_touching_count / _all): a float32 [n, 9] array is one
 TRI_QUERY_DTYPE = np.dtype([("v0", "<f4", (3,)), ("v1", "<f4", (3,)), ("v2", "<f4", (3,))])
+# rtk_sphere_sweep of include/rtk_amd.h (rtk_dev_sweep_spheres): a float32 [n, 9] array is one; its record is HIT_RECORD_DTYPE
+SPHERE_SWEEP_DTYPE = np.dtype([("origin", "<f4", (3,)), ("direction", "<f4", (3,)), ("min_t", "<f4"), ("max_t", "<f4"), ("radius", "<f4")])
 
+assert SPHERE_SWEEP_DTYPE.itemsize == 36
 assert POINT_QUERY_DTYPE.itemsize == 16 and CLOSEST_RECORD_DTYPE.itemsize == 16 and BOX_QUERY_DTYPE.itemsize == 24
 assert TRI_QUERY_DTYPE.itemsize == 36
 assert VERTEX_DTYPE.itemsize == 16 and RAY_DTYPE.itemsize == 32
