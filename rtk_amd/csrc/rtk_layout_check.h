@@ -27,6 +27,8 @@ static_assert(sizeof(rtk_point_query) == 16 && offsetof(rtk_point_query, max_dis
 static_assert(sizeof(rtk_closest_record) == 16 && offsetof(rtk_closest_record, prim) == 12, "rtk_closest_record");
 static_assert(sizeof(rtk_sphere_sweep) == 36 && offsetof(rtk_sphere_sweep, direction) == 12 && offsetof(rtk_sphere_sweep, min_t) == 24 &&
 	offsetof(rtk_sphere_sweep, radius) == 32, "rtk_sphere_sweep");
+static_assert(sizeof(rtk_box_sweep) == 44 && offsetof(rtk_box_sweep, direction) == 12 && offsetof(rtk_box_sweep, min_t) == 24 &&
+	offsetof(rtk_box_sweep, half) == 32, "rtk_box_sweep");
 static_assert(sizeof(rtk_dev_filter) == 32 && offsetof(rtk_dev_filter, d_ignore_prim) == 16 && offsetof(rtk_dev_filter, d_after) == 24, "rtk_dev_filter");
 static_assert(sizeof(rtk_dev_rebuild_info) == 40 && offsetof(rtk_dev_rebuild_info, nodes_before) == 8 && offsetof(rtk_dev_rebuild_info, max_depth_before) == 24 &&
 	offsetof(rtk_dev_rebuild_info, rebuild_ms) == 32, "rtk_dev_rebuild_info");
