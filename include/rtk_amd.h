@@ -956,6 +956,72 @@ int rtk_dev_sweep_boxes_counted(const rtk_dev_scene *ds, const rtk_box_sweep *d_
 /* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
 uint32_t rtk_amd_boxsweep_stack_entries(void);
 
+/* ---- Capsule sweeps: how far a capsule (a segment with a radius) can move along a direction before it first touches the scene ----
+ * The shape a character or camera controller sweeps, a thick limb, a cable segment, a tool shaft. Neither other sweep stands in
+ * for it: a ball of the capsule's radius tunnels with the body's ends, a ball that encloses it gets stuck in every doorway, and
+ * the axis-aligned box cannot lean; marching rtk_dev_triangles_near_count along the path costs one walk per step and only
+ * brackets the time. The scene is read as it stands -- a device build, an uploaded blob, after any refit, split or rebuild --
+ * and no bit of it changes.
+ *
+ * A query is a rtk_capsule_sweep: the capsule at time t is every point within `radius` of the segment from c(t) - half_axis to
+ * c(t) + half_axis, with the centre c(t) = origin + direction * t, t in units of `direction` (which need not be normalised)
+ * over the CLOSED interval [min_t, max_t] -- not a ray's open one: a capsule that already touches a triangle at min_t is a hit
+ * at the start, and no time outside [min_t, max_t] is ever reported. The capsule does not rotate; its axis may point anywhere.
+ * A torch float32 [n, 12] tensor is an array of them.
+ *
+ * THE RULE (rtk_amd/csrc/rtk_capsule_rule.h; INTEGRATION.md "Capsule sweeps"): THE RESULT DOES NOT DEPEND ON THE TREE. It is a
+ * function of the scene's triangle records, the filter and the query alone, stated in float arithmetic, every operation rounded
+ * on its own. Every triangle has a time or none: none if the path of the centre misses the triangle's own box grown by
+ * radius + |half_axis[k]| on axis k; the entry into that box if the capsule at the start is within `radius` of the triangle
+ * (its axis going through the triangle, or the smallest of five distances: the axis's two ends against the triangle and the
+ * axis against the three edges); otherwise the smallest valid entry time of a ball of that radius into the 26 features of the
+ * prism the triangle sweeps out along +-half_axis -- eight faces, twelve edges, six vertices, the first in the rule's order
+ * among equal times --, measured from the centre at the entry into the grown box, never earlier than that entry, and none if
+ * it exceeds max_t. The answer is the smallest time, THE LOWEST PRIMITIVE ID AMONG EQUAL TIMES, or a miss. Leaf sizes, loose
+ * boxes and the node format only decide how many triangles are never looked at.
+ *   hit    t, u (weight of vertex 0), v (weight of vertex 1) and the global primitive id: a rtk_hit_record, which
+ *          rtk_dev_select_rays and rtk_dev_expand_hits take as it is. ONE evaluation of the rule's distance walk at c(t) on the
+ *          answer's triangle gives u, v and both points: d_points[3 i ..] = the point of the triangle nearest the capsule's
+ *          segment at that time, d_axis_points[3 i ..] = the point of the capsule's segment nearest the triangle. A
+ *          controller's contact normal is their difference (of length `radius` up to rounding at a first contact; zero where
+ *          the axis itself goes through the triangle, where both are the point of crossing).
+ *   miss   t = max_t as given, u = v = 0, prim = RTK_PRIM_NONE; d_points[3 i ..] = d_axis_points[3 i ..] = the origin as given
+ * A query is live iff all twelve floats are finite (RTK_INF is a finite number: "no limit"), the direction is not all zeros,
+ * radius >= 0 and min_t <= max_t; a query that is not live is a miss, and so is every query of a scene without triangles.
+ * half_axis == 0 is legal and is a ball; radius == 0 is legal and is a moving segment; both at once is a point, on which the
+ * rule is NOT rtk's watertight ray test, and its results are not bit-equal to a trace's. half_axis == 0 IS NOT PROMISED
+ * BIT-EQUAL TO rtk_dev_sweep_spheres: the start test is a different float expression (the times from features are the same).
+ * THE FILTER is part of the rule: of a rtk_dev_filter, d_mesh_mask (with mesh_mask_bits) and d_ignore_prim (read per query slot)
+ * say which triangles are candidates, as for the filtered traces; a non-NULL d_after is refused. `filter` may be NULL.
+ * rtk_dev_sweep_capsules_any answers "is the path blocked": d_blocked[i] = 1 if query i has a candidate with a time, else 0 --
+ * exactly prim != RTK_PRIM_NONE of rtk_dev_sweep_capsules; its walk ends at the first one it meets.
+ * `list` may be NULL: all num_sweeps queries are answered. Otherwise the words of the listed traces hold: m = min(*d_count,
+ * num_sweeps) entries are answered, the result of query r goes to slot r of the outputs, d_ignore_prim is read at slot r, A SLOT
+ * THAT IS NOT LISTED IS NOT WRITTEN, an id may repeat, and the count is read when the work reaches it on `stream`. d_points and
+ * d_axis_points may each be NULL.
+ * Asynchronous on `stream`: no host wait, nothing read back. The scene is only read, so the thread-safety rules of the batches
+ * hold; the part of the walk's stack that does not fit on chip lives in the per-(scene, stream) scratch set, and a dropped push
+ * (impossible for a tree) is reported by rtk_dev_trace_status like a trace's. Nothing it allocates counts toward the scene.
+ * Refused before anything is launched, RTK_AMD_ERR_BAD_ARG: a NULL scene; NULL d_sweeps or a NULL d_records / d_blocked with
+ * num_sweeps != 0; a bad list (as for the listed traces); a filter whose struct_size is too small, whose d_after is set or whose
+ * mesh mask has no bits; num_sweeps >= 2^32; a calling thread whose current device is not the scene's. num_sweeps == 0 is
+ * RTK_AMD_OK with nothing launched. Works as it is on rtk_mgpu_scene(m, i).
+ * A scene with non-finite vertex coordinates: the call terminates and writes only inside its outputs; NOTHING ELSE IS PROMISED
+ * about its results. */
+typedef struct rtk_capsule_sweep { float origin[3], direction[3], min_t, max_t, radius, half_axis[3]; } rtk_capsule_sweep;   /* 48 bytes; a float32 [n, 12] tensor */
+int rtk_dev_sweep_capsules(const rtk_dev_scene *ds, const rtk_capsule_sweep *d_sweeps, size_t num_sweeps, const rtk_ray_list *list,
+	rtk_hit_record *d_records, float *d_points /* may be NULL */, float *d_axis_points /* may be NULL */,
+	const rtk_dev_filter *filter /* may be NULL */, void *stream);
+int rtk_dev_sweep_capsules_any(const rtk_dev_scene *ds, const rtk_capsule_sweep *d_sweeps, size_t num_sweeps, const rtk_ray_list *list,
+	uint8_t *d_blocked, const rtk_dev_filter *filter, void *stream);
+/* Same result as rtk_dev_sweep_capsules without a list, plus visit counts in the fields of rtk_dev_closest_points_counted (rays =
+ * queries answered; triangles = records fetched, of which those the filter rules out are not evaluated; hits = queries that
+ * found a triangle). Null stream, synchronous; not for timing. */
+int rtk_dev_sweep_capsules_counted(const rtk_dev_scene *ds, const rtk_capsule_sweep *d_sweeps, size_t num_sweeps,
+	rtk_hit_record *d_records, float *d_points, float *d_axis_points, const rtk_dev_filter *filter, rtk_trace_counters *out);
+/* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
+uint32_t rtk_amd_capsule_stack_entries(void);
+
 /* ---- Every hit along a ray: how many triangles a ray crosses, and all of them (or the k closest) in one walk ----
  * What transparency and alpha compositing, thickness and x-ray depth, visibility through several occluders and point-in-mesh by
  * crossing parity ask. Until now the only route was the d_after loop of rtk_dev_trace_rays_filtered: one complete closest-hit

@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from .types import (BOX_QUERY_DTYPE, BOX_SWEEP_DTYPE, CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, SPHERE_SWEEP_DTYPE, TRI_QUERY_DTYPE, MeshSet, Placement, SceneDesc, SceneHeader,
+from .types import (BOX_QUERY_DTYPE, BOX_SWEEP_DTYPE, CAPSULE_SWEEP_DTYPE, CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, SPHERE_SWEEP_DTYPE, TRI_QUERY_DTYPE, MeshSet, Placement, SceneDesc, SceneHeader,
                     placement_array)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -190,7 +190,8 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_amd_near_stack_entries",
                      "rtk_dev_sweep_spheres", "rtk_dev_sweep_spheres_any", "rtk_dev_sweep_spheres_counted",
                      "rtk_amd_sweep_stack_entries",
-                     "rtk_dev_sweep_boxes", "rtk_dev_sweep_boxes_any", "rtk_dev_sweep_boxes_counted", "rtk_amd_boxsweep_stack_entries"]
+                     "rtk_dev_sweep_boxes", "rtk_dev_sweep_boxes_any", "rtk_dev_sweep_boxes_counted", "rtk_amd_boxsweep_stack_entries",
+                     "rtk_dev_sweep_capsules", "rtk_dev_sweep_capsules_any", "rtk_dev_sweep_capsules_counted", "rtk_amd_capsule_stack_entries"]
 
 _lib = None
 
@@ -279,6 +280,16 @@ def lib():
     L.rtk_dev_sweep_boxes_counted.restype = C.c_int
     L.rtk_amd_boxsweep_stack_entries.argtypes = []
     L.rtk_amd_boxsweep_stack_entries.restype = C.c_uint32
+    L.rtk_dev_sweep_capsules.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(DevFilter), C.c_void_p]
+    L.rtk_dev_sweep_capsules.restype = C.c_int
+    L.rtk_dev_sweep_capsules_any.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.POINTER(DevFilter), C.c_void_p]
+    L.rtk_dev_sweep_capsules_any.restype = C.c_int
+    L.rtk_dev_sweep_capsules_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter),
+                                                 C.POINTER(TraceCounters)]
+    L.rtk_dev_sweep_capsules_counted.restype = C.c_int
+    L.rtk_amd_capsule_stack_entries.argtypes = []
+    L.rtk_amd_capsule_stack_entries.restype = C.c_uint32
     L.rtk_dev_triangles_within_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p]
     L.rtk_dev_triangles_within_count.restype = C.c_int
     L.rtk_dev_triangles_within_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
@@ -923,6 +934,99 @@ class DeviceScene:
         if n == 0:
             return np.zeros(0, bool)
         d_blocked = self.sweep_boxes_any_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return d_blocked.cpu().numpy() != 0
+
+    # -- capsule sweeps (rtk_dev_sweep_capsules / _any): asynchronous on the current stream, nothing here waits for it --
+
+    def sweep_capsules_device(self, d_sweeps, n, d_records=None, d_points=None, d_axis_points=None, count=None, ids=None, mesh_mask=None,
+                              ignore_prim=None):
+        """The first contact of each of n moving capsules (CAPSULE_SWEEP_DTYPE bytes on the device; include/rtk_amd.h, "Capsule
+        sweeps") with the scene: returns (d_records, d_points, d_axis_points), uint8 cuda tensors of HIT_RECORD_DTYPE records and of
+        3 floats per query each (the point of the triangle nearest the capsule's segment at the contact, the point of that segment
+        nearest the triangle). count / ids: cuda int64 tensors naming the queries to answer, as for closest_points_device; slots
+        that are not listed are not written. mesh_mask: bools per mesh; ignore_prim: one id per query slot (a cuda tensor, or
+        array-like)."""
+        torch = _torch()
+        if d_records is None:
+            d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        if d_points is None:
+            d_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        if d_axis_points is None:
+            d_axis_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        if ids is not None and count is None:
+            raise RtkError("sweep_capsules_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
+        _check(lib().rtk_dev_sweep_capsules(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
+                                            C.c_void_p(d_records.data_ptr()), C.c_void_p(d_points.data_ptr()), C.c_void_p(d_axis_points.data_ptr()),
+                                            C.byref(f) if f is not None else None, _stream_ptr()), "rtk_dev_sweep_capsules")
+        return d_records, d_points, d_axis_points
+
+    def sweep_capsules_any_device(self, d_sweeps, n, d_blocked=None, count=None, ids=None, mesh_mask=None, ignore_prim=None):
+        """The any-hit form of sweep_capsules_device: one byte per query, 1 where the path is blocked, in the queries' own slots."""
+        torch = _torch()
+        if d_blocked is None:
+            d_blocked = torch.empty(n, dtype=torch.uint8, device="cuda")
+        if ids is not None and count is None:
+            raise RtkError("sweep_capsules_any_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
+        _check(lib().rtk_dev_sweep_capsules_any(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                C.c_void_p(d_blocked.data_ptr()), C.byref(f) if f is not None else None, _stream_ptr()),
+               "rtk_dev_sweep_capsules_any")
+        return d_blocked
+
+    def sweep_capsules_counted(self, d_sweeps, n, mesh_mask=None, ignore_prim=None):
+        """sweep_capsules_device of all n queries on the null stream, synchronous, with the visit counts of
+        rtk_dev_sweep_capsules_counted: returns (d_records, d_points, d_axis_points, counts dict)."""
+        torch = _torch()
+        d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        d_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        d_axis_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        ctr = TraceCounters()
+        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
+        torch.cuda.synchronize()
+        _check(lib().rtk_dev_sweep_capsules_counted(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.c_void_p(d_records.data_ptr()),
+                                                    C.c_void_p(d_points.data_ptr()), C.c_void_p(d_axis_points.data_ptr()),
+                                                    C.byref(f) if f is not None else None, C.byref(ctr)), "rtk_dev_sweep_capsules_counted")
+        return d_records, d_points, d_axis_points, ctr.as_dict()
+
+    @staticmethod
+    def _capsule_sweep_array(origins, directions, radius, half_axis, max_t, min_t):
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        s = np.zeros(n, CAPSULE_SWEEP_DTYPE)
+        s["origin"] = o
+        s["direction"] = np.broadcast_to(np.asarray(directions, np.float32), (n, 3))
+        s["min_t"] = np.broadcast_to(np.asarray(min_t, np.float32), (n,))
+        s["max_t"] = RTK_INF if max_t is None else np.broadcast_to(np.asarray(max_t, np.float32), (n,))
+        s["radius"] = np.broadcast_to(np.asarray(radius, np.float32), (n,))
+        s["half_axis"] = np.broadcast_to(np.asarray(half_axis, np.float32), (n, 3))
+        return s
+
+    def sweep_capsules(self, origins, directions, radius, half_axis, max_t=None, min_t=0.0, mesh_mask=None, ignore_prim=None):
+        """origins: array-like (n, 3) float32; directions (n, 3) or (3,), not necessarily normalised: t is in their units; radius: a
+        scalar or one per query; half_axis: (n, 3) or (3,), from the capsule's centre to one end of its segment; max_t, min_t:
+        scalars or one per query; max_t None = no limit (RTK_INF). Returns (records HIT_RECORD_DTYPE, the points of the triangles
+        nearest the capsule's segment at the contact (n, 3) float32, the points of that segment nearest the triangle (n, 3)
+        float32): prim == 0xFFFFFFFF is a miss, whose t is max_t and whose two points are the origin."""
+        s = self._capsule_sweep_array(origins, directions, radius, half_axis, max_t, min_t)
+        n = s.shape[0]
+        if n == 0:
+            return np.zeros(0, HIT_RECORD_DTYPE), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
+        d_rec, d_pts, d_axs = self.sweep_capsules_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return (d_rec.cpu().numpy().view(HIT_RECORD_DTYPE), d_pts.cpu().numpy().view(np.float32).reshape(n, 3),
+                d_axs.cpu().numpy().view(np.float32).reshape(n, 3))
+
+    def capsule_path_blocked(self, origins, directions, radius, half_axis, max_t=None, min_t=0.0, mesh_mask=None, ignore_prim=None):
+        """The any-hit form of sweep_capsules: a bool array, True where the capsule touches the scene somewhere in [min_t, max_t]."""
+        s = self._capsule_sweep_array(origins, directions, radius, half_axis, max_t, min_t)
+        n = s.shape[0]
+        if n == 0:
+            return np.zeros(0, bool)
+        d_blocked = self.sweep_capsules_any_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
         _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
         return d_blocked.cpu().numpy() != 0
 

@@ -33,6 +33,10 @@ assert SPHERE_SWEEP_DTYPE.itemsize == 36
 # rtk_box_sweep (rtk_dev_sweep_boxes): a float32 [n, 11] array is one; its record is HIT_RECORD_DTYPE
 BOX_SWEEP_DTYPE = np.dtype([("origin", "<f4", (3,)), ("direction", "<f4", (3,)), ("min_t", "<f4"), ("max_t", "<f4"), ("half", "<f4", (3,))])
 assert BOX_SWEEP_DTYPE.itemsize == 44
+# rtk_capsule_sweep (rtk_dev_sweep_capsules): a float32 [n, 12] array is one; its record is HIT_RECORD_DTYPE
+CAPSULE_SWEEP_DTYPE = np.dtype([("origin", "<f4", (3,)), ("direction", "<f4", (3,)), ("min_t", "<f4"), ("max_t", "<f4"), ("radius", "<f4"),
+                                ("half_axis", "<f4", (3,))])
+assert CAPSULE_SWEEP_DTYPE.itemsize == 48
 assert POINT_QUERY_DTYPE.itemsize == 16 and CLOSEST_RECORD_DTYPE.itemsize == 16 and BOX_QUERY_DTYPE.itemsize == 24
 assert TRI_QUERY_DTYPE.itemsize == 36
 assert VERTEX_DTYPE.itemsize == 16 and RAY_DTYPE.itemsize == 32
