@@ -901,8 +901,8 @@ uint32_t rtk_amd_sweep_stack_entries(void);
  * A query is a rtk_box_sweep: the box at time t is [c(t) - half, c(t) + half] with the centre c(t) = origin + direction * t, t
  * in units of `direction` (which need not be normalised) over the CLOSED interval [min_t, max_t] -- not a ray's open one: a box
  * that already overlaps a triangle at min_t is a hit at the start, and no time outside [min_t, max_t] is ever reported. A torch
- * float32 [n, 11] tensor is an array of them. The box keeps the scene's axes: an oriented box is not offered (flatten the
- * rotation into the scene with placed meshes).
+ * float32 [n, 11] tensor is an array of them. The box keeps the scene's axes: a box with axes of its own is
+ * rtk_dev_sweep_obbs, "Oriented box sweeps" below.
  *
  * THE RULE (rtk_amd/csrc/rtk_boxsweep_rule.h; INTEGRATION.md "Box sweeps"): THE RESULT DOES NOT DEPEND ON THE TREE. It is a
  * function of the scene's triangle records, the filter and the query alone, stated in float arithmetic, every operation rounded
@@ -1021,6 +1021,75 @@ int rtk_dev_sweep_capsules_counted(const rtk_dev_scene *ds, const rtk_capsule_sw
 	rtk_hit_record *d_records, float *d_points, float *d_axis_points, const rtk_dev_filter *filter, rtk_trace_counters *out);
 /* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
 uint32_t rtk_amd_capsule_stack_entries(void);
+
+/* ---- Oriented box sweeps: how far a box with axes of its own can move along a direction before it first touches the scene ----
+ * A rigid body's hull, a vehicle chassis, a crate on a ramp, a rotated camera volume: a box that does not keep the scene's axes.
+ * rtk_dev_sweep_boxes cannot lean, and turning the scene instead (placed meshes and a refit) costs one pass over the whole scene
+ * per orientation; here every query of a batch carries its own rotation. The box does not turn while it moves. The scene is
+ * read as it stands -- a device build, an uploaded blob, after any refit, split or rebuild -- and no bit of it changes.
+ *
+ * A query is a rtk_obb_sweep: `axes` holds three rows u0, u1, u2, the box's own axes in scene coordinates (the rows of a rotation
+ * matrix that takes scene coordinates to the box's), and the box at time t is { c(t) + a0 * u0 + a1 * u1 + a2 * u2 :
+ * |aj| <= half[j] } with the centre c(t) = origin + direction * t, t in units of `direction` (which need not be normalised) over
+ * the CLOSED interval [min_t, max_t] -- not a ray's open one: a box that already overlaps a triangle at min_t is a hit at the
+ * start, and no time outside [min_t, max_t] is ever reported. A torch float32 [n, 20] tensor is an array of them.
+ *
+ * THE RULE (rtk_amd/csrc/rtk_obbsweep_rule.h; INTEGRATION.md "Oriented box sweeps"): THE RESULT DOES NOT DEPEND ON THE TREE. It is
+ * a function of the scene's triangle records, the filter and the query alone, stated in float arithmetic, every operation
+ * rounded on its own. Every triangle has a time or none, by swept separating axes: none if the path of the centre misses the
+ * triangle's own box grown on scene axis k by the box's reach along it, |u0[k]| * half[0] + |u1[k]| * half[1] + |u2[k]| * half[2];
+ * otherwise the triangle is measured from the centre at the entry into that grown box and taken into the box's frame (three
+ * dots per vertex), where the box is axis-aligned, and thirteen axes -- the box's three, the triangle's normal and the nine
+ * cross products of an edge and a box axis -- each give an interval of times at which they do not separate the two; the time
+ * is the start of the intersection of all of them, none if it is empty, never earlier than the entry into the grown box, and
+ * none if it exceeds max_t. The answer is the smallest time, THE LOWEST PRIMITIVE ID AMONG EQUAL TIMES, or a miss. Leaf sizes,
+ * loose boxes and the node format only decide how many triangles are never looked at. With the unit vectors as axes the
+ * answers are rtk_dev_sweep_boxes' UP TO ROUNDING, NOT BIT FOR BIT.
+ *   hit    t, u (weight of vertex 0), v (weight of vertex 1) and the global primitive id: a rtk_hit_record, which
+ *          rtk_dev_select_rays and rtk_dev_expand_hits take as it is. u and v are those of the point of the triangle nearest to
+ *          the centre c(t) (one rtk_closest_rule.h evaluation): A WITNESS ON THE TRIANGLE, NOT NECESSARILY A POINT OF CONTACT.
+ *          d_centres[3 i ..] = c(t) as the rule computed it; d_normals[3 i ..] = the unit separating axis that gave the time, in
+ *          scene coordinates, turned against the motion (dot(normal, direction) < 0): the contact normal a controller slides
+ *          along. It is all zeros where the box already overlaps at the start (t == min_t), or where the axis has no length in
+ *          float; it is never a NaN for a live query and a finite scene.
+ *   miss   t = max_t as given, u = v = 0, prim = RTK_PRIM_NONE; d_centres[3 i ..] = the origin as given, d_normals[3 i ..] = 0
+ * A query is live iff all twenty floats are finite (RTK_INF is a finite number: "no limit"), the direction is not all zeros,
+ * every half[j] >= 0, min_t <= max_t and THE AXES ARE ORTHONORMAL TO WITHIN 2^-10: |dot(uj, uj) - 1| <= 2^-10 for each axis and
+ * |dot(ui, uj)| <= 2^-10 for each pair, in float. That gate keeps garbage out and is no accuracy claim: rows rounded from a
+ * float64 rotation or made from a float32 unit quaternion pass with room to spare; scaled, sheared or zero axes do not. Within
+ * the gate the axes are used as given. A query that is not live is a miss, and so is every query of a scene without triangles.
+ * half == 0 on one, two or all three axes is legal: a rectangle, a segment and a point are boxes; on a point the rule is NOT
+ * rtk's watertight ray test, and its results are not bit-equal to a trace's.
+ * THE FILTER is part of the rule: of a rtk_dev_filter, d_mesh_mask (with mesh_mask_bits) and d_ignore_prim (read per query slot)
+ * say which triangles are candidates, as for the filtered traces; a non-NULL d_after is refused. `filter` may be NULL.
+ * rtk_dev_sweep_obbs_any answers "is the path blocked": d_blocked[i] = 1 if query i has a candidate with a time, else 0 --
+ * exactly prim != RTK_PRIM_NONE of rtk_dev_sweep_obbs; its walk ends at the first one it meets.
+ * `list` may be NULL: all num_sweeps queries are answered. Otherwise the words of the listed traces hold: m = min(*d_count,
+ * num_sweeps) entries are answered, the result of query r goes to slot r of the outputs, d_ignore_prim is read at slot r, A SLOT
+ * THAT IS NOT LISTED IS NOT WRITTEN, an id may repeat, and the count is read when the work reaches it on `stream`. d_centres and
+ * d_normals may each be NULL.
+ * Asynchronous on `stream`: no host wait, nothing read back. The scene is only read, so the thread-safety rules of the batches
+ * hold; the part of the walk's stack that does not fit on chip lives in the per-(scene, stream) scratch set, and a dropped push
+ * (impossible for a tree) is reported by rtk_dev_trace_status like a trace's. Nothing it allocates counts toward the scene.
+ * Refused before anything is launched, RTK_AMD_ERR_BAD_ARG: a NULL scene; NULL d_sweeps or a NULL d_records / d_blocked with
+ * num_sweeps != 0; a bad list (as for the listed traces); a filter whose struct_size is too small, whose d_after is set or whose
+ * mesh mask has no bits; num_sweeps >= 2^32; a calling thread whose current device is not the scene's. num_sweeps == 0 is
+ * RTK_AMD_OK with nothing launched. Works as it is on rtk_mgpu_scene(m, i).
+ * A scene with non-finite vertex coordinates: the call terminates and writes only inside its outputs; NOTHING ELSE IS PROMISED
+ * about its results. */
+typedef struct rtk_obb_sweep { float origin[3], direction[3], min_t, max_t, half[3], axes[9]; } rtk_obb_sweep;   /* 80 bytes; a float32 [n, 20] tensor */
+int rtk_dev_sweep_obbs(const rtk_dev_scene *ds, const rtk_obb_sweep *d_sweeps, size_t num_sweeps, const rtk_ray_list *list,
+	rtk_hit_record *d_records, float *d_centres /* may be NULL */, float *d_normals /* may be NULL */,
+	const rtk_dev_filter *filter /* may be NULL */, void *stream);
+int rtk_dev_sweep_obbs_any(const rtk_dev_scene *ds, const rtk_obb_sweep *d_sweeps, size_t num_sweeps, const rtk_ray_list *list,
+	uint8_t *d_blocked, const rtk_dev_filter *filter, void *stream);
+/* Same result as rtk_dev_sweep_obbs without a list, plus visit counts in the fields of rtk_dev_closest_points_counted (rays =
+ * queries answered; triangles = records fetched, of which those the filter rules out are not evaluated; hits = queries that
+ * found a triangle). Null stream, synchronous; not for timing. */
+int rtk_dev_sweep_obbs_counted(const rtk_dev_scene *ds, const rtk_obb_sweep *d_sweeps, size_t num_sweeps,
+	rtk_hit_record *d_records, float *d_centres, float *d_normals, const rtk_dev_filter *filter, rtk_trace_counters *out);
+/* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
+uint32_t rtk_amd_obbsweep_stack_entries(void);
 
 /* ---- Every hit along a ray: how many triangles a ray crosses, and all of them (or the k closest) in one walk ----
  * What transparency and alpha compositing, thickness and x-ray depth, visibility through several occluders and point-in-mesh by

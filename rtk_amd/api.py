@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from .types import (BOX_QUERY_DTYPE, BOX_SWEEP_DTYPE, CAPSULE_SWEEP_DTYPE, CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, SPHERE_SWEEP_DTYPE, TRI_QUERY_DTYPE, MeshSet, Placement, SceneDesc, SceneHeader,
+from .types import (BOX_QUERY_DTYPE, BOX_SWEEP_DTYPE, CAPSULE_SWEEP_DTYPE, CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, OBB_SWEEP_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, SPHERE_SWEEP_DTYPE, TRI_QUERY_DTYPE, MeshSet, Placement, SceneDesc, SceneHeader,
                     placement_array)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -191,7 +191,8 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_dev_sweep_spheres", "rtk_dev_sweep_spheres_any", "rtk_dev_sweep_spheres_counted",
                      "rtk_amd_sweep_stack_entries",
                      "rtk_dev_sweep_boxes", "rtk_dev_sweep_boxes_any", "rtk_dev_sweep_boxes_counted", "rtk_amd_boxsweep_stack_entries",
-                     "rtk_dev_sweep_capsules", "rtk_dev_sweep_capsules_any", "rtk_dev_sweep_capsules_counted", "rtk_amd_capsule_stack_entries"]
+                     "rtk_dev_sweep_capsules", "rtk_dev_sweep_capsules_any", "rtk_dev_sweep_capsules_counted", "rtk_amd_capsule_stack_entries",
+                     "rtk_dev_sweep_obbs", "rtk_dev_sweep_obbs_any", "rtk_dev_sweep_obbs_counted", "rtk_amd_obbsweep_stack_entries"]
 
 _lib = None
 
@@ -290,6 +291,16 @@ def lib():
     L.rtk_dev_sweep_capsules_counted.restype = C.c_int
     L.rtk_amd_capsule_stack_entries.argtypes = []
     L.rtk_amd_capsule_stack_entries.restype = C.c_uint32
+    L.rtk_dev_sweep_obbs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(DevFilter), C.c_void_p]
+    L.rtk_dev_sweep_obbs.restype = C.c_int
+    L.rtk_dev_sweep_obbs_any.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.POINTER(DevFilter), C.c_void_p]
+    L.rtk_dev_sweep_obbs_any.restype = C.c_int
+    L.rtk_dev_sweep_obbs_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter),
+                                             C.POINTER(TraceCounters)]
+    L.rtk_dev_sweep_obbs_counted.restype = C.c_int
+    L.rtk_amd_obbsweep_stack_entries.argtypes = []
+    L.rtk_amd_obbsweep_stack_entries.restype = C.c_uint32
     L.rtk_dev_triangles_within_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p]
     L.rtk_dev_triangles_within_count.restype = C.c_int
     L.rtk_dev_triangles_within_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1027,6 +1038,99 @@ class DeviceScene:
         if n == 0:
             return np.zeros(0, bool)
         d_blocked = self.sweep_capsules_any_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return d_blocked.cpu().numpy() != 0
+
+    # -- oriented box sweeps (rtk_dev_sweep_obbs / _any): asynchronous on the current stream, nothing here waits for it --
+
+    def sweep_obbs_device(self, d_sweeps, n, d_records=None, d_centres=None, d_normals=None, count=None, ids=None, mesh_mask=None,
+                          ignore_prim=None):
+        """The first contact of each of n moving oriented boxes (OBB_SWEEP_DTYPE bytes on the device; include/rtk_amd.h, "Oriented
+        box sweeps") with the scene: returns (d_records, d_centres, d_normals), uint8 cuda tensors of HIT_RECORD_DTYPE records and
+        of 3 floats per query each (the box's centre at the contact, the contact normal against the motion). count / ids: cuda
+        int64 tensors naming the queries to answer, as for closest_points_device; slots that are not listed are not written.
+        mesh_mask: bools per mesh; ignore_prim: one id per query slot (a cuda tensor, or array-like)."""
+        torch = _torch()
+        if d_records is None:
+            d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        if d_centres is None:
+            d_centres = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        if d_normals is None:
+            d_normals = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        if ids is not None and count is None:
+            raise RtkError("sweep_obbs_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
+        _check(lib().rtk_dev_sweep_obbs(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
+                                        C.c_void_p(d_records.data_ptr()), C.c_void_p(d_centres.data_ptr()), C.c_void_p(d_normals.data_ptr()),
+                                        C.byref(f) if f is not None else None, _stream_ptr()), "rtk_dev_sweep_obbs")
+        return d_records, d_centres, d_normals
+
+    def sweep_obbs_any_device(self, d_sweeps, n, d_blocked=None, count=None, ids=None, mesh_mask=None, ignore_prim=None):
+        """The any-hit form of sweep_obbs_device: one byte per query, 1 where the path is blocked, in the queries' own slots."""
+        torch = _torch()
+        if d_blocked is None:
+            d_blocked = torch.empty(n, dtype=torch.uint8, device="cuda")
+        if ids is not None and count is None:
+            raise RtkError("sweep_obbs_any_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
+        _check(lib().rtk_dev_sweep_obbs_any(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
+                                            C.c_void_p(d_blocked.data_ptr()), C.byref(f) if f is not None else None, _stream_ptr()),
+               "rtk_dev_sweep_obbs_any")
+        return d_blocked
+
+    def sweep_obbs_counted(self, d_sweeps, n, mesh_mask=None, ignore_prim=None):
+        """sweep_obbs_device of all n queries on the null stream, synchronous, with the visit counts of
+        rtk_dev_sweep_obbs_counted: returns (d_records, d_centres, d_normals, counts dict)."""
+        torch = _torch()
+        d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        d_centres = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        d_normals = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        ctr = TraceCounters()
+        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
+        torch.cuda.synchronize()
+        _check(lib().rtk_dev_sweep_obbs_counted(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.c_void_p(d_records.data_ptr()),
+                                                C.c_void_p(d_centres.data_ptr()), C.c_void_p(d_normals.data_ptr()),
+                                                C.byref(f) if f is not None else None, C.byref(ctr)), "rtk_dev_sweep_obbs_counted")
+        return d_records, d_centres, d_normals, ctr.as_dict()
+
+    @staticmethod
+    def _obb_sweep_array(origins, directions, half, rotation, max_t, min_t):
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        s = np.zeros(n, OBB_SWEEP_DTYPE)
+        s["origin"] = o
+        s["direction"] = np.broadcast_to(np.asarray(directions, np.float32), (n, 3))
+        s["min_t"] = np.broadcast_to(np.asarray(min_t, np.float32), (n,))
+        s["max_t"] = RTK_INF if max_t is None else np.broadcast_to(np.asarray(max_t, np.float32), (n,))
+        s["half"] = np.broadcast_to(np.asarray(half, np.float32), (n, 3))
+        s["axes"] = obb_axes(rotation, n)
+        return s
+
+    def sweep_obbs(self, origins, directions, half, rotation, max_t=None, min_t=0.0, mesh_mask=None, ignore_prim=None):
+        """origins: array-like (n, 3) float32; directions (n, 3) or (3,), not necessarily normalised: t is in their units; half:
+        the half extents along the box's own axes, (n, 3), (3,) or a scalar (a cube); rotation: (n, 3, 3) or (3, 3) matrices whose
+        ROWS are the box's axes in scene coordinates, or (n, 4) or (4,) quaternions (x, y, z, w) that turn the unit vectors into
+        them (see obb_axes); max_t, min_t: scalars or one per query; max_t None = no limit (RTK_INF). Returns (records
+        HIT_RECORD_DTYPE, centres at the contact (n, 3) float32, contact normals (n, 3) float32): prim == 0xFFFFFFFF is a miss,
+        whose t is max_t, whose centre is the origin and whose normal is zeros. Axes that are not orthonormal to 2^-10 are a miss."""
+        s = self._obb_sweep_array(origins, directions, half, rotation, max_t, min_t)
+        n = s.shape[0]
+        if n == 0:
+            return np.zeros(0, HIT_RECORD_DTYPE), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
+        d_rec, d_ctr, d_nrm = self.sweep_obbs_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return (d_rec.cpu().numpy().view(HIT_RECORD_DTYPE), d_ctr.cpu().numpy().view(np.float32).reshape(n, 3),
+                d_nrm.cpu().numpy().view(np.float32).reshape(n, 3))
+
+    def obb_path_blocked(self, origins, directions, half, rotation, max_t=None, min_t=0.0, mesh_mask=None, ignore_prim=None):
+        """The any-hit form of sweep_obbs: a bool array, True where the box touches the scene somewhere in [min_t, max_t]."""
+        s = self._obb_sweep_array(origins, directions, half, rotation, max_t, min_t)
+        n = s.shape[0]
+        if n == 0:
+            return np.zeros(0, bool)
+        d_blocked = self.sweep_obbs_any_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
         _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
         return d_blocked.cpu().numpy() != 0
 
@@ -1885,6 +1989,27 @@ class DeviceScene:
 
 
 # -- the reference's own entry points, host pointers (reference rtk.h:126-130) --
+
+def obb_axes(rotation, n):
+    """The `axes` of n rtk_obb_sweep queries, float32 (n, 3, 3), rows = the box's own axes in scene coordinates. rotation: (n, 3, 3) or
+    (3, 3) matrices with those rows, or (n, 4) or (4,) quaternions (x, y, z, w): normalised and converted in float64 -- row j is the
+    image of unit vector j under the quaternion's rotation -- then rounded once to float32."""
+    r = np.asarray(rotation, np.float64)
+    if r.shape in ((3, 3), (n, 3, 3)):
+        m = r
+    elif r.shape in ((4,), (n, 4)):
+        q = r.reshape(-1, 4)
+        with np.errstate(all="ignore"):
+            q = q / np.sqrt((q * q).sum(1, keepdims=True))
+        x, y, z, w = q.T
+        # (the transpose of the usual rotation matrix: its columns are the images of the unit vectors)
+        m = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y + z * w), 2 * (x * z - y * w),
+                      2 * (x * y - z * w), 1 - 2 * (x * x + z * z), 2 * (y * z + x * w),
+                      2 * (x * z + y * w), 2 * (y * z - x * w), 1 - 2 * (x * x + y * y)], -1).reshape(-1, 3, 3)
+    else:
+        raise RtkError("obb_axes: rotation of shape %s: (n, 3, 3), (3, 3), (n, 4) or (4,) with n = %d" % (r.shape, n))
+    return np.ascontiguousarray(np.broadcast_to(m.reshape(-1, 3, 3), (n, 3, 3)), np.float32)
+
 
 def build_scene(meshes):
     """rtk_build_scene: returns (scene pointer, MeshSet keepalive). Release with free_scene."""

@@ -350,6 +350,25 @@ extern "C" int rtk_dev_sweep_capsules_counted(const rtk_dev_scene *ds, const rtk
 	return rtk_launch_capsule(ds, d_sweeps, num_sweeps, nullptr, d_records, d_points, d_axis_points, nullptr, false, filter, nullptr, out);
 }
 
+extern "C" int rtk_dev_sweep_obbs(const rtk_dev_scene *ds, const rtk_obb_sweep *d_sweeps, size_t num_sweeps, const rtk_ray_list *list,
+	rtk_hit_record *d_records, float *d_centres, float *d_normals, const rtk_dev_filter *filter, void *stream)
+{
+	return rtk_launch_obbsweep(ds, d_sweeps, num_sweeps, list, d_records, d_centres, d_normals, nullptr, false, filter, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_sweep_obbs_any(const rtk_dev_scene *ds, const rtk_obb_sweep *d_sweeps, size_t num_sweeps, const rtk_ray_list *list,
+	uint8_t *d_blocked, const rtk_dev_filter *filter, void *stream)
+{
+	return rtk_launch_obbsweep(ds, d_sweeps, num_sweeps, list, nullptr, nullptr, nullptr, d_blocked, true, filter, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_sweep_obbs_counted(const rtk_dev_scene *ds, const rtk_obb_sweep *d_sweeps, size_t num_sweeps,
+	rtk_hit_record *d_records, float *d_centres, float *d_normals, const rtk_dev_filter *filter, rtk_trace_counters *out)
+{
+	if (!out) { rtk_set_error("rtk_dev_sweep_obbs_counted: NULL counters"); return RTK_AMD_ERR_BAD_ARG; }
+	return rtk_launch_obbsweep(ds, d_sweeps, num_sweeps, nullptr, d_records, d_centres, d_normals, nullptr, false, filter, nullptr, out);
+}
+
 extern "C" int rtk_dev_trace_rays_count(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n,
 	uint32_t *d_counts, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream)
 {

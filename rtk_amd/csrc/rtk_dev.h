@@ -372,6 +372,11 @@ int rtk_launch_boxsweep(const rtk_dev_scene *ds, const rtk_box_sweep *d_sweeps, 
 int rtk_launch_capsule(const rtk_dev_scene *ds, const rtk_capsule_sweep *d_sweeps, size_t num_sweeps, const rtk_ray_list *list,
 	rtk_hit_record *d_records, float *d_points, float *d_axis_points, uint8_t *d_blocked, bool any_hit, const rtk_dev_filter *filter,
 	hipStream_t stream, rtk_trace_counters *counted = nullptr);
+// -- rtk_dev_sweep_obbs / rtk_dev_sweep_obbs_any (rtk_obbsweep.hip) --
+// as rtk_launch_boxsweep, every query with axes of its own
+int rtk_launch_obbsweep(const rtk_dev_scene *ds, const rtk_obb_sweep *d_sweeps, size_t num_sweeps, const rtk_ray_list *list,
+	rtk_hit_record *d_records, float *d_centres, float *d_normals, uint8_t *d_blocked, bool any_hit, const rtk_dev_filter *filter,
+	hipStream_t stream, rtk_trace_counters *counted = nullptr);
 // -- the look for an image nobody announced (rtk_detect.hip) --
 int rtk_detect_image(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, hipStream_t stream, uint32_t *w_out, uint32_t *h_out);
 // -- hit records to full hits, and rtk_trace_ray's one-ray launch (rtk_expand.hip) --

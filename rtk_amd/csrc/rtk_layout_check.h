@@ -31,6 +31,8 @@ static_assert(sizeof(rtk_box_sweep) == 44 && offsetof(rtk_box_sweep, direction) 
 	offsetof(rtk_box_sweep, half) == 32, "rtk_box_sweep");
 static_assert(sizeof(rtk_capsule_sweep) == 48 && offsetof(rtk_capsule_sweep, direction) == 12 && offsetof(rtk_capsule_sweep, min_t) == 24 &&
 	offsetof(rtk_capsule_sweep, radius) == 32 && offsetof(rtk_capsule_sweep, half_axis) == 36, "rtk_capsule_sweep");
+static_assert(sizeof(rtk_obb_sweep) == 80 && offsetof(rtk_obb_sweep, direction) == 12 && offsetof(rtk_obb_sweep, min_t) == 24 &&
+	offsetof(rtk_obb_sweep, half) == 32 && offsetof(rtk_obb_sweep, axes) == 44, "rtk_obb_sweep");
 static_assert(sizeof(rtk_dev_filter) == 32 && offsetof(rtk_dev_filter, d_ignore_prim) == 16 && offsetof(rtk_dev_filter, d_after) == 24, "rtk_dev_filter");
 static_assert(sizeof(rtk_dev_rebuild_info) == 40 && offsetof(rtk_dev_rebuild_info, nodes_before) == 8 && offsetof(rtk_dev_rebuild_info, max_depth_before) == 24 &&
 	offsetof(rtk_dev_rebuild_info, rebuild_ms) == 32, "rtk_dev_rebuild_info");

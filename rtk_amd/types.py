@@ -37,6 +37,10 @@ assert BOX_SWEEP_DTYPE.itemsize == 44
 CAPSULE_SWEEP_DTYPE = np.dtype([("origin", "<f4", (3,)), ("direction", "<f4", (3,)), ("min_t", "<f4"), ("max_t", "<f4"), ("radius", "<f4"),
                                 ("half_axis", "<f4", (3,))])
 assert CAPSULE_SWEEP_DTYPE.itemsize == 48
+# rtk_obb_sweep (rtk_dev_sweep_obbs): a float32 [n, 20] array is one; the rows of `axes` are the box's own axes; its record is HIT_RECORD_DTYPE
+OBB_SWEEP_DTYPE = np.dtype([("origin", "<f4", (3,)), ("direction", "<f4", (3,)), ("min_t", "<f4"), ("max_t", "<f4"), ("half", "<f4", (3,)),
+                            ("axes", "<f4", (3, 3))])
+assert OBB_SWEEP_DTYPE.itemsize == 80
 assert POINT_QUERY_DTYPE.itemsize == 16 and CLOSEST_RECORD_DTYPE.itemsize == 16 and BOX_QUERY_DTYPE.itemsize == 24
 assert TRI_QUERY_DTYPE.itemsize == 36
 assert VERTEX_DTYPE.itemsize == 16 and RAY_DTYPE.itemsize == 32
