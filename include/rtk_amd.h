@@ -510,6 +510,61 @@ int rtk_dev_closest_points_counted(const rtk_dev_scene *ds, const rtk_point_quer
 /* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
 uint32_t rtk_amd_closest_stack_entries(void);
 
+/* ---- Signed distance: how far a point is from the surface, and on which side of it ----
+ * What a closest-point query is asked next (sampling a signed distance field for implicit and neural shapes, voxelising a solid,
+ * "is this particle inside the body", pushing a point out of a body). rtk_dev_signed_distances answers every query as
+ * rtk_dev_closest_points does -- the same walk, the same records and points, byte for byte -- and then gives the distance a sign.
+ *
+ * THE RULE (rtk_amd/csrc/rtk_sign_rule.h; INTEGRATION.md "Signed distance") is Baerentzen and Aanaes's angle-weighted
+ * pseudonormal. The closest point q of the answer's triangle lies on a feature of it: the face, one of its three edges or one of
+ * its three vertices (the region 1 .. 7 of the closest rule, evaluated again on that record). The feature has a normal N: the
+ * face's own cross product; for an edge the sum of the unit normals of every triangle on that edge; for a vertex the sum of
+ * angle * unit normal over every triangle corner at that vertex. s = dot(p - q, N); the point is INSIDE iff s < 0 (a zero or a
+ * NaN s is outside) and signed = inside ? -sqrt(dist2) : sqrt(dist2). The face normal alone, dot(p - q, n), is wrong at every
+ * concave or saddle edge and vertex; the sums are right there. Corners are WELDED BY PLACE: two corners are the same vertex iff
+ * their three coordinates compare equal as numbers (-0 equals +0, a NaN equals nothing). Vertex indices and mesh numbers play no
+ * part, so a seam with duplicated vertices and two meshes that meet are one surface; a placed mesh's records are world positions.
+ * Every operation is one float operation rounded on its own, sums are taken in ascending (primitive, corner) order, the angle
+ * is a polynomial arctangent written in the header (no libm): THE TABLE AND THE SIGN DO NOT DEPEND ON THE TREE, on slots or on
+ * the way the scene was made, and a numpy float32 restatement gives the same bits (tests/sign_ref.py).
+ *   hit    d_signed[i] = +-sqrt(dist2); d_records[i] and d_points[3 i ..] as rtk_dev_closest_points writes them
+ *   miss   d_signed[i] = RTK_INF: no triangle within max_dist2, the side is not known; record and point are that call's miss.
+ *          A query that call answers with a miss without a walk (a NaN, zero or negative limit, a non-finite coordinate) is one.
+ * What the method promises: on a CLOSED, CONSISTENTLY WOUND, NON-SELF-INTERSECTING surface the sign is the true one, up to the
+ * float rounding of a dot product that is near zero only for points near the surface's tangent planes. On an open or
+ * inconsistently wound mesh the call still terminates and is deterministic; the sign near the defects means nothing. The
+ * diagnostics say which case a scene is in:
+ *     closed = boundary_sides == 0 && nonmanifold_sides == 0 && inconsistent_sides == 0
+ * is the "is the sign meaningful" test (degenerate_triangles only says how many records gave no normal to their neighbours).
+ *
+ * The table (18 floats per primitive: the edge normals of ab, ac, bc, then the vertex normals of a, b, c) is made on the device
+ * on first use -- by rtk_dev_scene_prepare_signs or by the first rtk_dev_signed_distances / rtk_dev_scene_pseudonormals -- which
+ * synchronises `stream` that one time; it counts 72 bytes per primitive toward total_device_bytes. A refit of any kind (vertices
+ * moved) drops it and the next call makes it again; rtk_dev_scene_split_leaves and rtk_dev_scene_rebuild keep it. The call reads
+ * a record through the scene's side arrays, which a device-built scene makes on first use as rtk_dev_expand_hits does.
+ * `list`, d_points == NULL, asynchrony, the scratch set and rtk_dev_trace_status: as for rtk_dev_closest_points; A SLOT THAT IS
+ * NOT LISTED IS NOT WRITTEN in d_signed either. d_records may be NULL: the walk's records then live in the per-(scene, stream)
+ * scratch set.
+ * Refused before any HIP call: RTK_AMD_ERR_BAD_ARG for everything rtk_dev_closest_points refuses and for a NULL d_signed with
+ * num_queries != 0 (rtk_dev_scene_pseudonormals: a NULL d_out); RTK_AMD_ERR_UNSUPPORTED for a scene that does not hold exactly
+ * one triangle record per primitive (an uploaded blob may name an id twice): nothing is allocated or written.
+ * num_queries == 0 is RTK_AMD_OK and does not make the table. Works as it is on rtk_mgpu_scene(m, i). */
+typedef struct rtk_dev_sign_info {
+	uint64_t boundary_sides;        /* (prim, edge) pairs whose edge no other triangle shares */
+	uint64_t nonmanifold_sides;     /* ... whose edge three or more triangles share */
+	uint64_t inconsistent_sides;    /* ... shared with exactly one other triangle that runs it in the same direction */
+	uint64_t degenerate_triangles;  /* records without a unit normal in float */
+	uint64_t places;                /* distinct vertex places after welding */
+	uint64_t table_bytes;
+	double   table_ms;              /* wall time of the last making of the table; 0 if this call found it made */
+} rtk_dev_sign_info;
+/* makes the table now if it is not there (synchronises `stream` the one time it has to work), reports the diagnostics (kept with the table) */
+int rtk_dev_scene_prepare_signs(const rtk_dev_scene *ds, rtk_dev_sign_info *out /* may be NULL */, void *stream);
+/* copies the table to d_out[18 * num_prims] on `stream` (for tests and for users who want smooth feature normals) */
+int rtk_dev_scene_pseudonormals(const rtk_dev_scene *ds, float *d_out, void *stream);
+int rtk_dev_signed_distances(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries, const rtk_ray_list *list,
+	rtk_closest_record *d_records /* may be NULL */, float *d_points /* may be NULL */, float *d_signed, void *stream);
+
 /* ---- Triangles within a distance: how many triangles lie within r of a point, and all of them (or the k nearest) ----
  * The question asked in the same breath as "which triangle is nearest": contact generation needs every triangle a sphere
  * touches, robust normals and ICP with outlier rejection the k nearest, photon and sample gathering a radius query. Closest

@@ -78,6 +78,15 @@ class RebuildInfo(C.Structure):
         return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_}
 
 
+class SignInfo(C.Structure):
+    """rtk_dev_sign_info: what the making of a scene's table of pseudonormals found (rtk_dev_scene_prepare_signs)."""
+    _fields_ = [("boundary_sides", C.c_uint64), ("nonmanifold_sides", C.c_uint64), ("inconsistent_sides", C.c_uint64),
+                ("degenerate_triangles", C.c_uint64), ("places", C.c_uint64), ("table_bytes", C.c_uint64), ("table_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_}
+
+
 class TraceOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("image_width", C.c_uint32),
                 ("image_height", C.c_uint32), ("refill_min", C.c_uint32), ("blocks_per_cu", C.c_uint32),
@@ -178,6 +187,7 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_dev_trace_rays_listed", "rtk_dev_trace_rays_any_listed", "rtk_dev_select_rays",
                      "rtk_amd_select_block_items", "rtk_amd_select_scan_items",
                      "rtk_dev_closest_points", "rtk_dev_closest_points_counted", "rtk_amd_closest_stack_entries",
+                     "rtk_dev_scene_prepare_signs", "rtk_dev_scene_pseudonormals", "rtk_dev_signed_distances",
                      "rtk_dev_trace_rays_count", "rtk_dev_trace_rays_all", "rtk_amd_allhits_stack_entries",
                      "rtk_dev_triangles_within_count", "rtk_dev_triangles_within_all", "rtk_dev_triangles_within_counted",
                      "rtk_amd_within_stack_entries",
@@ -259,6 +269,12 @@ def lib():
     L.rtk_dev_closest_points.restype = C.c_int
     L.rtk_dev_closest_points_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
     L.rtk_dev_closest_points_counted.restype = C.c_int
+    L.rtk_dev_scene_prepare_signs.argtypes = [C.c_void_p, C.POINTER(SignInfo), C.c_void_p]
+    L.rtk_dev_scene_prepare_signs.restype = C.c_int
+    L.rtk_dev_scene_pseudonormals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtk_dev_scene_pseudonormals.restype = C.c_int
+    L.rtk_dev_signed_distances.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtk_dev_signed_distances.restype = C.c_int
     L.rtk_amd_closest_stack_entries.argtypes = []
     L.rtk_amd_closest_stack_entries.restype = C.c_uint32
     L.rtk_dev_sweep_spheres.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
@@ -755,6 +771,82 @@ class DeviceScene:
         d_rec, d_pts = self.closest_points_device(to_device(q), n)
         _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
         return d_rec.cpu().numpy().view(CLOSEST_RECORD_DTYPE), d_pts.cpu().numpy().view(np.float32).reshape(n, 3)
+
+    # -- signed distances (rtk_dev_signed_distances): the closest-point call and the side of the surface --
+
+    def prepare_signs(self):
+        """Makes the scene's table of pseudonormals now if it is not there (rtk_dev_scene_prepare_signs, on the current stream)
+        and returns the fields of rtk_dev_sign_info as a dict, plus closed = no boundary, non-manifold or inconsistent side:
+        whether the sign of a distance means anything. table_ms is 0 when the table was found made."""
+        _torch()
+        s = SignInfo()
+        _check(lib().rtk_dev_scene_prepare_signs(self.handle, C.byref(s), _stream_ptr()), "rtk_dev_scene_prepare_signs")
+        d = s.as_dict()
+        d["closed"] = d["boundary_sides"] == 0 and d["nonmanifold_sides"] == 0 and d["inconsistent_sides"] == 0
+        return d
+
+    def pseudonormals(self):
+        """The table as a float32 cuda tensor (num_prims, 18): per primitive the edge normals of ab, ac, bc, then the vertex
+        normals of a, b, c (rtk_dev_scene_pseudonormals). Made on first use."""
+        torch = _torch()
+        n = self.info()["num_triangles"]
+        out = torch.empty((n, 18), dtype=torch.float32, device="cuda")
+        _check(lib().rtk_dev_scene_pseudonormals(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr()), "rtk_dev_scene_pseudonormals")
+        return out
+
+    def signed_distances_device(self, d_queries, n, d_records=None, d_points=None, d_signed=None, count=None, ids=None, want_records=True, want_points=True):
+        """closest_points_device plus the signed distance of every answered query: returns (d_signed, d_records, d_points) --
+        a float32 cuda tensor of n entries, negative inside, RTK_INF for a miss, and the two tensors of closest_points_device
+        (None for the one that want_records=False or want_points=False leaves out: the call gets NULL for it). count / ids as
+        there; slots that are not listed are not written. Nothing waits for the stream, except the one call that makes the table."""
+        torch = _torch()
+        if not want_records:
+            d_records = None
+        elif d_records is None:
+            d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        if not want_points:
+            d_points = None
+        elif d_points is None:
+            d_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        if d_signed is None:
+            d_signed = torch.empty(n, dtype=torch.float32, device="cuda")
+        if ids is not None and count is None:
+            raise RtkError("signed_distances_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        _check(lib().rtk_dev_signed_distances(self.handle, C.c_void_p(d_queries.data_ptr()), n, C.byref(l) if l is not None else None,
+                                              C.c_void_p(d_records.data_ptr()) if d_records is not None else None,
+                                              C.c_void_p(d_points.data_ptr()) if d_points is not None else None,
+                                              C.c_void_p(d_signed.data_ptr()), _stream_ptr()), "rtk_dev_signed_distances")
+        return d_signed, d_records, d_points
+
+    def signed_distances(self, points, max_dist=None):
+        """points: array-like or tensor (n, 3) float32; max_dist as for closest_points. Returns cuda tensors (signed (n,) float32
+        -- negative inside, RTK_INF where no triangle is within max_dist --, prim (n,) int64 with -1 for a miss, points (n, 3)
+        float32: the closest points)."""
+        torch = _torch()
+        pts = points.detach().cpu().numpy() if hasattr(points, "detach") else points
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        q = np.zeros(n, POINT_QUERY_DTYPE)
+        q["point"] = pts
+        if max_dist is None:
+            q["max_dist2"] = RTK_INF
+        else:
+            d = np.broadcast_to(np.asarray(max_dist, np.float32), (n,))
+            with np.errstate(over="ignore", invalid="ignore"):
+                q["max_dist2"] = d * d
+        if n == 0:
+            return (torch.empty(0, dtype=torch.float32, device="cuda"), torch.empty(0, dtype=torch.int64, device="cuda"),
+                    torch.empty((0, 3), dtype=torch.float32, device="cuda"))
+        d_signed, d_rec, d_pts = self.signed_distances_device(to_device(q), n)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        prim = d_rec.view(torch.int32).view(n, 4)[:, 3].to(torch.int64)
+        return d_signed, prim, d_pts.view(torch.float32).view(n, 3)
+
+    def contains_signed(self, points):
+        """A bool cuda tensor: signed_distances(points)[0] < 0. Meaningful on a closed scene (prepare_signs()["closed"]). (contains()
+        is the older crossing-parity route through count_hits and stays as it is; this one does not flip at grazed edges.)"""
+        return self.signed_distances(points)[0] < 0
 
     # -- sphere sweeps (rtk_dev_sweep_spheres / _any): asynchronous on the current stream, nothing here waits for it --
 

@@ -58,7 +58,13 @@ extern "C" rtk_dev_scene *rtk_dev_scene_upload_buffer(const void *blob, size_t b
 void rtk_scene_forget_derived(rtk_dev_scene *ds, unsigned what)
 {
 	rtk_export_forget(ds);
-	if (what & RTK_FORGET_BOXES) ds->quality.refitted = true;
+	if (what & RTK_FORGET_BOXES) {
+		ds->quality.refitted = true;
+		// (vertices moved: the pseudonormals are made from positions; the next signed query makes them again)
+		std::lock_guard<std::mutex> lock(ds->sign_mutex);
+		ds->mem.release(ds->sign.d_table);
+		ds->sign = SignTable();
+	}
 	if (what & RTK_FORGET_TREE) {
 		ds->refit.reset(ds->mem);
 		ds->partial.reset(ds->mem);

@@ -116,6 +116,14 @@ struct QualityState {
 	double sah_cost_at_build = 0.0;            // ... and gave this cost
 };
 
+// The table of pseudonormals behind rtk_dev_signed_distances (rtk_sign.hip, the rule: rtk_sign_rule.h): 18 floats per primitive,
+// indexed by the global primitive id, made from the positions of the triangle records on first use, one entry of
+// rtk_dev_scene::mem. The diagnostics of its making are kept with it. Under sign_mutex.
+struct SignTable {
+	float *d_table = nullptr;                  // [18 * num_prims]; NULL: not made (or dropped by RTK_FORGET_BOXES)
+	rtk_dev_sign_info info = {};               // as the making left it (table_ms: of that making)
+};
+
 static inline void *rtk_dev_malloc(size_t bytes) { void *p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; }
 static inline void rtk_dev_free(void *p) { (void)hipFree(p); }
 
@@ -169,14 +177,20 @@ struct rtk_dev_scene {
 	uint64_t refit_nodes = 0;                  // nodes whose boxes the last successful refit remade
 	uint32_t partial_readback = 0;             // the dirty count of a partial refit, brought home with the constants
 	QualityState quality;                      // under refit_mutex, like the schedule
+	// Signed distances (rtk_sign.hip). The table goes by primitive id and is made from positions: RTK_FORGET_BOXES drops it,
+	// RTK_FORGET_TREE and RTK_FORGET_SLOTS keep it. records_once: every primitive id is named by exactly one triangle record (a
+	// device build and a rebuild always; an upload counts, on the host) -- what the making of the table needs.
+	std::mutex sign_mutex;
+	SignTable sign;
+	bool records_once = true;
 };
 // makes the side arrays if they are not there yet (synchronises `stream` the one time it has to work)
 int rtk_scene_side_arrays(const rtk_dev_scene *ds, hipStream_t stream);
 // What was derived from the scene and no longer holds is dropped here, and only here (rtk_capi.hip); whoever needs a table
 // again makes it again. A new derived table is added to this function and nowhere else.
-#define RTK_FORGET_BOXES 1u       // boxes moved, the topology stayed (a refit): the export plan; a cost measured from now on is not the build's
-#define RTK_FORGET_TREE 2u        // nodes or slots were renumbered (a split): the refit schedule, the partial refit's tables, the export plan, the cost at build
-#define RTK_FORGET_SLOTS 4u       // every record changed its slot (a rebuild): the four side arrays, made again on first use. The caller holds side_mutex.
+#define RTK_FORGET_BOXES 1u       // boxes moved, the topology stayed (a refit): the export plan; a cost measured from now on is not the build's; the table of pseudonormals (vertices moved: it is made from positions)
+#define RTK_FORGET_TREE 2u        // nodes or slots were renumbered (a split): the refit schedule, the partial refit's tables, the export plan, the cost at build. Keeps the table of pseudonormals: it goes by primitive id
+#define RTK_FORGET_SLOTS 4u       // every record changed its slot (a rebuild): the four side arrays, made again on first use. The caller holds side_mutex. Keeps the table of pseudonormals: records moved, not vertices
 void rtk_scene_forget_derived(rtk_dev_scene *ds, unsigned what);
 
 // -- error plumbing (rtk_capi.hip) --
@@ -332,6 +346,12 @@ int rtk_launch_select(rtk_dev_scene *ds, const void *d_src, uint32_t kind, size_
 // -- rtk_dev_closest_points (rtk_closest.hip) --
 int rtk_launch_closest(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries, const rtk_ray_list *list,
 	rtk_closest_record *d_records, float *d_points, hipStream_t stream, rtk_trace_counters *counted = nullptr);   // counted: synchronises the stream
+// -- rtk_dev_signed_distances (rtk_sign.hip) --
+// the table of pseudonormals, made if it is not there (synchronises `stream` the one time it has to work); ds->sign.d_table after RTK_AMD_OK
+int rtk_scene_pseudonormals(const rtk_dev_scene *ds, hipStream_t stream);
+// rtk_launch_closest as it is, then the epilogue that writes d_signed on the same stream
+int rtk_launch_signed(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries, const rtk_ray_list *list,
+	rtk_closest_record *d_records, float *d_points, float *d_signed, hipStream_t stream);
 // -- rtk_dev_triangles_within_count / rtk_dev_triangles_within_all (rtk_within.hip) --
 // fill: offsets, records, points or NULL, d_counts the written numbers or NULL; else d_counts the counts. counted: synchronises the stream
 int rtk_launch_within(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries, const rtk_ray_list *list,

@@ -43,7 +43,7 @@ struct ScratchBuf {
 };
 
 struct LaunchScratch {
-	enum { SPILL, SORT, ENTRIES, LEFTOVER, SELECT, NUM_BUFFERS };
+	enum { SPILL, SORT, ENTRIES, LEFTOVER, SELECT, SIGNED, NUM_BUFFERS };
 	void *const stream;
 	const ScratchHooks &hooks;
 	unsigned long long *d_counter = nullptr;    // RTK_COUNTER_WORDS, the error word, the image look's words (rtk_dev.h)
@@ -54,6 +54,7 @@ struct LaunchScratch {
 	ScratchBuf &entries = buf[ENTRIES];         // packet kernels: entry lists of the image's 64x64-pixel blocks (PkBlockEntries); capacity: blocks
 	ScratchBuf &leftover = buf[LEFTOVER];       // tiles the assembly packet kernel hands to the C++ one, or rays the assembly per-lane kernel hands to rtk_trace_kernel; capacity: bytes
 	ScratchBuf &select = buf[SELECT];           // rtk_dev_select_rays: keep masks, per-workgroup counts and their sums (rtk_select.hip); capacity: bytes
+	ScratchBuf &signed_records = buf[SIGNED];   // rtk_dev_signed_distances without d_records: the closest walk's records (rtk_sign.hip); capacity: queries
 	size_t spill_entries_per_lane = 0;
 
 	LaunchScratch(void *stream_, const ScratchHooks &hooks_) : stream(stream_), hooks(hooks_) {}

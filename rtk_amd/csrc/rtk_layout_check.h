@@ -36,3 +36,4 @@ static_assert(sizeof(rtk_obb_sweep) == 80 && offsetof(rtk_obb_sweep, direction) 
 static_assert(sizeof(rtk_dev_filter) == 32 && offsetof(rtk_dev_filter, d_ignore_prim) == 16 && offsetof(rtk_dev_filter, d_after) == 24, "rtk_dev_filter");
 static_assert(sizeof(rtk_dev_rebuild_info) == 40 && offsetof(rtk_dev_rebuild_info, nodes_before) == 8 && offsetof(rtk_dev_rebuild_info, max_depth_before) == 24 &&
 	offsetof(rtk_dev_rebuild_info, rebuild_ms) == 32, "rtk_dev_rebuild_info");
+static_assert(sizeof(rtk_dev_sign_info) == 56 && offsetof(rtk_dev_sign_info, places) == 32 && offsetof(rtk_dev_sign_info, table_ms) == 48, "rtk_dev_sign_info");

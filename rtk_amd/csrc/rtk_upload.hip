@@ -229,7 +229,13 @@ rtk_dev_scene *rtk_dev_scene_from_host_bvh(const HostBvh &h)
 	ds->tree.max_depth = h.max_depth;
 
 	std::vector<uint32_t> prim_slot(h.mesh_base.empty() ? 0 : (size_t)h.mesh_base.back(), 0xffffffffu);
-	for (size_t s = 0; s < h.tris.size(); s++) if (h.tris[s].prim < prim_slot.size()) prim_slot[h.tris[s].prim] = (uint32_t)s;
+	// (a blob may name a primitive id twice, or never: records_once is what the table of pseudonormals asks before it is made)
+	ds->records_once = h.tris.size() == prim_slot.size();
+	for (size_t s = 0; s < h.tris.size(); s++) {
+		if (h.tris[s].prim >= prim_slot.size()) { ds->records_once = false; continue; }
+		if (prim_slot[h.tris[s].prim] != 0xffffffffu) ds->records_once = false;
+		prim_slot[h.tris[s].prim] = (uint32_t)s;
+	}
 
 	bool ok = upload_vec(ds, h.nodes, &ds->view.nodes) && upload_vec(ds, h.tris, &ds->view.tris) &&
 		upload_vec(ds, h.vertex_index, &ds->view.vertex_index) && upload_vec(ds, prim_slot, &ds->view.prim_slot) &&
