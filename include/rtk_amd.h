@@ -565,6 +565,61 @@ int rtk_dev_scene_pseudonormals(const rtk_dev_scene *ds, float *d_out, void *str
 int rtk_dev_signed_distances(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries, const rtk_ray_list *list,
 	rtk_closest_record *d_records /* may be NULL */, float *d_points /* may be NULL */, float *d_signed, void *stream);
 
+/* ---- Winding numbers: how many times the surface wraps round a point, also where the surface has holes ----
+ * The inside test for the meshes the two others fail on: a scan, a game asset, a CAD export with a hole, a crack or a duplicated
+ * shell, where pseudonormals (rtk_dev_signed_distances) and crossing parity mean nothing near the defect. The generalized
+ * winding number (Jacobson et al. 2013) of a point is the sum of the signed solid angles of all triangles seen from it, over
+ * 4 pi: 1 inside and 0 outside a closed surface wound outwards, k inside k nested shells, -1 inside a shell wound inwards, a
+ * smooth fraction near a hole. w > 0.5 is an inside test that degrades gracefully.
+ *
+ * THE RULE (rtk_amd/csrc/rtk_winding_rule.h; INTEGRATION.md "Winding numbers"). The sum is taken over the scene's tree (Barill et
+ * al. 2018, first order): each child slot of a node has MOMENTS -- the area vector N = sum of 0.5 * cross(b - a, c - a), the
+ * area-weighted centre P and a radius R that every corner under the slot lies within of P (from the slot's box) --, and a child
+ * is answered by the one far term dot(N, P - p) / |P - p|^3 / (4 pi) iff |P - p|^2 > (beta * R)^2; otherwise it is descended,
+ * and a leaf's triangles are summed by van Oosterom and Strackee's solid angle with the polynomial atan2 of rtk_sign_rule.h.
+ * One float operation at a time, no libm. beta = 2 is the default; a larger beta descends more and is more exact;
+ * RTK_WINDING_EXACT takes no far term at all: every triangle is summed, O(n) per query, the form the fast one is measured against.
+ *   d_winding[i] = w of (x, y, z) of d_queries[i]. max_dist2 of an rtk_point_query IS NOT READ.
+ *   A query with a non-finite coordinate is answered without a walk, with the quiet NaN 0x7fc00000.
+ * THE SUM'S ORDER FOLLOWS THE TREE, so -- unlike a signed distance -- the result is NOT promised bit for bit across trees (a
+ * split, a rebuild, another builder): it is promised within a tolerance. Measured for points not within 5 % of the shape's size
+ * of the surface (profiles/winding_accuracy.log, asserted by tests/test_gpu_winding.py): the exact form within 1e-3 of the
+ * float64 sum, and the fast form on the side of 0.5 the float64 sum is on. The same scene object gives the same bits every call.
+ *
+ * The table of moments (one 128-byte record per node: Nx Ny Nz Px Py Pz R of the four child slots, four floats each, then a copy
+ * of the node's four child words: 32 words, so a node step of the walk reads that one line and never the boxes) is made on the
+ * device on first use -- by rtk_dev_scene_prepare_winding or by the first rtk_dev_winding_numbers / rtk_dev_scene_winding_moments
+ * --, which synchronises `stream` that one time; it counts 128 bytes per node toward total_device_bytes and is released with the
+ * scene. It depends on positions AND on the tree: every refit (rtk_dev_scene_refit, _refit_meshes, the _placed forms),
+ * rtk_dev_scene_split_leaves and rtk_dev_scene_rebuild drop it, and the next call makes it again.
+ * `list`, asynchrony on `stream`, the scratch set and rtk_dev_trace_status: as for rtk_dev_closest_points; A SLOT THAT IS NOT
+ * LISTED IS NOT WRITTEN. _counted: rays = queries, nodes = table records fetched, leaves and triangles as for the closest call,
+ * hits = far terms taken, stack_spills = pushes past the on-chip part.
+ * Refused before any HIP call: RTK_AMD_ERR_BAD_ARG for everything rtk_dev_closest_points refuses, for a NULL d_winding with
+ * num_queries != 0, and for opts with a wrong struct_size, an unknown flag, a negative or a NaN beta (beta == 0: the default, 2);
+ * RTK_AMD_ERR_UNSUPPORTED for a scene that does not hold exactly one triangle record per primitive (a triangle named twice
+ * would be counted twice): nothing is allocated or written. num_queries == 0 is RTK_AMD_OK and does not make the table.
+ * Works as it is on rtk_mgpu_scene(m, i). */
+typedef struct rtk_winding_opts { uint32_t struct_size; uint32_t flags; float beta; } rtk_winding_opts;
+#define RTK_WINDING_EXACT 1u   /* never accept a far term: every triangle is summed (the reference the fast form is measured against) */
+typedef struct rtk_dev_winding_info {
+	uint64_t nodes;                 /* records of the table: the scene's nodes when it was made */
+	uint64_t table_bytes;           /* 128 * nodes */
+	double   table_ms;              /* wall time of the last making of the table; 0 if this call found it made */
+	double   total_area_vector[3];  /* the sum of N over the root's child slots: near 0 for a closed surface */
+	double   total_area;            /* the sum of the triangles' areas, as the table's float sums give it */
+} rtk_dev_winding_info;
+/* makes the table now if it is not there (synchronises `stream` only when it has to work) */
+int rtk_dev_scene_prepare_winding(const rtk_dev_scene *ds, rtk_dev_winding_info *out /* may be NULL */, void *stream);
+/* copies the table to d_out[32 * nodes] on `stream` (for tests) */
+int rtk_dev_scene_winding_moments(const rtk_dev_scene *ds, float *d_out, void *stream);
+int rtk_dev_winding_numbers(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries,
+	const rtk_ray_list *list, const rtk_winding_opts *opts /* NULL: beta 2, flags 0 */, float *d_winding, void *stream);
+int rtk_dev_winding_numbers_counted(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries,
+	const rtk_winding_opts *opts, float *d_winding, rtk_trace_counters *out);
+/* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
+uint32_t rtk_amd_winding_stack_entries(void);
+
 /* ---- Triangles within a distance: how many triangles lie within r of a point, and all of them (or the k nearest) ----
  * The question asked in the same breath as "which triangle is nearest": contact generation needs every triangle a sphere
  * touches, robust normals and ICP with outlier rejection the k nearest, photon and sample gathering a radius query. Closest

@@ -87,6 +87,30 @@ class SignInfo(C.Structure):
         return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_}
 
 
+class WindingInfo(C.Structure):
+    """rtk_dev_winding_info: what the making of a scene's table of winding moments found (rtk_dev_scene_prepare_winding)."""
+    _fields_ = [("nodes", C.c_uint64), ("table_bytes", C.c_uint64), ("table_ms", C.c_double), ("total_area_vector", C.c_double * 3),
+                ("total_area", C.c_double)]
+
+    def as_dict(self):
+        return dict(nodes=int(self.nodes), table_bytes=int(self.table_bytes), table_ms=float(self.table_ms),
+                    total_area_vector=[float(x) for x in self.total_area_vector], total_area=float(self.total_area))
+
+
+class WindingOpts(C.Structure):
+    """rtk_winding_opts: beta of the accept test (0: the default, 2) and RTK_WINDING_EXACT."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("beta", C.c_float)]
+
+
+RTK_WINDING_EXACT = 1
+
+
+def make_winding_opts(beta=2.0, exact=False):
+    o = WindingOpts()
+    o.struct_size, o.flags, o.beta = C.sizeof(WindingOpts), (RTK_WINDING_EXACT if exact else 0), beta
+    return o
+
+
 class TraceOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("image_width", C.c_uint32),
                 ("image_height", C.c_uint32), ("refill_min", C.c_uint32), ("blocks_per_cu", C.c_uint32),
@@ -188,6 +212,8 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_amd_select_block_items", "rtk_amd_select_scan_items",
                      "rtk_dev_closest_points", "rtk_dev_closest_points_counted", "rtk_amd_closest_stack_entries",
                      "rtk_dev_scene_prepare_signs", "rtk_dev_scene_pseudonormals", "rtk_dev_signed_distances",
+                     "rtk_dev_scene_prepare_winding", "rtk_dev_scene_winding_moments", "rtk_dev_winding_numbers",
+                     "rtk_dev_winding_numbers_counted", "rtk_amd_winding_stack_entries",
                      "rtk_dev_trace_rays_count", "rtk_dev_trace_rays_all", "rtk_amd_allhits_stack_entries",
                      "rtk_dev_triangles_within_count", "rtk_dev_triangles_within_all", "rtk_dev_triangles_within_counted",
                      "rtk_amd_within_stack_entries",
@@ -277,6 +303,16 @@ def lib():
     L.rtk_dev_signed_distances.restype = C.c_int
     L.rtk_amd_closest_stack_entries.argtypes = []
     L.rtk_amd_closest_stack_entries.restype = C.c_uint32
+    L.rtk_dev_scene_prepare_winding.argtypes = [C.c_void_p, C.POINTER(WindingInfo), C.c_void_p]
+    L.rtk_dev_scene_prepare_winding.restype = C.c_int
+    L.rtk_dev_scene_winding_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtk_dev_scene_winding_moments.restype = C.c_int
+    L.rtk_dev_winding_numbers.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(WindingOpts), C.c_void_p, C.c_void_p]
+    L.rtk_dev_winding_numbers.restype = C.c_int
+    L.rtk_dev_winding_numbers_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(WindingOpts), C.c_void_p, C.POINTER(TraceCounters)]
+    L.rtk_dev_winding_numbers_counted.restype = C.c_int
+    L.rtk_amd_winding_stack_entries.argtypes = []
+    L.rtk_amd_winding_stack_entries.restype = C.c_uint32
     L.rtk_dev_sweep_spheres.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.POINTER(DevFilter), C.c_void_p]
     L.rtk_dev_sweep_spheres.restype = C.c_int
@@ -847,6 +883,78 @@ class DeviceScene:
         """A bool cuda tensor: signed_distances(points)[0] < 0. Meaningful on a closed scene (prepare_signs()["closed"]). (contains()
         is the older crossing-parity route through count_hits and stays as it is; this one does not flip at grazed edges.)"""
         return self.signed_distances(points)[0] < 0
+
+    # -- winding numbers (rtk_dev_winding_numbers): the inside test that survives holes, cracks and duplicated shells --
+
+    def prepare_winding(self):
+        """Makes the scene's table of winding moments now if it is not there (rtk_dev_scene_prepare_winding, on the current
+        stream) and returns the fields of rtk_dev_winding_info as a dict. table_ms is 0 when the table was found made."""
+        _torch()
+        s = WindingInfo()
+        _check(lib().rtk_dev_scene_prepare_winding(self.handle, C.byref(s), _stream_ptr()), "rtk_dev_scene_prepare_winding")
+        return s.as_dict()
+
+    def winding_moments(self):
+        """The table as a float32 cuda tensor (nodes, 8, 4): per node the rows Nx Ny Nz Px Py Pz R of its four child slots, then
+        the node's four child words (view the last row as int32). Made on first use (rtk_dev_scene_winding_moments)."""
+        torch = _torch()
+        n = self.prepare_winding()["nodes"]
+        out = torch.empty((n, 8, 4), dtype=torch.float32, device="cuda")
+        _check(lib().rtk_dev_scene_winding_moments(self.handle, C.c_void_p(out.data_ptr()), _stream_ptr()), "rtk_dev_scene_winding_moments")
+        return out
+
+    def winding_numbers_device(self, d_queries, n, d_winding=None, count=None, ids=None, beta=2.0, exact=False):
+        """The winding number of each of n queries (POINT_QUERY_DTYPE bytes on the device; max_dist2 is not read): returns
+        d_winding, a float32 cuda tensor of n entries. count / ids as for closest_points_device; slots that are not listed are
+        not written. exact: RTK_WINDING_EXACT, every triangle is summed. Nothing waits for the stream, except the one call that
+        makes the table."""
+        torch = _torch()
+        if d_winding is None:
+            d_winding = torch.empty(n, dtype=torch.float32, device="cuda")
+        if ids is not None and count is None:
+            raise RtkError("winding_numbers_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        o = make_winding_opts(beta, exact)
+        _check(lib().rtk_dev_winding_numbers(self.handle, C.c_void_p(d_queries.data_ptr()), n, C.byref(l) if l is not None else None,
+                                             C.byref(o), C.c_void_p(d_winding.data_ptr()), _stream_ptr()), "rtk_dev_winding_numbers")
+        return d_winding
+
+    def winding_numbers_counted(self, d_queries, n, beta=2.0, exact=False):
+        """winding_numbers_device of all n queries on the null stream, synchronous, with the visit counts of
+        rtk_dev_winding_numbers_counted (nodes: table records fetched; hits: far terms taken): returns (d_winding, counts dict)."""
+        torch = _torch()
+        d_winding = torch.empty(n, dtype=torch.float32, device="cuda")
+        ctr = TraceCounters()
+        o = make_winding_opts(beta, exact)
+        torch.cuda.synchronize()
+        _check(lib().rtk_dev_winding_numbers_counted(self.handle, C.c_void_p(d_queries.data_ptr()), n, C.byref(o),
+                                                     C.c_void_p(d_winding.data_ptr()), C.byref(ctr)), "rtk_dev_winding_numbers_counted")
+        return d_winding, ctr.as_dict()
+
+    def winding_numbers(self, points, beta=2.0, exact=False):
+        """points: array-like or tensor (n, 3) float32. Returns the generalized winding numbers as a numpy float32 array (n,): 1
+        inside and 0 outside a closed surface wound outwards, k inside k nested shells, -1 inside a shell wound inwards, a
+        fraction near a hole; NaN for a point with a non-finite coordinate."""
+        pts = points.detach().cpu().numpy() if hasattr(points, "detach") else points
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        if n == 0:
+            return np.zeros(0, np.float32)
+        q = np.zeros(n, POINT_QUERY_DTYPE)
+        q["point"] = pts
+        q["max_dist2"] = RTK_INF
+        d_w = self.winding_numbers_device(to_device(q), n, beta=beta, exact=exact)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return d_w.cpu().numpy()
+
+    def contains_winding(self, points, beta=2.0):
+        """A numpy bool array: winding_numbers(points, beta) > 0.5. A shell wound INWARDS gives -1 inside and is therefore
+        "outside"; k nested shells give k and are inside. Prefer this over contains_signed and contains when the mesh may have
+        holes, cracks, duplicated or overlapping shells or inconsistent patches (scans, game assets, CAD exports): the winding
+        number degrades smoothly there, where the pseudonormal's sign and the crossing parity mean nothing near the defect. On a
+        closed, consistently wound mesh contains_signed is cheaper (one nearest-triangle walk, and it gives the distance too)
+        and contains needs no table at all."""
+        return self.winding_numbers(points, beta=beta) > 0.5
 
     # -- sphere sweeps (rtk_dev_sweep_spheres / _any): asynchronous on the current stream, nothing here waits for it --
 

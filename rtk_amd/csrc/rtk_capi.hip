@@ -58,6 +58,13 @@ extern "C" rtk_dev_scene *rtk_dev_scene_upload_buffer(const void *blob, size_t b
 void rtk_scene_forget_derived(rtk_dev_scene *ds, unsigned what)
 {
 	rtk_export_forget(ds);
+	if (what & (RTK_FORGET_BOXES | RTK_FORGET_TREE | RTK_FORGET_SLOTS)) {
+		// (the winding moments are made from positions and go by node: whatever moved or was renumbered, the next winding query
+		// makes them again. A rebuild is here with scratch_mutex held: that lock comes before this one everywhere, rtk_winding.hip)
+		std::lock_guard<std::mutex> lock(ds->winding_mutex);
+		ds->mem.release(ds->winding.d_table);
+		ds->winding = WindingTable();
+	}
 	if (what & RTK_FORGET_BOXES) {
 		ds->quality.refitted = true;
 		// (vertices moved: the pseudonormals are made from positions; the next signed query makes them again)

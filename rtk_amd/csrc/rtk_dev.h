@@ -124,6 +124,22 @@ struct SignTable {
 	rtk_dev_sign_info info = {};               // as the making left it (table_ms: of that making)
 };
 
+// The moments behind rtk_dev_winding_numbers (rtk_winding.hip, the rule: rtk_winding_rule.h): one record per DevNode at the same
+// index, so that a node step of the walk reads this one 128-byte line and never the node's boxes. Per child slot the area vector
+// N, the centre P and the radius R of everything under it; then a copy of the node's child words.
+struct DevWinding {
+	float nx[4], ny[4], nz[4];
+	float px[4], py[4], pz[4];
+	float r[4];
+	uint32_t child[4];
+};
+static_assert(sizeof(DevWinding) == 128, "one record of moments per node, one 128 B line");
+// The table: made from positions and from the tree on first use, one entry of rtk_dev_scene::mem. Under winding_mutex.
+struct WindingTable {
+	DevWinding *d_table = nullptr;             // [num_nodes]; NULL: not made (or dropped by any RTK_FORGET_*)
+	rtk_dev_winding_info info = {};            // as the making left it (table_ms: of that making)
+};
+
 static inline void *rtk_dev_malloc(size_t bytes) { void *p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; }
 static inline void rtk_dev_free(void *p) { (void)hipFree(p); }
 
@@ -183,6 +199,9 @@ struct rtk_dev_scene {
 	std::mutex sign_mutex;
 	SignTable sign;
 	bool records_once = true;
+	// Winding numbers (rtk_winding.hip). The table goes by node and is made from positions: every RTK_FORGET_* drops it.
+	std::mutex winding_mutex;
+	WindingTable winding;
 };
 // makes the side arrays if they are not there yet (synchronises `stream` the one time it has to work)
 int rtk_scene_side_arrays(const rtk_dev_scene *ds, hipStream_t stream);
@@ -191,6 +210,7 @@ int rtk_scene_side_arrays(const rtk_dev_scene *ds, hipStream_t stream);
 #define RTK_FORGET_BOXES 1u       // boxes moved, the topology stayed (a refit): the export plan; a cost measured from now on is not the build's; the table of pseudonormals (vertices moved: it is made from positions)
 #define RTK_FORGET_TREE 2u        // nodes or slots were renumbered (a split): the refit schedule, the partial refit's tables, the export plan, the cost at build. Keeps the table of pseudonormals: it goes by primitive id
 #define RTK_FORGET_SLOTS 4u       // every record changed its slot (a rebuild): the four side arrays, made again on first use. The caller holds side_mutex. Keeps the table of pseudonormals: records moved, not vertices
+// Each of the three also drops the table of winding moments: it is made from positions (BOXES) and goes by node (TREE, SLOTS).
 void rtk_scene_forget_derived(rtk_dev_scene *ds, unsigned what);
 
 // -- error plumbing (rtk_capi.hip) --
@@ -352,6 +372,12 @@ int rtk_scene_pseudonormals(const rtk_dev_scene *ds, hipStream_t stream);
 // rtk_launch_closest as it is, then the epilogue that writes d_signed on the same stream
 int rtk_launch_signed(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries, const rtk_ray_list *list,
 	rtk_closest_record *d_records, float *d_points, float *d_signed, hipStream_t stream);
+// -- rtk_dev_winding_numbers (rtk_winding.hip) --
+// the table of moments, made if it is not there (synchronises `stream` the one time it has to work); ds->winding.d_table after RTK_AMD_OK
+int rtk_scene_winding_table(const rtk_dev_scene *ds, hipStream_t stream);
+// counted: synchronises the stream
+int rtk_launch_winding(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries, const rtk_ray_list *list,
+	const rtk_winding_opts *opts, float *d_winding, hipStream_t stream, rtk_trace_counters *counted = nullptr);
 // -- rtk_dev_triangles_within_count / rtk_dev_triangles_within_all (rtk_within.hip) --
 // fill: offsets, records, points or NULL, d_counts the written numbers or NULL; else d_counts the counts. counted: synchronises the stream
 int rtk_launch_within(const rtk_dev_scene *ds, const rtk_point_query *d_queries, size_t num_queries, const rtk_ray_list *list,

@@ -37,3 +37,5 @@ static_assert(sizeof(rtk_dev_filter) == 32 && offsetof(rtk_dev_filter, d_ignore_
 static_assert(sizeof(rtk_dev_rebuild_info) == 40 && offsetof(rtk_dev_rebuild_info, nodes_before) == 8 && offsetof(rtk_dev_rebuild_info, max_depth_before) == 24 &&
 	offsetof(rtk_dev_rebuild_info, rebuild_ms) == 32, "rtk_dev_rebuild_info");
 static_assert(sizeof(rtk_dev_sign_info) == 56 && offsetof(rtk_dev_sign_info, places) == 32 && offsetof(rtk_dev_sign_info, table_ms) == 48, "rtk_dev_sign_info");
+static_assert(sizeof(rtk_winding_opts) == 12 && offsetof(rtk_winding_opts, beta) == 8, "rtk_winding_opts");
+static_assert(sizeof(rtk_dev_winding_info) == 56 && offsetof(rtk_dev_winding_info, table_ms) == 16 && offsetof(rtk_dev_winding_info, total_area) == 48, "rtk_dev_winding_info");
