@@ -1255,6 +1255,83 @@ int rtk_dev_trace_rays_all(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_
 /* (4-byte stack entries per lane the walk keeps on chip before it uses the spill area, for tests) */
 uint32_t rtk_amd_allhits_stack_entries(void);
 
+/* ---- Instanced worlds: rays through placed copies of device scenes ----
+ * Every other call takes ONE rtk_dev_scene: one tree over one flat set of triangles; rtk_dev_scene_build_placed flattens its
+ * placed meshes into such a set, so memory and build time grow with instances x triangles and moving one body refits that
+ * body's triangles. A rtk_dev_world is the second level: a small TOP TREE over the world boxes of INSTANCES, each a
+ * (scene, rtk_placement) pair; a scene is held once however often it is placed, and moving an instance costs a 64-byte
+ * record and a refit of the top tree. Rays only, closest hit and any hit; other query kinds on a world are not there yet.
+ *
+ * THE OBJECT. rtk_dev_world_create(scenes, num_scenes, instance_scene, placements, num_instances): instance i places scene
+ * scenes[instance_scene[i]] by placements[i] (host memory, both arrays; the rule of rtk_dev_scene_build_placed maps the
+ * scene's coordinates to the world's). Synchronous. NULL on failure.
+ *   - THE WORLD BORROWS ITS SCENES and does not own them: FREEING A SCENE THAT A LIVE WORLD NAMES IS THE CALLER'S ERROR.
+ *     The world keeps a small device table per scene (nodes, triangle records, their counts) and the scene's stack_entries,
+ *     copied at create and at every rtk_dev_world_update. A SCENE THAT WAS REFITTED, SPLIT OR REBUILT MUST BE FOLLOWED BY
+ *     rtk_dev_world_update BEFORE THE NEXT TRACE of the world (placements == NULL re-reads the scenes and keeps the placements).
+ *   - Per instance the world holds one 64-byte record (the inverse placement, the scene number, flags), the placement and one
+ *     proxy triangle whose box is the instance's padded world box. The top tree is an ordinary rtk_dev_scene over the proxies,
+ *     which the world owns: rtk_dev_world_top_scene lends it for rtk_dev_scene_get_info, _validate and _quality, nothing else.
+ *   - A DEAD instance is never hit: its placement is not invertible in float (determinant 0 or not finite, an inverse that
+ *     overflows), its scene has no triangles, or its world box is not finite. It keeps its number and a point box.
+ *   - rtk_dev_world_update(w, placements, stream): new placements for the same instances (host or device memory,
+ *     num_instances entries; NULL: keep them), the scenes' tables read again, the top tree refitted. Synchronous, like
+ *     rtk_dev_scene_refit, and like it WRITES the world: no trace of the world may be in flight. rtk_dev_world_rebuild builds
+ *     the top tree again from the current boxes (rtk_dev_scene_rebuild) when instances have moved far; answers do not change.
+ *   - rtk_dev_world_info: dead_instances as of the last create or update; total_device_bytes is the world's own memory (the
+ *     top tree's ledger, the instance records, placements and proxies, the scene table, one counter), not the scenes';
+ *     stack_entries = the top tree's + 1 + the deepest scene's.
+ *
+ * THE RULES (rtk_amd/csrc/rtk_world_rule.h, for the host and the device). The inverse placement is made in double in a stated
+ * order and rounded to float once. An instance's scene is walked with the ray (inv * origin + translation, inv * direction),
+ * every product and sum rounded to float on its own; min_t and max_t are copied and THE DIRECTION IS NOT RENORMALISED: an affine
+ * map keeps the ray parameter, so t is comparable across instances and is the world ray's t.
+ *
+ * THE ANSWER. rtk_dev_world_trace_rays: per ray the rtk_hit_record of the closest candidate over all live instances the filter
+ * lets through, prim the GLOBAL PRIMITIVE ID IN THE INSTANCE'S SCENE, and (d_instances may be NULL) the instance number;
+ * a miss is t = max_t, u = v = 0, RTK_PRIM_NONE in both. A candidate of an instance has bit for bit the t, u, v, prim that
+ * rtk_dev_trace_rays gives for the transformed ray on that instance's scene (exact nodes, rtk's leaf rule; inside one
+ * instance the lowest primitive id wins among bit-equal t). TIES: t is the minimum over all instances; WHEN SEVERAL
+ * INSTANCES ATTAIN BIT-EQUAL t THE RECORD IS THAT OF ONE OF THEM, which one is not promised.
+ * rtk_dev_world_trace_rays_any: one byte per ray, 1 if some instance has a candidate. _counted: the closest form with visit
+ * counts (nodes and leaves of the top tree and of the scenes together, triangles = proxies and triangle records); synchronises.
+ * `list` as for the listed traces (a slot that is not listed is not written; an id >= n is skipped). rtk_world_filter:
+ * d_instance_mask (bit i set = instance i is walked; instances at and beyond instance_mask_bits are not) and d_ignore_instance
+ * (per ray slot, an instance that ray never enters: the instance a bounce starts on); both device memory, both optional.
+ * Asynchronous on `stream`, nothing is read back; the scratch set and the launch-error word are the top tree's for that stream
+ * (rtk_dev_world_trace_status waits and reports it). The top tree never culls an instance the walk of its scene would hit
+ * as long as every placement's 3 x 3 part has a condition number of at most 100 (DESIGN.md 3.23 derives the padding of the
+ * boxes and the margin of the top tree's slab test); beyond that nothing is promised but no fault and no access out of range.
+ *
+ * Refused before any HIP call (create: NULL; else RTK_AMD_ERR_BAD_ARG): NULL arguments, a struct_size that is too small,
+ * flags != 0, num_instances == 0 or >= 2^31, instance_scene[i] >= num_scenes, scenes on different devices, a mask without
+ * bits, n >= 2^32, a bad list; then a device other than the calling thread's current one, as for every launch. */
+typedef struct rtk_dev_world rtk_dev_world;
+typedef struct rtk_dev_world_info {
+	uint64_t num_scenes, num_instances, dead_instances;   /* dead: placement not invertible, or its scene has no triangles */
+	uint64_t top_nodes, total_device_bytes;               /* the world's own memory, not the scenes' */
+	uint32_t top_max_depth, stack_entries;                /* entries a ray can need: top + 1 + the deepest scene's */
+	double build_ms, update_ms;
+} rtk_dev_world_info;
+rtk_dev_world *rtk_dev_world_create(rtk_dev_scene *const *scenes, size_t num_scenes,
+	const uint32_t *instance_scene, const rtk_placement *placements, size_t num_instances);
+int rtk_dev_world_update(rtk_dev_world *w, const rtk_placement *placements, void *stream);  /* host or device pointer; NULL: keep the placements, re-read the scenes */
+int rtk_dev_world_rebuild(rtk_dev_world *w, void *stream);   /* the top tree built again from the current boxes */
+int rtk_dev_world_get_info(const rtk_dev_world *w, rtk_dev_world_info *out);
+void rtk_dev_world_free(rtk_dev_world *w);
+const rtk_dev_scene *rtk_dev_world_top_scene(const rtk_dev_world *w);   /* borrowed; replaced by an update of a one-instance world */
+int rtk_dev_world_trace_status(const rtk_dev_world *w, void *stream);   /* rtk_dev_trace_status of the top tree */
+typedef struct rtk_world_filter { uint32_t struct_size, flags; const uint32_t *d_instance_mask; uint32_t instance_mask_bits;
+                                  const uint32_t *d_ignore_instance; /* per ray slot */ } rtk_world_filter;
+int rtk_dev_world_trace_rays(const rtk_dev_world *w, const rtk_ray *d_rays, size_t n, const rtk_ray_list *list,
+	const rtk_world_filter *filter, rtk_hit_record *d_records, uint32_t *d_instances, void *stream);
+int rtk_dev_world_trace_rays_any(const rtk_dev_world *w, const rtk_ray *d_rays, size_t n, const rtk_ray_list *list,
+	const rtk_world_filter *filter, uint8_t *d_blocked, void *stream);
+int rtk_dev_world_trace_rays_counted(const rtk_dev_world *w, const rtk_ray *d_rays, size_t n, const rtk_world_filter *filter,
+	rtk_hit_record *d_records, uint32_t *d_instances, rtk_trace_counters *out);
+/* (8-byte stack entries per lane the walk keeps on chip before it uses the spill area, for tests) */
+uint32_t rtk_amd_world_stack_entries(void);
+
 /* Waits for `stream` and reports whether a launch of this scene on it overflowed a traversal stack
  * (RTK_AMD_ERR_BAD_SCENE; impossible for a validated tree -- the push is dropped, never written out of bounds). */
 int rtk_dev_trace_status(const rtk_dev_scene *ds, void *stream);

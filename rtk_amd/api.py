@@ -111,6 +111,22 @@ def make_winding_opts(beta=2.0, exact=False):
     return o
 
 
+class WorldInfo(C.Structure):
+    """rtk_dev_world_info: the figures of an instanced world (rtk_dev_world_get_info)."""
+    _fields_ = [("num_scenes", C.c_uint64), ("num_instances", C.c_uint64), ("dead_instances", C.c_uint64), ("top_nodes", C.c_uint64),
+                ("total_device_bytes", C.c_uint64), ("top_max_depth", C.c_uint32), ("stack_entries", C.c_uint32), ("build_ms", C.c_double),
+                ("update_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: (float(getattr(self, k)) if t is C.c_double else int(getattr(self, k))) for k, t in self._fields_}
+
+
+class WorldFilter(C.Structure):
+    """rtk_world_filter: which instances the rays of a world trace may enter."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("d_instance_mask", C.c_void_p), ("instance_mask_bits", C.c_uint32),
+                ("d_ignore_instance", C.c_void_p)]
+
+
 class TraceOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("image_width", C.c_uint32),
                 ("image_height", C.c_uint32), ("refill_min", C.c_uint32), ("blocks_per_cu", C.c_uint32),
@@ -214,6 +230,9 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_dev_scene_prepare_signs", "rtk_dev_scene_pseudonormals", "rtk_dev_signed_distances",
                      "rtk_dev_scene_prepare_winding", "rtk_dev_scene_winding_moments", "rtk_dev_winding_numbers",
                      "rtk_dev_winding_numbers_counted", "rtk_amd_winding_stack_entries",
+                     "rtk_dev_world_create", "rtk_dev_world_update", "rtk_dev_world_rebuild", "rtk_dev_world_get_info", "rtk_dev_world_free",
+                     "rtk_dev_world_top_scene", "rtk_dev_world_trace_status", "rtk_dev_world_trace_rays", "rtk_dev_world_trace_rays_any",
+                     "rtk_dev_world_trace_rays_counted", "rtk_amd_world_stack_entries",
                      "rtk_dev_trace_rays_count", "rtk_dev_trace_rays_all", "rtk_amd_allhits_stack_entries",
                      "rtk_dev_triangles_within_count", "rtk_dev_triangles_within_all", "rtk_dev_triangles_within_counted",
                      "rtk_amd_within_stack_entries",
@@ -313,6 +332,28 @@ def lib():
     L.rtk_dev_winding_numbers_counted.restype = C.c_int
     L.rtk_amd_winding_stack_entries.argtypes = []
     L.rtk_amd_winding_stack_entries.restype = C.c_uint32
+    L.rtk_dev_world_create.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(Placement), C.c_size_t]
+    L.rtk_dev_world_create.restype = C.c_void_p
+    L.rtk_dev_world_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtk_dev_world_update.restype = C.c_int
+    L.rtk_dev_world_rebuild.argtypes = [C.c_void_p, C.c_void_p]
+    L.rtk_dev_world_rebuild.restype = C.c_int
+    L.rtk_dev_world_get_info.argtypes = [C.c_void_p, C.POINTER(WorldInfo)]
+    L.rtk_dev_world_get_info.restype = C.c_int
+    L.rtk_dev_world_free.argtypes = [C.c_void_p]
+    L.rtk_dev_world_free.restype = None
+    L.rtk_dev_world_top_scene.argtypes = [C.c_void_p]
+    L.rtk_dev_world_top_scene.restype = C.c_void_p
+    L.rtk_dev_world_trace_status.argtypes = [C.c_void_p, C.c_void_p]
+    L.rtk_dev_world_trace_status.restype = C.c_int
+    L.rtk_dev_world_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(WorldFilter), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtk_dev_world_trace_rays.restype = C.c_int
+    L.rtk_dev_world_trace_rays_any.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(WorldFilter), C.c_void_p, C.c_void_p]
+    L.rtk_dev_world_trace_rays_any.restype = C.c_int
+    L.rtk_dev_world_trace_rays_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(WorldFilter), C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
+    L.rtk_dev_world_trace_rays_counted.restype = C.c_int
+    L.rtk_amd_world_stack_entries.argtypes = []
+    L.rtk_amd_world_stack_entries.restype = C.c_uint32
     L.rtk_dev_sweep_spheres.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.POINTER(DevFilter), C.c_void_p]
     L.rtk_dev_sweep_spheres.restype = C.c_int
@@ -2186,6 +2227,171 @@ class DeviceScene:
                                                        C.byref(opts) if opts is not None else None, C.byref(ctr)),
                "rtk_dev_trace_rays_packet_counted")
         return d_rec.cpu().numpy().view(HIT_RECORD_DTYPE), ctr.as_dict()
+
+
+class DeviceWorld:
+    """An instanced world (rtk_dev_world*; include/rtk_amd.h, "Instanced worlds"): placed copies of device scenes under a small
+    top tree, for rays. The object keeps its scenes alive; a scene that was refitted, split or rebuilt must be followed by
+    update() before the next trace."""
+
+    def __init__(self, handle, scenes):
+        if not handle:
+            raise RtkError("world creation failed: " + last_error())
+        self.handle = C.c_void_p(handle)
+        self.scenes = list(scenes)
+        self._keep = []
+
+    @classmethod
+    def create(cls, scenes, instance_scene, placements):
+        """scenes: DeviceScene objects; instance_scene: for every instance the index of its scene; placements: one 3 x 4 matrix
+        per instance, array-like (n, 3, 4) or (n, 12) float32, mapping the scene's coordinates to the world's."""
+        _torch()
+        scenes = list(scenes)
+        which = np.ascontiguousarray(instance_scene, np.uint32).reshape(-1)
+        ptr, _keep = placement_ptr(placements, which.size)
+        handles = (C.c_void_p * max(len(scenes), 1))(*[s.handle for s in scenes])
+        return cls(lib().rtk_dev_world_create(handles, len(scenes), which.ctypes.data_as(C.POINTER(C.c_uint32)), ptr, which.size), scenes)
+
+    def update(self, placements=None):
+        """New placements for the same instances (array-like as for create, or a float32 cuda tensor of n * 12 values used where
+        it is), or None: keep them and read the scenes again. Synchronous; no trace of the world may be in flight."""
+        _torch()
+        if placements is None:
+            p = None
+        elif hasattr(placements, "data_ptr"):
+            p = C.c_void_p(placements.data_ptr())
+        else:
+            arr = placement_array(placements, self.info()["num_instances"])
+            p = C.c_void_p(arr.ctypes.data)
+        _check(lib().rtk_dev_world_update(self.handle, p, _stream_ptr()), "rtk_dev_world_update")
+
+    def rebuild(self):
+        """The top tree built again from the instances' current boxes (rtk_dev_world_rebuild); no answer changes."""
+        _torch()
+        _check(lib().rtk_dev_world_rebuild(self.handle, _stream_ptr()), "rtk_dev_world_rebuild")
+
+    def info(self):
+        i = WorldInfo()
+        _check(lib().rtk_dev_world_get_info(self.handle, C.byref(i)), "rtk_dev_world_get_info")
+        return i.as_dict()
+
+    def top_scene_info(self):
+        """rtk_dev_scene_get_info of the top tree (borrowed through rtk_dev_world_top_scene) as a dict."""
+        i = SceneInfo()
+        _check(lib().rtk_dev_scene_get_info(C.c_void_p(lib().rtk_dev_world_top_scene(self.handle)), C.byref(i)), "rtk_dev_scene_get_info")
+        return i.as_dict()
+
+    def status(self):
+        """Waits for the current stream and raises if a launch of this world on it overflowed a traversal stack."""
+        _check(lib().rtk_dev_world_trace_status(self.handle, _stream_ptr()), "rtk_dev_world_trace_status")
+
+    def free(self):
+        if self.handle:
+            lib().rtk_dev_world_free(self.handle)
+            self.handle = None
+        self.scenes = []
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def _filter(self, instance_mask, ignore_instance):
+        """(WorldFilter or None, the tensors it points into). instance_mask: bools per instance; ignore_instance: a cuda tensor of
+        one 32-bit word per ray slot (used as it is) or array-like."""
+        if instance_mask is None and ignore_instance is None:
+            return None, []
+        torch = _torch()
+        f = WorldFilter()
+        f.struct_size = C.sizeof(WorldFilter)
+        keep = []
+        if instance_mask is not None:
+            bits = np.ascontiguousarray(instance_mask, bool).reshape(-1)
+            words = np.zeros((bits.size + 31) // 32, np.uint32)
+            for i in np.flatnonzero(bits):
+                words[i >> 5] |= np.uint32(1 << (int(i) & 31))
+            d = torch.from_numpy(words.view(np.int32)).cuda()
+            f.d_instance_mask, f.instance_mask_bits = d.data_ptr(), bits.size
+            keep.append(d)
+        if ignore_instance is not None:
+            d = ignore_instance if hasattr(ignore_instance, "data_ptr") else torch.from_numpy(np.ascontiguousarray(ignore_instance, np.uint32).view(np.int32)).cuda()
+            f.d_ignore_instance = d.data_ptr()
+            keep.append(d)
+        return f, keep
+
+    def trace_device(self, d_rays, n, d_records=None, d_instances=None, count=None, ids=None, instance_mask=None, ignore_instance=None):
+        """Closest hits of n rays (RAY_DTYPE bytes on the device) over all instances: returns (d_records, d_instances), a uint8 cuda
+        tensor of HIT_RECORD_DTYPE records (prim: the primitive id in the instance's scene) and an int32 cuda tensor of instance
+        numbers (-1 = RTK_PRIM_NONE on a miss). count / ids: cuda int64 tensors naming the rays to trace; slots that are not listed
+        are not written. Asynchronous on the current stream."""
+        torch = _torch()
+        if d_records is None:
+            d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        if d_instances is None:
+            d_instances = torch.empty(n, dtype=torch.int32, device="cuda")
+        if ids is not None and count is None:
+            raise RtkError("DeviceWorld.trace_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        f, _keep = self._filter(instance_mask, ignore_instance)
+        _check(lib().rtk_dev_world_trace_rays(self.handle, C.c_void_p(d_rays.data_ptr()), n, C.byref(l) if l is not None else None,
+                                              C.byref(f) if f is not None else None, C.c_void_p(d_records.data_ptr()),
+                                              C.c_void_p(d_instances.data_ptr()), _stream_ptr()), "rtk_dev_world_trace_rays")
+        self._keep = _keep
+        return d_records, d_instances
+
+    def trace_any_device(self, d_rays, n, d_blocked=None, count=None, ids=None, instance_mask=None, ignore_instance=None):
+        """The any-hit form of trace_device: one byte per ray, 1 where some instance has a candidate."""
+        torch = _torch()
+        if d_blocked is None:
+            d_blocked = torch.empty(n, dtype=torch.uint8, device="cuda")
+        if ids is not None and count is None:
+            raise RtkError("DeviceWorld.trace_any_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        f, _keep = self._filter(instance_mask, ignore_instance)
+        _check(lib().rtk_dev_world_trace_rays_any(self.handle, C.c_void_p(d_rays.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                  C.byref(f) if f is not None else None, C.c_void_p(d_blocked.data_ptr()), _stream_ptr()),
+               "rtk_dev_world_trace_rays_any")
+        self._keep = _keep
+        return d_blocked
+
+    def trace_counted(self, rays, instance_mask=None, ignore_instance=None):
+        """trace of all rays on the null stream, synchronous, with the visit counts of rtk_dev_world_trace_rays_counted: returns
+        (records, instances, counts dict)."""
+        torch = _torch()
+        rays = np.ascontiguousarray(rays)
+        n = rays.shape[0]
+        d_rays = to_device(rays)
+        d_rec = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        d_inst = torch.empty(n, dtype=torch.int32, device="cuda")
+        ctr = TraceCounters()
+        f, _keep = self._filter(instance_mask, ignore_instance)
+        torch.cuda.synchronize()
+        _check(lib().rtk_dev_world_trace_rays_counted(self.handle, C.c_void_p(d_rays.data_ptr()), n, C.byref(f) if f is not None else None,
+                                                      C.c_void_p(d_rec.data_ptr()), C.c_void_p(d_inst.data_ptr()), C.byref(ctr)),
+               "rtk_dev_world_trace_rays_counted")
+        return d_rec.cpu().numpy().view(HIT_RECORD_DTYPE), d_inst.cpu().numpy().view(np.uint32), ctr.as_dict()
+
+    def trace(self, rays, instance_mask=None, ignore_instance=None):
+        """rays: numpy RAY_DTYPE array. Returns (records, instances): HIT_RECORD_DTYPE records and uint32 instance numbers
+        (0xffffffff on a miss). Waits for the stream."""
+        rays = np.ascontiguousarray(rays)
+        n = rays.shape[0]
+        if n == 0:
+            return np.zeros(0, HIT_RECORD_DTYPE), np.zeros(0, np.uint32)
+        d_rec, d_inst = self.trace_device(to_device(rays), n, instance_mask=instance_mask, ignore_instance=ignore_instance)
+        self.status()
+        return d_rec.cpu().numpy().view(HIT_RECORD_DTYPE), d_inst.cpu().numpy().view(np.uint32)
+
+    def trace_any(self, rays, instance_mask=None, ignore_instance=None):
+        """rays: numpy RAY_DTYPE array. Returns a numpy bool array: the ray is blocked by some instance. Waits for the stream."""
+        rays = np.ascontiguousarray(rays)
+        n = rays.shape[0]
+        if n == 0:
+            return np.zeros(0, bool)
+        d = self.trace_any_device(to_device(rays), n, instance_mask=instance_mask, ignore_instance=ignore_instance)
+        self.status()
+        return d.cpu().numpy().astype(bool)
 
 
 # -- the reference's own entry points, host pointers (reference rtk.h:126-130) --

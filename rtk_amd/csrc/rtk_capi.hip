@@ -165,6 +165,26 @@ extern "C" int rtk_dev_trace_rays_any_filtered(const rtk_dev_scene *ds, const rt
 	return rtk_launch_trace(ds, c);
 }
 
+// Rays through a world (rtk_world.hip): the three doors of one launch
+extern "C" int rtk_dev_world_trace_rays(const rtk_dev_world *w, const rtk_ray *d_rays, size_t n, const rtk_ray_list *list,
+	const rtk_world_filter *filter, rtk_hit_record *d_records, uint32_t *d_instances, void *stream)
+{
+	return rtk_launch_world(w, d_rays, n, list, filter, d_records, d_instances, nullptr, false, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_world_trace_rays_any(const rtk_dev_world *w, const rtk_ray *d_rays, size_t n, const rtk_ray_list *list,
+	const rtk_world_filter *filter, uint8_t *d_blocked, void *stream)
+{
+	return rtk_launch_world(w, d_rays, n, list, filter, nullptr, nullptr, d_blocked, true, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_world_trace_rays_counted(const rtk_dev_world *w, const rtk_ray *d_rays, size_t n, const rtk_world_filter *filter,
+	rtk_hit_record *d_records, uint32_t *d_instances, rtk_trace_counters *out)
+{
+	if (!out) { rtk_set_error("rtk_dev_world_trace_rays_counted: NULL counters"); return RTK_AMD_ERR_BAD_ARG; }
+	return rtk_launch_world(w, d_rays, n, nullptr, filter, d_records, d_instances, nullptr, false, nullptr, out);
+}
+
 // Listed batches (rtk_ray_list): everything about the list that the host can see is refused here, before anything is launched
 static int listed_trace(const char *who, const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t num_rays, const rtk_ray_list *list,
 	rtk_hit_record *d_hits, uint8_t *d_occluded, bool any_hit, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream)

@@ -140,6 +140,15 @@ struct WindingTable {
 	rtk_dev_winding_info info = {};            // as the making left it (table_ms: of that making)
 };
 
+// One instance of a world (rtk_world.hip, the rules: rtk_world_rule.h): the inverse of its placement row by row, the scene it places
+// and its flags (bit 0: dead -- the placement is not invertible, its scene has no triangles or its world box is not finite).
+// Half a 128-byte line, read by a ray only when it enters the instance's box.
+struct DevWorldInstance {
+	float inv[12];
+	uint32_t scene, flags;
+	uint32_t pad[2];
+};
+
 static inline void *rtk_dev_malloc(size_t bytes) { void *p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; }
 static inline void rtk_dev_free(void *p) { (void)hipFree(p); }
 
@@ -423,6 +432,11 @@ int rtk_launch_capsule(const rtk_dev_scene *ds, const rtk_capsule_sweep *d_sweep
 int rtk_launch_obbsweep(const rtk_dev_scene *ds, const rtk_obb_sweep *d_sweeps, size_t num_sweeps, const rtk_ray_list *list,
 	rtk_hit_record *d_records, float *d_centres, float *d_normals, uint8_t *d_blocked, bool any_hit, const rtk_dev_filter *filter,
 	hipStream_t stream, rtk_trace_counters *counted = nullptr);
+// -- rtk_dev_world_trace_rays / _any / _counted (rtk_world.hip) --
+// the closest form writes d_records (d_instances or NULL), the any-hit form d_blocked; a non-null `counted` makes it the counting
+// form of the closest one (synchronises the stream)
+int rtk_launch_world(const rtk_dev_world *w, const rtk_ray *d_rays, size_t n, const rtk_ray_list *list, const rtk_world_filter *filter,
+	rtk_hit_record *d_records, uint32_t *d_instances, uint8_t *d_blocked, bool any_hit, hipStream_t stream, rtk_trace_counters *counted = nullptr);
 // -- the look for an image nobody announced (rtk_detect.hip) --
 int rtk_detect_image(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, hipStream_t stream, uint32_t *w_out, uint32_t *h_out);
 // -- hit records to full hits, and rtk_trace_ray's one-ray launch (rtk_expand.hip) --

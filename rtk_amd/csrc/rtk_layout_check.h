@@ -39,3 +39,8 @@ static_assert(sizeof(rtk_dev_rebuild_info) == 40 && offsetof(rtk_dev_rebuild_inf
 static_assert(sizeof(rtk_dev_sign_info) == 56 && offsetof(rtk_dev_sign_info, places) == 32 && offsetof(rtk_dev_sign_info, table_ms) == 48, "rtk_dev_sign_info");
 static_assert(sizeof(rtk_winding_opts) == 12 && offsetof(rtk_winding_opts, beta) == 8, "rtk_winding_opts");
 static_assert(sizeof(rtk_dev_winding_info) == 56 && offsetof(rtk_dev_winding_info, table_ms) == 16 && offsetof(rtk_dev_winding_info, total_area) == 48, "rtk_dev_winding_info");
+static_assert(sizeof(rtk_world_filter) == 32 && offsetof(rtk_world_filter, d_instance_mask) == 8 && offsetof(rtk_world_filter, d_ignore_instance) == 24, "rtk_world_filter");
+static_assert(sizeof(rtk_dev_world_info) == 64 && offsetof(rtk_dev_world_info, top_nodes) == 24 && offsetof(rtk_dev_world_info, top_max_depth) == 40 &&
+	offsetof(rtk_dev_world_info, build_ms) == 48, "rtk_dev_world_info");
+// (rtk_dev.h, which rtk_capi.hip includes before this file: the record k_world reads as four 16-byte pieces)
+static_assert(sizeof(DevWorldInstance) == 64 && offsetof(DevWorldInstance, scene) == 48 && offsetof(DevWorldInstance, flags) == 52, "one 64-byte record per instance of a world");

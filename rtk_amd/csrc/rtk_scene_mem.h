@@ -21,6 +21,8 @@
 //   rtk_dev_scene_rebuild of a blob, d_vidx_in  num_tris * 12, by Build::dev_alloc    the same
 //   rtk_scene_pseudonormals (rtk_sign.hip)      max(num_prims, 1) * 72                num_prims * 72
 //   rtk_scene_winding_table (rtk_winding.hip)   max(num_nodes, 1) * 128               num_nodes * 128
+//   rtk_dev_world_create (rtk_world.hip), in    instances * (64 + 48 + 36), scenes    the same
+//   the WORLD's ledger, not a scene's           * 24, one 8-byte counter
 //
 // The allocator and its free are the owner's (hipMalloc / hipFree for a scene, malloc / free for tests/scene_mem_driver.cpp).
 // One lock of its own: the side arrays arrive under another mutex of the scene than the tables of a refit or a measurement.
