@@ -7,6 +7,7 @@ is present the calls raise.
 
 torch is used only as plumbing: device buffers and the current HIP stream.
 """
+import collections
 import ctypes as C
 import os
 
@@ -249,6 +250,15 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_dev_sweep_capsules", "rtk_dev_sweep_capsules_any", "rtk_dev_sweep_capsules_counted", "rtk_amd_capsule_stack_entries",
                      "rtk_dev_sweep_obbs", "rtk_dev_sweep_obbs_any", "rtk_dev_sweep_obbs_counted", "rtk_amd_obbsweep_stack_entries"]
 
+# the four swept shapes (one walk, rtk_amd/csrc/rtk_sweep_walk.h): the name in the Python methods, the C symbol stem, the keyword
+# names of the two 3-float side arrays, the query record, the symbol that tells the on-chip stack entries
+Sweep = collections.namedtuple("Sweep", "name stem sides dtype stack_entries")
+SWEEPS = {f.name: f for f in (
+    Sweep("spheres", "rtk_dev_sweep_spheres", ("d_points", "d_centres"), SPHERE_SWEEP_DTYPE, "rtk_amd_sweep_stack_entries"),
+    Sweep("boxes", "rtk_dev_sweep_boxes", ("d_centres", "d_normals"), BOX_SWEEP_DTYPE, "rtk_amd_boxsweep_stack_entries"),
+    Sweep("capsules", "rtk_dev_sweep_capsules", ("d_points", "d_axis_points"), CAPSULE_SWEEP_DTYPE, "rtk_amd_capsule_stack_entries"),
+    Sweep("obbs", "rtk_dev_sweep_obbs", ("d_centres", "d_normals"), OBB_SWEEP_DTYPE, "rtk_amd_obbsweep_stack_entries"))}
+
 _lib = None
 
 
@@ -354,46 +364,14 @@ def lib():
     L.rtk_dev_world_trace_rays_counted.restype = C.c_int
     L.rtk_amd_world_stack_entries.argtypes = []
     L.rtk_amd_world_stack_entries.restype = C.c_uint32
-    L.rtk_dev_sweep_spheres.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.POINTER(DevFilter), C.c_void_p]
-    L.rtk_dev_sweep_spheres.restype = C.c_int
-    L.rtk_dev_sweep_spheres_any.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.POINTER(DevFilter), C.c_void_p]
-    L.rtk_dev_sweep_spheres_any.restype = C.c_int
-    L.rtk_dev_sweep_spheres_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter),
-                                                C.POINTER(TraceCounters)]
-    L.rtk_dev_sweep_spheres_counted.restype = C.c_int
-    L.rtk_amd_sweep_stack_entries.argtypes = []
-    L.rtk_amd_sweep_stack_entries.restype = C.c_uint32
-    L.rtk_dev_sweep_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.POINTER(DevFilter), C.c_void_p]
-    L.rtk_dev_sweep_boxes.restype = C.c_int
-    L.rtk_dev_sweep_boxes_any.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.POINTER(DevFilter), C.c_void_p]
-    L.rtk_dev_sweep_boxes_any.restype = C.c_int
-    L.rtk_dev_sweep_boxes_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter),
-                                              C.POINTER(TraceCounters)]
-    L.rtk_dev_sweep_boxes_counted.restype = C.c_int
-    L.rtk_amd_boxsweep_stack_entries.argtypes = []
-    L.rtk_amd_boxsweep_stack_entries.restype = C.c_uint32
-    L.rtk_dev_sweep_capsules.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.POINTER(DevFilter), C.c_void_p]
-    L.rtk_dev_sweep_capsules.restype = C.c_int
-    L.rtk_dev_sweep_capsules_any.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.POINTER(DevFilter), C.c_void_p]
-    L.rtk_dev_sweep_capsules_any.restype = C.c_int
-    L.rtk_dev_sweep_capsules_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter),
-                                                 C.POINTER(TraceCounters)]
-    L.rtk_dev_sweep_capsules_counted.restype = C.c_int
-    L.rtk_amd_capsule_stack_entries.argtypes = []
-    L.rtk_amd_capsule_stack_entries.restype = C.c_uint32
-    L.rtk_dev_sweep_obbs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.POINTER(DevFilter), C.c_void_p]
-    L.rtk_dev_sweep_obbs.restype = C.c_int
-    L.rtk_dev_sweep_obbs_any.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.POINTER(DevFilter), C.c_void_p]
-    L.rtk_dev_sweep_obbs_any.restype = C.c_int
-    L.rtk_dev_sweep_obbs_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter),
-                                             C.POINTER(TraceCounters)]
-    L.rtk_dev_sweep_obbs_counted.restype = C.c_int
-    L.rtk_amd_obbsweep_stack_entries.argtypes = []
-    L.rtk_amd_obbsweep_stack_entries.restype = C.c_uint32
+    for fam in SWEEPS.values():
+        fn, fn_any, fn_counted, entries = (getattr(L, name) for name in (fam.stem, fam.stem + "_any", fam.stem + "_counted", fam.stack_entries))
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter), C.c_void_p]
+        fn_any.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.POINTER(DevFilter), C.c_void_p]
+        fn_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter), C.POINTER(TraceCounters)]
+        fn.restype = fn_any.restype = fn_counted.restype = C.c_int
+        entries.argtypes = []
+        entries.restype = C.c_uint32
     L.rtk_dev_triangles_within_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p]
     L.rtk_dev_triangles_within_count.restype = C.c_int
     L.rtk_dev_triangles_within_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p,
@@ -997,7 +975,8 @@ class DeviceScene:
         and contains needs no table at all."""
         return self.winding_numbers(points, beta=beta) > 0.5
 
-    # -- sphere sweeps (rtk_dev_sweep_spheres / _any): asynchronous on the current stream, nothing here waits for it --
+    # -- swept shapes (rtk_dev_sweep_spheres / _boxes / _capsules / _obbs, each with _any and _counted; a row of SWEEPS each):
+    # asynchronous on the current stream, nothing here waits for it --
 
     def _sweep_filter(self, n, mesh_mask, ignore_prim):
         """(DevFilter or None, the tensors it points into). mesh_mask: bools per mesh; ignore_prim: a cuda tensor of n 32-bit
@@ -1011,6 +990,85 @@ class DeviceScene:
             return f, keep + [ignore_prim]
         return self._device_filter(n, mesh_mask, ignore_prim, None)
 
+    def _sweep_device(self, fam, d_sweeps, n, d_records, d_side0, d_side1, count, ids, mesh_mask, ignore_prim):
+        """sweep_<fam.name>_device; the two side arrays are fam.sides, in that order"""
+        torch = _torch()
+        if d_records is None:
+            d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        if d_side0 is None:
+            d_side0 = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        if d_side1 is None:
+            d_side1 = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        if ids is not None and count is None:
+            raise RtkError("sweep_%s_device: ids without count (a list's length lives on the device)" % fam.name)
+        l = make_ray_list(count, ids) if count is not None else None
+        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
+        _check(getattr(lib(), fam.stem)(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
+                                        C.c_void_p(d_records.data_ptr()), C.c_void_p(d_side0.data_ptr()), C.c_void_p(d_side1.data_ptr()),
+                                        C.byref(f) if f is not None else None, _stream_ptr()), fam.stem)
+        return d_records, d_side0, d_side1
+
+    def _sweep_any_device(self, fam, d_sweeps, n, d_blocked, count, ids, mesh_mask, ignore_prim):
+        """sweep_<fam.name>_any_device"""
+        torch = _torch()
+        if d_blocked is None:
+            d_blocked = torch.empty(n, dtype=torch.uint8, device="cuda")
+        if ids is not None and count is None:
+            raise RtkError("sweep_%s_any_device: ids without count (a list's length lives on the device)" % fam.name)
+        l = make_ray_list(count, ids) if count is not None else None
+        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
+        _check(getattr(lib(), fam.stem + "_any")(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                 C.c_void_p(d_blocked.data_ptr()), C.byref(f) if f is not None else None, _stream_ptr()),
+               fam.stem + "_any")
+        return d_blocked
+
+    def _sweep_counted(self, fam, d_sweeps, n, mesh_mask, ignore_prim):
+        """sweep_<fam.name>_counted"""
+        torch = _torch()
+        d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        d_side0 = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        d_side1 = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        ctr = TraceCounters()
+        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
+        torch.cuda.synchronize()
+        _check(getattr(lib(), fam.stem + "_counted")(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.c_void_p(d_records.data_ptr()),
+                                                     C.c_void_p(d_side0.data_ptr()), C.c_void_p(d_side1.data_ptr()),
+                                                     C.byref(f) if f is not None else None, C.byref(ctr)), fam.stem + "_counted")
+        return d_records, d_side0, d_side1, ctr.as_dict()
+
+    @staticmethod
+    def _sweep_array(fam, origins, directions, max_t, min_t, **fields):
+        """fam.dtype records: the path, and every other field (scalars or one per query) by its name"""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        s = np.zeros(n, fam.dtype)
+        s["origin"] = o
+        s["direction"] = np.broadcast_to(np.asarray(directions, np.float32), (n, 3))
+        s["min_t"] = np.broadcast_to(np.asarray(min_t, np.float32), (n,))
+        s["max_t"] = RTK_INF if max_t is None else np.broadcast_to(np.asarray(max_t, np.float32), (n,))
+        for name, value in fields.items():
+            s[name] = np.broadcast_to(np.asarray(value, np.float32), s[name].shape)
+        return s
+
+    def _sweep_host(self, fam, s, mesh_mask, ignore_prim):
+        """The closest form of host records s: (records, side array 0, side array 1) as numpy arrays"""
+        n = s.shape[0]
+        if n == 0:
+            return np.zeros(0, HIT_RECORD_DTYPE), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
+        d_rec, d_0, d_1 = self._sweep_device(fam, to_device(s), n, None, None, None, None, None, mesh_mask, ignore_prim)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return (d_rec.cpu().numpy().view(HIT_RECORD_DTYPE), d_0.cpu().numpy().view(np.float32).reshape(n, 3),
+                d_1.cpu().numpy().view(np.float32).reshape(n, 3))
+
+    def _sweep_blocked_host(self, fam, s, mesh_mask, ignore_prim):
+        """The any-hit form of host records s: a bool array"""
+        n = s.shape[0]
+        if n == 0:
+            return np.zeros(0, bool)
+        d_blocked = self._sweep_any_device(fam, to_device(s), n, None, None, None, mesh_mask, ignore_prim)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return d_blocked.cpu().numpy() != 0
+
     def sweep_spheres_device(self, d_sweeps, n, d_records=None, d_points=None, d_centres=None, count=None, ids=None, mesh_mask=None,
                              ignore_prim=None):
         """The first contact of each of n moving balls (SPHERE_SWEEP_DTYPE bytes on the device; include/rtk_amd.h, "Sphere
@@ -1018,88 +1076,29 @@ class DeviceScene:
         floats per query each (the contact point on the triangle, the ball's centre at the contact). count / ids: cuda int64
         tensors naming the queries to answer, as for closest_points_device; slots that are not listed are not written. mesh_mask:
         bools per mesh; ignore_prim: one id per query slot (a cuda tensor, or array-like)."""
-        torch = _torch()
-        if d_records is None:
-            d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
-        if d_points is None:
-            d_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        if d_centres is None:
-            d_centres = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        if ids is not None and count is None:
-            raise RtkError("sweep_spheres_device: ids without count (a list's length lives on the device)")
-        l = make_ray_list(count, ids) if count is not None else None
-        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
-        _check(lib().rtk_dev_sweep_spheres(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
-                                           C.c_void_p(d_records.data_ptr()), C.c_void_p(d_points.data_ptr()), C.c_void_p(d_centres.data_ptr()),
-                                           C.byref(f) if f is not None else None, _stream_ptr()), "rtk_dev_sweep_spheres")
-        return d_records, d_points, d_centres
+        return self._sweep_device(SWEEPS["spheres"], d_sweeps, n, d_records, d_points, d_centres, count, ids, mesh_mask, ignore_prim)
 
     def sweep_spheres_any_device(self, d_sweeps, n, d_blocked=None, count=None, ids=None, mesh_mask=None, ignore_prim=None):
         """The any-hit form of sweep_spheres_device: one byte per query, 1 where the path is blocked, in the queries' own slots."""
-        torch = _torch()
-        if d_blocked is None:
-            d_blocked = torch.empty(n, dtype=torch.uint8, device="cuda")
-        if ids is not None and count is None:
-            raise RtkError("sweep_spheres_any_device: ids without count (a list's length lives on the device)")
-        l = make_ray_list(count, ids) if count is not None else None
-        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
-        _check(lib().rtk_dev_sweep_spheres_any(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
-                                               C.c_void_p(d_blocked.data_ptr()), C.byref(f) if f is not None else None, _stream_ptr()),
-               "rtk_dev_sweep_spheres_any")
-        return d_blocked
+        return self._sweep_any_device(SWEEPS["spheres"], d_sweeps, n, d_blocked, count, ids, mesh_mask, ignore_prim)
 
     def sweep_spheres_counted(self, d_sweeps, n, mesh_mask=None, ignore_prim=None):
         """sweep_spheres_device of all n queries on the null stream, synchronous, with the visit counts of
         rtk_dev_sweep_spheres_counted: returns (d_records, d_points, d_centres, counts dict)."""
-        torch = _torch()
-        d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
-        d_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        d_centres = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        ctr = TraceCounters()
-        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
-        torch.cuda.synchronize()
-        _check(lib().rtk_dev_sweep_spheres_counted(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.c_void_p(d_records.data_ptr()),
-                                                   C.c_void_p(d_points.data_ptr()), C.c_void_p(d_centres.data_ptr()),
-                                                   C.byref(f) if f is not None else None, C.byref(ctr)), "rtk_dev_sweep_spheres_counted")
-        return d_records, d_points, d_centres, ctr.as_dict()
-
-    @staticmethod
-    def _sweep_array(origins, directions, radius, max_t, min_t):
-        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
-        n = o.shape[0]
-        s = np.zeros(n, SPHERE_SWEEP_DTYPE)
-        s["origin"] = o
-        s["direction"] = np.broadcast_to(np.asarray(directions, np.float32), (n, 3))
-        s["min_t"] = np.broadcast_to(np.asarray(min_t, np.float32), (n,))
-        s["max_t"] = RTK_INF if max_t is None else np.broadcast_to(np.asarray(max_t, np.float32), (n,))
-        s["radius"] = np.broadcast_to(np.asarray(radius, np.float32), (n,))
-        return s
+        return self._sweep_counted(SWEEPS["spheres"], d_sweeps, n, mesh_mask, ignore_prim)
 
     def sweep_spheres(self, origins, directions, radius, max_t=None, min_t=0.0, mesh_mask=None, ignore_prim=None):
         """origins: array-like (n, 3) float32; directions (n, 3) or (3,), not necessarily normalised: t is in their units;
         radius, max_t, min_t: scalars or one per query; max_t None = no limit (RTK_INF). Returns (records HIT_RECORD_DTYPE,
         contact points (n, 3) float32, centres at the contact (n, 3) float32): prim == 0xFFFFFFFF is a miss, whose t is max_t and
         whose two points are the origin."""
-        s = self._sweep_array(origins, directions, radius, max_t, min_t)
-        n = s.shape[0]
-        if n == 0:
-            return np.zeros(0, HIT_RECORD_DTYPE), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
-        d_rec, d_pts, d_ctr = self.sweep_spheres_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
-        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
-        return (d_rec.cpu().numpy().view(HIT_RECORD_DTYPE), d_pts.cpu().numpy().view(np.float32).reshape(n, 3),
-                d_ctr.cpu().numpy().view(np.float32).reshape(n, 3))
+        fam = SWEEPS["spheres"]
+        return self._sweep_host(fam, self._sweep_array(fam, origins, directions, max_t, min_t, radius=radius), mesh_mask, ignore_prim)
 
     def path_blocked(self, origins, directions, radius, max_t=None, min_t=0.0, mesh_mask=None, ignore_prim=None):
         """The any-hit form of sweep_spheres: a bool array, True where the ball touches the scene somewhere in [min_t, max_t]."""
-        s = self._sweep_array(origins, directions, radius, max_t, min_t)
-        n = s.shape[0]
-        if n == 0:
-            return np.zeros(0, bool)
-        d_blocked = self.sweep_spheres_any_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
-        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
-        return d_blocked.cpu().numpy() != 0
-
-    # -- box sweeps (rtk_dev_sweep_boxes / _any): asynchronous on the current stream, nothing here waits for it --
+        fam = SWEEPS["spheres"]
+        return self._sweep_blocked_host(fam, self._sweep_array(fam, origins, directions, max_t, min_t, radius=radius), mesh_mask, ignore_prim)
 
     def sweep_boxes_device(self, d_sweeps, n, d_records=None, d_centres=None, d_normals=None, count=None, ids=None, mesh_mask=None,
                            ignore_prim=None):
@@ -1108,88 +1107,29 @@ class DeviceScene:
         floats per query each (the box's centre at the contact, the contact normal against the motion). count / ids: cuda int64
         tensors naming the queries to answer, as for closest_points_device; slots that are not listed are not written. mesh_mask:
         bools per mesh; ignore_prim: one id per query slot (a cuda tensor, or array-like)."""
-        torch = _torch()
-        if d_records is None:
-            d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
-        if d_centres is None:
-            d_centres = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        if d_normals is None:
-            d_normals = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        if ids is not None and count is None:
-            raise RtkError("sweep_boxes_device: ids without count (a list's length lives on the device)")
-        l = make_ray_list(count, ids) if count is not None else None
-        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
-        _check(lib().rtk_dev_sweep_boxes(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
-                                         C.c_void_p(d_records.data_ptr()), C.c_void_p(d_centres.data_ptr()), C.c_void_p(d_normals.data_ptr()),
-                                         C.byref(f) if f is not None else None, _stream_ptr()), "rtk_dev_sweep_boxes")
-        return d_records, d_centres, d_normals
+        return self._sweep_device(SWEEPS["boxes"], d_sweeps, n, d_records, d_centres, d_normals, count, ids, mesh_mask, ignore_prim)
 
     def sweep_boxes_any_device(self, d_sweeps, n, d_blocked=None, count=None, ids=None, mesh_mask=None, ignore_prim=None):
         """The any-hit form of sweep_boxes_device: one byte per query, 1 where the path is blocked, in the queries' own slots."""
-        torch = _torch()
-        if d_blocked is None:
-            d_blocked = torch.empty(n, dtype=torch.uint8, device="cuda")
-        if ids is not None and count is None:
-            raise RtkError("sweep_boxes_any_device: ids without count (a list's length lives on the device)")
-        l = make_ray_list(count, ids) if count is not None else None
-        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
-        _check(lib().rtk_dev_sweep_boxes_any(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
-                                             C.c_void_p(d_blocked.data_ptr()), C.byref(f) if f is not None else None, _stream_ptr()),
-               "rtk_dev_sweep_boxes_any")
-        return d_blocked
+        return self._sweep_any_device(SWEEPS["boxes"], d_sweeps, n, d_blocked, count, ids, mesh_mask, ignore_prim)
 
     def sweep_boxes_counted(self, d_sweeps, n, mesh_mask=None, ignore_prim=None):
         """sweep_boxes_device of all n queries on the null stream, synchronous, with the visit counts of
         rtk_dev_sweep_boxes_counted: returns (d_records, d_centres, d_normals, counts dict)."""
-        torch = _torch()
-        d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
-        d_centres = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        d_normals = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        ctr = TraceCounters()
-        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
-        torch.cuda.synchronize()
-        _check(lib().rtk_dev_sweep_boxes_counted(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.c_void_p(d_records.data_ptr()),
-                                                 C.c_void_p(d_centres.data_ptr()), C.c_void_p(d_normals.data_ptr()),
-                                                 C.byref(f) if f is not None else None, C.byref(ctr)), "rtk_dev_sweep_boxes_counted")
-        return d_records, d_centres, d_normals, ctr.as_dict()
-
-    @staticmethod
-    def _box_sweep_array(origins, directions, half, max_t, min_t):
-        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
-        n = o.shape[0]
-        s = np.zeros(n, BOX_SWEEP_DTYPE)
-        s["origin"] = o
-        s["direction"] = np.broadcast_to(np.asarray(directions, np.float32), (n, 3))
-        s["min_t"] = np.broadcast_to(np.asarray(min_t, np.float32), (n,))
-        s["max_t"] = RTK_INF if max_t is None else np.broadcast_to(np.asarray(max_t, np.float32), (n,))
-        s["half"] = np.broadcast_to(np.asarray(half, np.float32), (n, 3))
-        return s
+        return self._sweep_counted(SWEEPS["boxes"], d_sweeps, n, mesh_mask, ignore_prim)
 
     def sweep_boxes(self, origins, directions, half, max_t=None, min_t=0.0, mesh_mask=None, ignore_prim=None):
         """origins: array-like (n, 3) float32; directions (n, 3) or (3,), not necessarily normalised: t is in their units; half:
         the half extents, (n, 3), (3,) or a scalar (a cube); max_t, min_t: scalars or one per query; max_t None = no limit
         (RTK_INF). Returns (records HIT_RECORD_DTYPE, centres at the contact (n, 3) float32, contact normals (n, 3) float32):
         prim == 0xFFFFFFFF is a miss, whose t is max_t, whose centre is the origin and whose normal is zeros."""
-        s = self._box_sweep_array(origins, directions, half, max_t, min_t)
-        n = s.shape[0]
-        if n == 0:
-            return np.zeros(0, HIT_RECORD_DTYPE), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
-        d_rec, d_ctr, d_nrm = self.sweep_boxes_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
-        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
-        return (d_rec.cpu().numpy().view(HIT_RECORD_DTYPE), d_ctr.cpu().numpy().view(np.float32).reshape(n, 3),
-                d_nrm.cpu().numpy().view(np.float32).reshape(n, 3))
+        fam = SWEEPS["boxes"]
+        return self._sweep_host(fam, self._sweep_array(fam, origins, directions, max_t, min_t, half=half), mesh_mask, ignore_prim)
 
     def box_path_blocked(self, origins, directions, half, max_t=None, min_t=0.0, mesh_mask=None, ignore_prim=None):
         """The any-hit form of sweep_boxes: a bool array, True where the box touches the scene somewhere in [min_t, max_t]."""
-        s = self._box_sweep_array(origins, directions, half, max_t, min_t)
-        n = s.shape[0]
-        if n == 0:
-            return np.zeros(0, bool)
-        d_blocked = self.sweep_boxes_any_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
-        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
-        return d_blocked.cpu().numpy() != 0
-
-    # -- capsule sweeps (rtk_dev_sweep_capsules / _any): asynchronous on the current stream, nothing here waits for it --
+        fam = SWEEPS["boxes"]
+        return self._sweep_blocked_host(fam, self._sweep_array(fam, origins, directions, max_t, min_t, half=half), mesh_mask, ignore_prim)
 
     def sweep_capsules_device(self, d_sweeps, n, d_records=None, d_points=None, d_axis_points=None, count=None, ids=None, mesh_mask=None,
                               ignore_prim=None):
@@ -1199,63 +1139,16 @@ class DeviceScene:
         nearest the triangle). count / ids: cuda int64 tensors naming the queries to answer, as for closest_points_device; slots
         that are not listed are not written. mesh_mask: bools per mesh; ignore_prim: one id per query slot (a cuda tensor, or
         array-like)."""
-        torch = _torch()
-        if d_records is None:
-            d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
-        if d_points is None:
-            d_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        if d_axis_points is None:
-            d_axis_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        if ids is not None and count is None:
-            raise RtkError("sweep_capsules_device: ids without count (a list's length lives on the device)")
-        l = make_ray_list(count, ids) if count is not None else None
-        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
-        _check(lib().rtk_dev_sweep_capsules(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
-                                            C.c_void_p(d_records.data_ptr()), C.c_void_p(d_points.data_ptr()), C.c_void_p(d_axis_points.data_ptr()),
-                                            C.byref(f) if f is not None else None, _stream_ptr()), "rtk_dev_sweep_capsules")
-        return d_records, d_points, d_axis_points
+        return self._sweep_device(SWEEPS["capsules"], d_sweeps, n, d_records, d_points, d_axis_points, count, ids, mesh_mask, ignore_prim)
 
     def sweep_capsules_any_device(self, d_sweeps, n, d_blocked=None, count=None, ids=None, mesh_mask=None, ignore_prim=None):
         """The any-hit form of sweep_capsules_device: one byte per query, 1 where the path is blocked, in the queries' own slots."""
-        torch = _torch()
-        if d_blocked is None:
-            d_blocked = torch.empty(n, dtype=torch.uint8, device="cuda")
-        if ids is not None and count is None:
-            raise RtkError("sweep_capsules_any_device: ids without count (a list's length lives on the device)")
-        l = make_ray_list(count, ids) if count is not None else None
-        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
-        _check(lib().rtk_dev_sweep_capsules_any(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
-                                                C.c_void_p(d_blocked.data_ptr()), C.byref(f) if f is not None else None, _stream_ptr()),
-               "rtk_dev_sweep_capsules_any")
-        return d_blocked
+        return self._sweep_any_device(SWEEPS["capsules"], d_sweeps, n, d_blocked, count, ids, mesh_mask, ignore_prim)
 
     def sweep_capsules_counted(self, d_sweeps, n, mesh_mask=None, ignore_prim=None):
         """sweep_capsules_device of all n queries on the null stream, synchronous, with the visit counts of
         rtk_dev_sweep_capsules_counted: returns (d_records, d_points, d_axis_points, counts dict)."""
-        torch = _torch()
-        d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
-        d_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        d_axis_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        ctr = TraceCounters()
-        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
-        torch.cuda.synchronize()
-        _check(lib().rtk_dev_sweep_capsules_counted(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.c_void_p(d_records.data_ptr()),
-                                                    C.c_void_p(d_points.data_ptr()), C.c_void_p(d_axis_points.data_ptr()),
-                                                    C.byref(f) if f is not None else None, C.byref(ctr)), "rtk_dev_sweep_capsules_counted")
-        return d_records, d_points, d_axis_points, ctr.as_dict()
-
-    @staticmethod
-    def _capsule_sweep_array(origins, directions, radius, half_axis, max_t, min_t):
-        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
-        n = o.shape[0]
-        s = np.zeros(n, CAPSULE_SWEEP_DTYPE)
-        s["origin"] = o
-        s["direction"] = np.broadcast_to(np.asarray(directions, np.float32), (n, 3))
-        s["min_t"] = np.broadcast_to(np.asarray(min_t, np.float32), (n,))
-        s["max_t"] = RTK_INF if max_t is None else np.broadcast_to(np.asarray(max_t, np.float32), (n,))
-        s["radius"] = np.broadcast_to(np.asarray(radius, np.float32), (n,))
-        s["half_axis"] = np.broadcast_to(np.asarray(half_axis, np.float32), (n, 3))
-        return s
+        return self._sweep_counted(SWEEPS["capsules"], d_sweeps, n, mesh_mask, ignore_prim)
 
     def sweep_capsules(self, origins, directions, radius, half_axis, max_t=None, min_t=0.0, mesh_mask=None, ignore_prim=None):
         """origins: array-like (n, 3) float32; directions (n, 3) or (3,), not necessarily normalised: t is in their units; radius: a
@@ -1263,26 +1156,15 @@ class DeviceScene:
         scalars or one per query; max_t None = no limit (RTK_INF). Returns (records HIT_RECORD_DTYPE, the points of the triangles
         nearest the capsule's segment at the contact (n, 3) float32, the points of that segment nearest the triangle (n, 3)
         float32): prim == 0xFFFFFFFF is a miss, whose t is max_t and whose two points are the origin."""
-        s = self._capsule_sweep_array(origins, directions, radius, half_axis, max_t, min_t)
-        n = s.shape[0]
-        if n == 0:
-            return np.zeros(0, HIT_RECORD_DTYPE), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
-        d_rec, d_pts, d_axs = self.sweep_capsules_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
-        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
-        return (d_rec.cpu().numpy().view(HIT_RECORD_DTYPE), d_pts.cpu().numpy().view(np.float32).reshape(n, 3),
-                d_axs.cpu().numpy().view(np.float32).reshape(n, 3))
+        fam = SWEEPS["capsules"]
+        s = self._sweep_array(fam, origins, directions, max_t, min_t, radius=radius, half_axis=half_axis)
+        return self._sweep_host(fam, s, mesh_mask, ignore_prim)
 
     def capsule_path_blocked(self, origins, directions, radius, half_axis, max_t=None, min_t=0.0, mesh_mask=None, ignore_prim=None):
         """The any-hit form of sweep_capsules: a bool array, True where the capsule touches the scene somewhere in [min_t, max_t]."""
-        s = self._capsule_sweep_array(origins, directions, radius, half_axis, max_t, min_t)
-        n = s.shape[0]
-        if n == 0:
-            return np.zeros(0, bool)
-        d_blocked = self.sweep_capsules_any_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
-        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
-        return d_blocked.cpu().numpy() != 0
-
-    # -- oriented box sweeps (rtk_dev_sweep_obbs / _any): asynchronous on the current stream, nothing here waits for it --
+        fam = SWEEPS["capsules"]
+        s = self._sweep_array(fam, origins, directions, max_t, min_t, radius=radius, half_axis=half_axis)
+        return self._sweep_blocked_host(fam, s, mesh_mask, ignore_prim)
 
     def sweep_obbs_device(self, d_sweeps, n, d_records=None, d_centres=None, d_normals=None, count=None, ids=None, mesh_mask=None,
                           ignore_prim=None):
@@ -1291,62 +1173,21 @@ class DeviceScene:
         of 3 floats per query each (the box's centre at the contact, the contact normal against the motion). count / ids: cuda
         int64 tensors naming the queries to answer, as for closest_points_device; slots that are not listed are not written.
         mesh_mask: bools per mesh; ignore_prim: one id per query slot (a cuda tensor, or array-like)."""
-        torch = _torch()
-        if d_records is None:
-            d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
-        if d_centres is None:
-            d_centres = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        if d_normals is None:
-            d_normals = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        if ids is not None and count is None:
-            raise RtkError("sweep_obbs_device: ids without count (a list's length lives on the device)")
-        l = make_ray_list(count, ids) if count is not None else None
-        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
-        _check(lib().rtk_dev_sweep_obbs(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
-                                        C.c_void_p(d_records.data_ptr()), C.c_void_p(d_centres.data_ptr()), C.c_void_p(d_normals.data_ptr()),
-                                        C.byref(f) if f is not None else None, _stream_ptr()), "rtk_dev_sweep_obbs")
-        return d_records, d_centres, d_normals
+        return self._sweep_device(SWEEPS["obbs"], d_sweeps, n, d_records, d_centres, d_normals, count, ids, mesh_mask, ignore_prim)
 
     def sweep_obbs_any_device(self, d_sweeps, n, d_blocked=None, count=None, ids=None, mesh_mask=None, ignore_prim=None):
         """The any-hit form of sweep_obbs_device: one byte per query, 1 where the path is blocked, in the queries' own slots."""
-        torch = _torch()
-        if d_blocked is None:
-            d_blocked = torch.empty(n, dtype=torch.uint8, device="cuda")
-        if ids is not None and count is None:
-            raise RtkError("sweep_obbs_any_device: ids without count (a list's length lives on the device)")
-        l = make_ray_list(count, ids) if count is not None else None
-        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
-        _check(lib().rtk_dev_sweep_obbs_any(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.byref(l) if l is not None else None,
-                                            C.c_void_p(d_blocked.data_ptr()), C.byref(f) if f is not None else None, _stream_ptr()),
-               "rtk_dev_sweep_obbs_any")
-        return d_blocked
+        return self._sweep_any_device(SWEEPS["obbs"], d_sweeps, n, d_blocked, count, ids, mesh_mask, ignore_prim)
 
     def sweep_obbs_counted(self, d_sweeps, n, mesh_mask=None, ignore_prim=None):
         """sweep_obbs_device of all n queries on the null stream, synchronous, with the visit counts of
         rtk_dev_sweep_obbs_counted: returns (d_records, d_centres, d_normals, counts dict)."""
-        torch = _torch()
-        d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
-        d_centres = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        d_normals = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
-        ctr = TraceCounters()
-        f, _keep = self._sweep_filter(n, mesh_mask, ignore_prim)
-        torch.cuda.synchronize()
-        _check(lib().rtk_dev_sweep_obbs_counted(self.handle, C.c_void_p(d_sweeps.data_ptr()), n, C.c_void_p(d_records.data_ptr()),
-                                                C.c_void_p(d_centres.data_ptr()), C.c_void_p(d_normals.data_ptr()),
-                                                C.byref(f) if f is not None else None, C.byref(ctr)), "rtk_dev_sweep_obbs_counted")
-        return d_records, d_centres, d_normals, ctr.as_dict()
+        return self._sweep_counted(SWEEPS["obbs"], d_sweeps, n, mesh_mask, ignore_prim)
 
     @staticmethod
     def _obb_sweep_array(origins, directions, half, rotation, max_t, min_t):
-        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
-        n = o.shape[0]
-        s = np.zeros(n, OBB_SWEEP_DTYPE)
-        s["origin"] = o
-        s["direction"] = np.broadcast_to(np.asarray(directions, np.float32), (n, 3))
-        s["min_t"] = np.broadcast_to(np.asarray(min_t, np.float32), (n,))
-        s["max_t"] = RTK_INF if max_t is None else np.broadcast_to(np.asarray(max_t, np.float32), (n,))
-        s["half"] = np.broadcast_to(np.asarray(half, np.float32), (n, 3))
-        s["axes"] = obb_axes(rotation, n)
+        s = DeviceScene._sweep_array(SWEEPS["obbs"], origins, directions, max_t, min_t, half=half)
+        s["axes"] = obb_axes(rotation, s.shape[0])
         return s
 
     def sweep_obbs(self, origins, directions, half, rotation, max_t=None, min_t=0.0, mesh_mask=None, ignore_prim=None):
@@ -1357,23 +1198,12 @@ class DeviceScene:
         HIT_RECORD_DTYPE, centres at the contact (n, 3) float32, contact normals (n, 3) float32): prim == 0xFFFFFFFF is a miss,
         whose t is max_t, whose centre is the origin and whose normal is zeros. Axes that are not orthonormal to 2^-10 are a miss."""
         s = self._obb_sweep_array(origins, directions, half, rotation, max_t, min_t)
-        n = s.shape[0]
-        if n == 0:
-            return np.zeros(0, HIT_RECORD_DTYPE), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
-        d_rec, d_ctr, d_nrm = self.sweep_obbs_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
-        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
-        return (d_rec.cpu().numpy().view(HIT_RECORD_DTYPE), d_ctr.cpu().numpy().view(np.float32).reshape(n, 3),
-                d_nrm.cpu().numpy().view(np.float32).reshape(n, 3))
+        return self._sweep_host(SWEEPS["obbs"], s, mesh_mask, ignore_prim)
 
     def obb_path_blocked(self, origins, directions, half, rotation, max_t=None, min_t=0.0, mesh_mask=None, ignore_prim=None):
         """The any-hit form of sweep_obbs: a bool array, True where the box touches the scene somewhere in [min_t, max_t]."""
         s = self._obb_sweep_array(origins, directions, half, rotation, max_t, min_t)
-        n = s.shape[0]
-        if n == 0:
-            return np.zeros(0, bool)
-        d_blocked = self.sweep_obbs_any_device(to_device(s), n, mesh_mask=mesh_mask, ignore_prim=ignore_prim)
-        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
-        return d_blocked.cpu().numpy() != 0
+        return self._sweep_blocked_host(SWEEPS["obbs"], s, mesh_mask, ignore_prim)
 
     # -- triangles within a distance (rtk_dev_triangles_within_count / _all): asynchronous on the current stream --
 

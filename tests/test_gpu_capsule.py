@@ -340,7 +340,7 @@ def test_a_stack_deeper_than_the_on_chip_part(api):
     assert api.lib().rtk_dev_trace_status(ds.handle, None) == 0
 
 
-@pytest.mark.parametrize("n", [0, 1, 65])
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 257])
 def test_sizes(api, base, n):
     which = np.arange(n) % len(base.sweeps)
     out = run(api, base.ds, base.sweeps[which], n=n)
