@@ -736,6 +736,76 @@ int rtk_dev_triangles_in_box_counted(const rtk_dev_scene *ds, const rtk_box_quer
 /* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
 uint32_t rtk_amd_box_stack_entries(void);
 
+/* ---- Triangles that touch an oriented box: how many triangles touch a box with axes of its own, and which ----
+ * The region question for a shape that does not follow the scene's axes: a rigid body's hull, a vehicle chassis, a tilted
+ * selection volume; the start test of an oriented sweep and of a depenetration step; voxelising a scene in a body's own frame.
+ * rtk_dev_triangles_in_box_* on the hull's world bounds over-reports by everything in the bounds but not in the hull -- a cube
+ * turned by 45 degrees about two axes has bounds of several times its volume -- and leaves the caller to filter;
+ * rtk_dev_sweep_obbs with a tiny path answers one triangle, not the set. The walk is the axis-aligned one's, box against box on
+ * the turned box's bounds, comparisons only; the box's own axes are paid per triangle. The calls read the scene as it stands,
+ * changing no bit of it.
+ *
+ * A query is a rtk_obb_query: `axes` holds three rows u0, u1, u2, the box's own axes in scene coordinates (the rows of a rotation
+ * matrix whose rows are those axes); the box is { centre + a0 * u0 + a1 * u1 + a2 * u2 : |aj| <= half[j] }.
+ *
+ * THE RULE (rtk_amd/csrc/rtk_obb_rule.h; INTEGRATION.md "Triangles that touch an oriented box"). All arithmetic is float32, every
+ * operation rounded on its own, no FMA. A query is LIVE iff its fifteen numbers are finite, every half[j] >= 0 and the axes are
+ * orthonormal to within 2^-10 (the gate of rtk_dev_sweep_obbs: a gate against garbage, not an accuracy claim; a left-handed
+ * triple is a box as well); half == 0 on one, two or three axes is legal (a rectangle, a segment, a point). A query that is not
+ * live has no candidates; neither has any query of a scene without triangles. With g[k] = (|u0[k]| * half[0] + |u1[k]| * half[1])
+ * + |u2[k]| * half[2] the box's reach along scene axis k, qlo = centre - g and qhi = centre + g, a triangle is a CANDIDATE of a
+ * live query iff its own box (componentwise min / max of its vertices) has tlo[a] <= qhi[a] && thi[a] >= qlo[a] on all three
+ * axes -- CLOSED: touching counts -- and, with its vertices taken into the box's frame (w = v - centre, then the three dots with
+ * u0, u1, u2), none of the thirteen axes separates the two: the box's own three (all three coordinates > half[j] or all
+ * < -half[j]) and the ten of Akenine-Moller's test as "Triangles that touch a box" states them, about the origin of the frame
+ * with the half extent `half`; a comparison with a NaN never separates. It is a FLOAT RULE and the candidate set is DEFINED BY IT;
+ * on inputs whose intermediates are exact it is the exact answer. Identity axes give the answer of rtk_dev_triangles_in_box_* on
+ * [centre - half, centre + half] up to rounding only, not bit for bit. The LIST of a query is its candidates in ASCENDING PRIMITIVE
+ * ID. THE RESULT DOES NOT DEPEND ON THE TREE OR ON THE ORDER OF THE WALK: a child box [clo, chi] is left out only if
+ * clo[a] > qhi[a] || chi[a] < qlo[a] on some axis, exact without a margin because every box above a triangle contains the
+ * triangle's own box and the test of the triangle's box against [qlo, qhi] is part of the rule. Only the exact 128-byte nodes
+ * are used.
+ *
+ * rtk_dev_triangles_in_obb_count: d_counts[i] = the number of candidates of query i, written for EVERY answered query (0 for a
+ *   query without any); nothing else is written.
+ * rtk_dev_triangles_in_obb_all: query i owns d_prims[d_offsets[i] .. d_offsets[i + 1]); d_offsets has num_queries + 1 entries,
+ *   indexed by query slot; r = d_offsets[i + 1] - d_offsets[i] is its room and may be 0. Written are the first min(count_i, r)
+ *   entries of the query's list, each one global primitive id; d_written[i] (d_written may be NULL) is that number. Entries of
+ *   the segment beyond it ARE NOT WRITTEN, entries outside every segment are not written. A query whose offsets decrease has
+ *   no room and nothing is written for it (d_written[i] = 0). One call serves two uses:
+ *     every triangle in the box   count, an inclusive prefix sum into uint64 offsets on the same stream (torch.cumsum into an
+ *                                 int64 tensor is one as it stands), then fill;
+ *     at most k, deterministic    d_offsets[i] = i * k, no count pass: the k LOWEST ids among the candidates. THAT WALK CANNOT BE
+ *                                 CULLED BY WHAT IT HAS KEPT, since the tree is not ordered by id: it visits what the count
+ *                                 visits, and a candidate that does not get in costs no memory access.
+ * `list` may be NULL: all num_queries queries are answered. Otherwise the words of closest points hold: m = min(*d_count,
+ * num_queries) entries are answered, the results of query r go to slot r of d_counts / d_written and to segment r, A SLOT THAT
+ * IS NOT LISTED IS NOT WRITTEN, an id may repeat (the query is answered once), the count is read when the work reaches it on
+ * `stream`, and an id >= num_queries is the caller's error.
+ * DETERMINISTIC: the same inputs give the same bytes. Asynchronous on `stream`: no host wait, nothing read back. The scene is
+ * only read, as it stands: built, uploaded, refitted, split or rebuilt, and rtk_mgpu_scene(m, i) as it is; the thread-safety
+ * rules of the batches hold. The part of the walk's stack that does not fit on chip (and one bit per query for a list with ids)
+ * lives in the per-(scene, stream) scratch set, and a dropped push (impossible for a tree) is reported by rtk_dev_trace_status
+ * like a trace's. Nothing they allocate counts toward the scene.
+ * Refused before anything is launched and before any HIP call, RTK_AMD_ERR_BAD_ARG, with a message that names the function: a
+ * NULL scene; NULL d_obbs or d_counts, NULL d_offsets or d_prims with num_queries != 0; a bad list (as for the listed
+ * traces); num_queries >= 2^32; a calling thread whose current device is not the scene's. num_queries == 0 is RTK_AMD_OK with
+ * nothing launched. Offsets that run past the caller's buffer are the caller's error and are NOT CHECKED.
+ * A scene with non-finite vertex coordinates: the calls terminate and write only inside their outputs; NOTHING ELSE IS PROMISED
+ * about their results. */
+typedef struct rtk_obb_query { float centre[3], half[3], axes[9]; } rtk_obb_query;   /* 60 bytes; a float32 [n, 15] tensor */
+int rtk_dev_triangles_in_obb_count(const rtk_dev_scene *ds, const rtk_obb_query *d_obbs, size_t num_queries,
+	const rtk_ray_list *list, uint32_t *d_counts, void *stream);
+int rtk_dev_triangles_in_obb_all(const rtk_dev_scene *ds, const rtk_obb_query *d_obbs, size_t num_queries,
+	const rtk_ray_list *list, const uint64_t *d_offsets, uint32_t *d_prims, uint32_t *d_written /* may be NULL */, void *stream);
+/* The same results without a list, plus visit counts in the fields of rtk_dev_closest_points_counted (hits = queries with at least
+ * one candidate counted or kept). d_offsets == NULL: the count form, d_counts_or_written receives the counts (required);
+ * otherwise the fill form, d_counts_or_written may be NULL. Null stream, synchronous; not for timing. */
+int rtk_dev_triangles_in_obb_counted(const rtk_dev_scene *ds, const rtk_obb_query *d_obbs, size_t num_queries,
+	const uint64_t *d_offsets, uint32_t *d_prims, uint32_t *d_counts_or_written, rtk_trace_counters *out);
+/* (entries per lane the walk keeps on chip before it uses the spill area, for tests) */
+uint32_t rtk_amd_obb_stack_entries(void);
+
 /* ---- Triangles that touch a triangle: which triangles of the scene a given triangle meets ----
  * The narrow phase that the box query (a body's bounds) and the distance query (contact generation) lead up to: mesh-against-mesh
  * collision, one body's triangles against another body's scene; self-intersection checks of a deforming mesh after a refit;

@@ -13,7 +13,7 @@ import os
 
 import numpy as np
 
-from .types import (BOX_QUERY_DTYPE, BOX_SWEEP_DTYPE, CAPSULE_SWEEP_DTYPE, CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, OBB_SWEEP_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, SPHERE_SWEEP_DTYPE, TRI_QUERY_DTYPE, MeshSet, Placement, SceneDesc, SceneHeader,
+from .types import (BOX_QUERY_DTYPE, BOX_SWEEP_DTYPE, CAPSULE_SWEEP_DTYPE, CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, OBB_QUERY_DTYPE, OBB_SWEEP_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, SPHERE_SWEEP_DTYPE, TRI_QUERY_DTYPE, MeshSet, Placement, SceneDesc, SceneHeader,
                     placement_array)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -239,6 +239,8 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_amd_within_stack_entries",
                      "rtk_dev_triangles_in_box_count", "rtk_dev_triangles_in_box_all", "rtk_dev_triangles_in_box_counted",
                      "rtk_amd_box_stack_entries",
+                     "rtk_dev_triangles_in_obb_count", "rtk_dev_triangles_in_obb_all", "rtk_dev_triangles_in_obb_counted",
+                     "rtk_amd_obb_stack_entries",
                      "rtk_dev_triangles_touching_count", "rtk_dev_triangles_touching_all", "rtk_dev_triangles_touching_counted",
                      "rtk_amd_touch_stack_entries",
                      "rtk_dev_closest_triangles", "rtk_dev_closest_triangles_counted", "rtk_amd_pair_stack_entries",
@@ -390,6 +392,14 @@ def lib():
     L.rtk_dev_triangles_in_box_counted.restype = C.c_int
     L.rtk_amd_box_stack_entries.argtypes = []
     L.rtk_amd_box_stack_entries.restype = C.c_uint32
+    L.rtk_dev_triangles_in_obb_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p]
+    L.rtk_dev_triangles_in_obb_count.restype = C.c_int
+    L.rtk_dev_triangles_in_obb_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtk_dev_triangles_in_obb_all.restype = C.c_int
+    L.rtk_dev_triangles_in_obb_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
+    L.rtk_dev_triangles_in_obb_counted.restype = C.c_int
+    L.rtk_amd_obb_stack_entries.argtypes = []
+    L.rtk_amd_obb_stack_entries.restype = C.c_uint32
     L.rtk_dev_triangles_touching_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(TouchFilter), C.c_void_p, C.c_void_p]
     L.rtk_dev_triangles_touching_count.restype = C.c_int
     L.rtk_dev_triangles_touching_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(TouchFilter), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1400,6 +1410,89 @@ class DeviceScene:
         d_counts = self.count_in_boxes_device(d_boxes, n)
         return (d_counts != 0).reshape(shape)
 
+    # -- triangles that touch an oriented box (rtk_dev_triangles_in_obb_count / _all): asynchronous on the current stream --
+
+    def count_in_obbs_device(self, d_obbs, n, d_counts=None, count=None, ids=None):
+        """The number of triangles that touch each of n oriented boxes (OBB_QUERY_DTYPE bytes on the device, or a float32
+        [n, 15] cuda tensor of centre, half, axes; include/rtk_amd.h, "Triangles that touch an oriented box"): a cuda tensor of
+        n uint32 words (d_counts: any cuda tensor of at least 4 n bytes; None: a new int32 tensor). count / ids: cuda int64
+        tensors naming the queries to answer, as for count_in_boxes_device; slots that are not listed are not written. Nothing
+        waits for the stream."""
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        if ids is not None and count is None:
+            raise RtkError("count_in_obbs_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        _check(lib().rtk_dev_triangles_in_obb_count(self.handle, C.c_void_p(d_obbs.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                    C.c_void_p(d_counts.data_ptr()), _stream_ptr()), "rtk_dev_triangles_in_obb_count")
+        return d_counts
+
+    def in_obbs_all_device(self, d_obbs, n, d_offsets, d_prims, d_written=None, count=None, ids=None):
+        """Oriented box i's triangles, ascending global primitive ids (uint32), into entries d_offsets[i] .. d_offsets[i + 1] of
+        d_prims: as many as the box has or the segment holds, the lowest ids first. d_offsets: a cuda int64 tensor of n + 1
+        entries. d_written: a cuda tensor of 4 n bytes, or None (the call gets NULL). Entries beyond written[i], and outside every
+        segment, are not written. count / ids as for count_in_obbs_device. Nothing waits for the stream."""
+        if ids is not None and count is None:
+            raise RtkError("in_obbs_all_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        _check(lib().rtk_dev_triangles_in_obb_all(self.handle, C.c_void_p(d_obbs.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                  C.c_void_p(d_offsets.data_ptr()), C.c_void_p(d_prims.data_ptr()),
+                                                  C.c_void_p(d_written.data_ptr()) if d_written is not None else None,
+                                                  _stream_ptr()), "rtk_dev_triangles_in_obb_all")
+        return d_written
+
+    def triangles_in_obbs_counted(self, d_obbs, n, d_offsets=None, d_prims=None, d_counts=None):
+        """count_in_obbs_device (d_offsets None) or in_obbs_all_device of all n boxes on the null stream, synchronous, with the
+        visit counts of rtk_dev_triangles_in_obb_counted: returns (d_counts -- the counts, or the written numbers --, counts dict)."""
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        ctr = TraceCounters()
+        torch.cuda.synchronize()
+        _check(lib().rtk_dev_triangles_in_obb_counted(self.handle, C.c_void_p(d_obbs.data_ptr()), n,
+                                                      C.c_void_p(d_offsets.data_ptr()) if d_offsets is not None else None,
+                                                      C.c_void_p(d_prims.data_ptr()) if d_prims is not None else None,
+                                                      C.c_void_p(d_counts.data_ptr()), C.byref(ctr)), "rtk_dev_triangles_in_obb_counted")
+        return d_counts, ctr.as_dict()
+
+    def triangles_in_obbs(self, centres, half, rotation, max_per_box=None):
+        """Every triangle that touches each oriented box, or with max_per_box=k the k lowest ids of them. centres: (n, 3); half:
+        the half extents along the box's own axes, (n, 3), (3,) or a scalar (a cube); rotation: (n, 3, 3) or (3, 3) matrices whose
+        ROWS are the box's axes in scene coordinates, or (n, 4) or (4,) quaternions (x, y, z, w) (see obb_axes). Returns what
+        triangles_in_boxes returns: (offsets int64[n + 1], prims uint32[offsets[n]], written uint32[n])."""
+        torch = _torch()
+        q = obb_query_array(centres, half, rotation)
+        n = q.shape[0]
+        if n == 0:
+            return np.zeros(1, np.int64), np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+        d_q = to_device(q)
+        if max_per_box is None:
+            d_counts = self.count_in_obbs_device(d_q, n)
+            d_offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+            d_offsets[1:] = torch.cumsum(d_counts, 0, dtype=torch.int64)
+            total = int(d_offsets[n].item())                 # (the one read-back: how many ids to allocate)
+        else:
+            k = int(max_per_box)
+            if k < 0:
+                raise RtkError("triangles_in_obbs: max_per_box %r" % (max_per_box,))
+            d_offsets = torch.arange(n + 1, dtype=torch.int64, device="cuda") * k
+            total = n * k
+        d_prims = torch.zeros(max(total, 1), dtype=torch.int32, device="cuda")
+        d_written = torch.empty(n, dtype=torch.int32, device="cuda")
+        self.in_obbs_all_device(d_q, n, d_offsets, d_prims, d_written)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return d_offsets.cpu().numpy(), d_prims.cpu().numpy().view(np.uint32)[:total], d_written.cpu().numpy().view(np.uint32)
+
+    def occupancy_oriented(self, centre, half, rotation, shape):
+        """A bool cuda tensor of `shape` (nx, ny, nz): true where at least one triangle touches the cell of the nx x ny x nz grid
+        that fills the oriented box (centre, half, rotation as for triangles_in_obbs, one box). The cells' centres and half
+        extents are made on the host in numpy float32 (oriented_grid), so their bits do not depend on the device. One count over
+        nx * ny * nz oriented boxes on the current stream; the result is not waited for."""
+        q = oriented_grid(centre, half, rotation, shape)
+        d_counts = self.count_in_obbs_device(to_device(q), q.shape[0])
+        return (d_counts != 0).reshape(tuple(int(s) for s in shape))
+
     # -- triangles that touch a triangle (rtk_dev_triangles_touching_count / _all): asynchronous on the current stream --
 
     def count_touching_device(self, d_tris, n, d_counts=None, count=None, ids=None, first_prim=None, skip_shared=False):
@@ -2245,6 +2338,40 @@ def obb_axes(rotation, n):
     else:
         raise RtkError("obb_axes: rotation of shape %s: (n, 3, 3), (3, 3), (n, 4) or (4,) with n = %d" % (r.shape, n))
     return np.ascontiguousarray(np.broadcast_to(m.reshape(-1, 3, 3), (n, 3, 3)), np.float32)
+
+
+def obb_query_array(centres, half, rotation):
+    """n rtk_obb_query records (OBB_QUERY_DTYPE). centres: (n, 3); half: (n, 3), (3,) or a scalar; rotation: see obb_axes."""
+    c = np.ascontiguousarray(centres, np.float32).reshape(-1, 3)
+    n = c.shape[0]
+    q = np.zeros(n, OBB_QUERY_DTYPE)
+    q["centre"] = c
+    h = np.asarray(half, np.float32)
+    if h.shape not in ((), (3,), (n, 3)):
+        raise RtkError("obb_query_array: half of shape %s: (n, 3), (3,) or a scalar with n = %d" % (h.shape, n))
+    q["half"] = h if h.shape != () else np.broadcast_to(h, (n, 3))
+    q["axes"] = obb_axes(rotation, n)
+    return q
+
+
+def oriented_grid(centre, half, rotation, shape):
+    """The nx * ny * nz cells (OBB_QUERY_DTYPE, x slowest) of the grid that fills one oriented box, all in numpy float32, every
+    operation rounded on its own: a cell's half extent is half[j] / n_j, its centre centre + ((a0 * u0 + a1 * u1) + a2 * u2) with
+    a_j = (2 i_j + 1 - n_j) * (half[j] / n_j), and its axes are the box's."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise RtkError("oriented_grid: shape %r" % (shape,))
+    F = np.float32
+    box = obb_query_array(np.asarray(centre, F).reshape(1, 3), half, rotation)
+    c, h, u = box["centre"][0], box["half"][0], box["axes"][0]
+    ch = h / np.array(shape, F)
+    a = [((2 * np.arange(shape[j]) + 1 - shape[j]).astype(F) * ch[j]).astype(F) for j in range(3)]
+    a0, a1, a2 = (x.reshape(-1, 1) for x in np.meshgrid(a[0], a[1], a[2], indexing="ij"))
+    q = np.zeros(shape[0] * shape[1] * shape[2], OBB_QUERY_DTYPE)
+    q["centre"] = c[None, :] + ((a0 * u[0][None, :] + a1 * u[1][None, :]) + a2 * u[2][None, :])
+    q["half"] = ch
+    q["axes"] = u
+    return q
 
 
 def build_scene(meshes):

@@ -269,6 +269,25 @@ extern "C" int rtk_dev_triangles_in_box_counted(const rtk_dev_scene *ds, const r
 	return rtk_launch_box(ds, d_boxes, num_queries, nullptr, d_counts_or_written, d_offsets, d_prims, d_offsets != nullptr, nullptr, out);
 }
 
+extern "C" int rtk_dev_triangles_in_obb_count(const rtk_dev_scene *ds, const rtk_obb_query *d_obbs, size_t num_queries,
+	const rtk_ray_list *list, uint32_t *d_counts, void *stream)
+{
+	return rtk_launch_obb(ds, d_obbs, num_queries, list, d_counts, nullptr, nullptr, false, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_triangles_in_obb_all(const rtk_dev_scene *ds, const rtk_obb_query *d_obbs, size_t num_queries,
+	const rtk_ray_list *list, const uint64_t *d_offsets, uint32_t *d_prims, uint32_t *d_written, void *stream)
+{
+	return rtk_launch_obb(ds, d_obbs, num_queries, list, d_written, d_offsets, d_prims, true, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_triangles_in_obb_counted(const rtk_dev_scene *ds, const rtk_obb_query *d_obbs, size_t num_queries,
+	const uint64_t *d_offsets, uint32_t *d_prims, uint32_t *d_counts_or_written, rtk_trace_counters *out)
+{
+	if (!out) { rtk_set_error("rtk_dev_triangles_in_obb_counted: NULL counters"); return RTK_AMD_ERR_BAD_ARG; }
+	return rtk_launch_obb(ds, d_obbs, num_queries, nullptr, d_counts_or_written, d_offsets, d_prims, d_offsets != nullptr, nullptr, out);
+}
+
 extern "C" int rtk_dev_triangles_touching_count(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries,
 	const rtk_ray_list *list, const rtk_touch_filter *filter, uint32_t *d_counts, void *stream)
 {

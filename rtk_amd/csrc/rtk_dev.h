@@ -396,6 +396,10 @@ int rtk_launch_within(const rtk_dev_scene *ds, const rtk_point_query *d_queries,
 // fill: offsets, prims, d_counts the written numbers or NULL; else d_counts the counts. counted: synchronises the stream
 int rtk_launch_box(const rtk_dev_scene *ds, const rtk_box_query *d_boxes, size_t num_queries, const rtk_ray_list *list,
 	uint32_t *d_counts, const uint64_t *d_offsets, uint32_t *d_prims, bool fill, hipStream_t stream, rtk_trace_counters *counted = nullptr);
+// -- rtk_dev_triangles_in_obb_count / rtk_dev_triangles_in_obb_all (rtk_obb.hip) --
+// as rtk_launch_box, every query with axes of its own
+int rtk_launch_obb(const rtk_dev_scene *ds, const rtk_obb_query *d_obbs, size_t num_queries, const rtk_ray_list *list,
+	uint32_t *d_counts, const uint64_t *d_offsets, uint32_t *d_prims, bool fill, hipStream_t stream, rtk_trace_counters *counted = nullptr);
 // -- rtk_dev_triangles_touching_count / rtk_dev_triangles_touching_all (rtk_touch.hip) --
 // as rtk_launch_box, with the filter (or NULL)
 int rtk_launch_touch(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries, const rtk_ray_list *list,

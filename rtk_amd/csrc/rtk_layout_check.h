@@ -33,7 +33,8 @@ static_assert(sizeof(rtk_capsule_sweep) == 48 && offsetof(rtk_capsule_sweep, dir
 	offsetof(rtk_capsule_sweep, radius) == 32 && offsetof(rtk_capsule_sweep, half_axis) == 36, "rtk_capsule_sweep");
 static_assert(sizeof(rtk_obb_sweep) == 80 && offsetof(rtk_obb_sweep, direction) == 12 && offsetof(rtk_obb_sweep, min_t) == 24 &&
 	offsetof(rtk_obb_sweep, half) == 32 && offsetof(rtk_obb_sweep, axes) == 44, "rtk_obb_sweep");
-static_assert(sizeof(rtk_dev_filter) == 32 && offsetof(rtk_dev_filter, d_ignore_prim) == 16 && offsetof(rtk_dev_filter, d_after) == 24, "rtk_dev_filter");
+static_assert(sizeof(rtk_obb_query) == 60 && offsetof(rtk_obb_query, half) == 12 && offsetof(rtk_obb_query, axes) == 24, "rtk_obb_query");
+static_assert(sizeof(rtk_dev_filter) == 32&& offsetof(rtk_dev_filter, d_ignore_prim) == 16 && offsetof(rtk_dev_filter, d_after) == 24, "rtk_dev_filter");
 static_assert(sizeof(rtk_dev_rebuild_info) == 40 && offsetof(rtk_dev_rebuild_info, nodes_before) == 8 && offsetof(rtk_dev_rebuild_info, max_depth_before) == 24 &&
 	offsetof(rtk_dev_rebuild_info, rebuild_ms) == 32, "rtk_dev_rebuild_info");
 static_assert(sizeof(rtk_dev_sign_info) == 56 && offsetof(rtk_dev_sign_info, places) == 32 && offsetof(rtk_dev_sign_info, table_ms) == 48, "rtk_dev_sign_info");

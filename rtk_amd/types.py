@@ -41,6 +41,9 @@ assert CAPSULE_SWEEP_DTYPE.itemsize == 48
 OBB_SWEEP_DTYPE = np.dtype([("origin", "<f4", (3,)), ("direction", "<f4", (3,)), ("min_t", "<f4"), ("max_t", "<f4"), ("half", "<f4", (3,)),
                             ("axes", "<f4", (3, 3))])
 assert OBB_SWEEP_DTYPE.itemsize == 80
+# rtk_obb_query (rtk_dev_triangles_in_obb_count / _all): a float32 [n, 15] array is one; the rows of `axes` are the box's own axes
+OBB_QUERY_DTYPE = np.dtype([("centre", "<f4", (3,)), ("half", "<f4", (3,)), ("axes", "<f4", (3, 3))])
+assert OBB_QUERY_DTYPE.itemsize == 60
 assert POINT_QUERY_DTYPE.itemsize == 16 and CLOSEST_RECORD_DTYPE.itemsize == 16 and BOX_QUERY_DTYPE.itemsize == 24
 assert TRI_QUERY_DTYPE.itemsize == 36
 assert VERTEX_DTYPE.itemsize == 16 and RAY_DTYPE.itemsize == 32
