@@ -429,9 +429,12 @@ def test_the_walk_is_the_axis_aligned_walk(api, base):
 
 
 def test_more_queries_than_one_pass_of_the_grid(api, base):
-    """2^19 + 3 queries: the resident grid steps through the batch several times; every copy of the mix counts what the first does"""
+    """tests/many_passes.py's batch size -- two passes of the largest grid the device's CUs can hold, five waves and 37: the
+    resident grid steps through the batch at least three times; every copy of the mix counts what the first does"""
     import torch
-    n = (1 << 19) + 3
+    from tests.many_passes import batch_size
+    n = batch_size(torch.cuda.get_device_properties(0).multi_processor_count)
+    assert n > (1 << 19) + 3 and n % 64
     d_mix = api.to_device(base.q).view(torch.uint8).reshape(base.n, 60)
     reps = -(-n // base.n)
     d_q = d_mix.repeat(reps, 1)[:n].contiguous()
