@@ -1330,7 +1330,8 @@ uint32_t rtk_amd_allhits_stack_entries(void);
  * placed meshes into such a set, so memory and build time grow with instances x triangles and moving one body refits that
  * body's triangles. A rtk_dev_world is the second level: a small TOP TREE over the world boxes of INSTANCES, each a
  * (scene, rtk_placement) pair; a scene is held once however often it is placed, and moving an instance costs a 64-byte
- * record and a refit of the top tree. Rays only, closest hit and any hit; other query kinds on a world are not there yet.
+ * record and a refit of the top tree. A world answers rays (closest hit and any hit) and closest points
+ * (rtk_dev_world_closest_points, below); signed distance, within, overlaps, pairs and sweeps still take one rtk_dev_scene.
  *
  * THE OBJECT. rtk_dev_world_create(scenes, num_scenes, instance_scene, placements, num_instances): instance i places scene
  * scenes[instance_scene[i]] by placements[i] (host memory, both arrays; the rule of rtk_dev_scene_build_placed maps the
@@ -1401,6 +1402,35 @@ int rtk_dev_world_trace_rays_counted(const rtk_dev_world *w, const rtk_ray *d_ra
 	rtk_hit_record *d_records, uint32_t *d_instances, rtk_trace_counters *out);
 /* (8-byte stack entries per lane the walk keeps on chip before it uses the spill area, for tests) */
 uint32_t rtk_amd_world_stack_entries(void);
+
+/* CLOSEST POINTS ON A WORLD. rtk_dev_world_closest_points: per query the rtk_closest_record of the nearest triangle over all
+ * live instances the filter lets through, prim the GLOBAL PRIMITIVE ID IN THE INSTANCE'S SCENE as for rtk_dev_world_trace_rays,
+ * (d_instances may be NULL) the instance number and (d_points may be NULL, 3 floats per query) the point on the triangle in
+ * world coordinates. The rule (rtk_amd/csrc/rtk_world_closest_rule.h): a record's vertices are placed by the instance's
+ * FORWARD placement with the rule of rtk_dev_scene_build_placed, then rtk_dev_closest_points's rule answers on the placed
+ * vertices. THE RESULT HAS THE BITS rtk_dev_closest_points GIVES ON THE FLAT PLACED TWIN (rtk_dev_scene_build_placed of the same
+ * meshes under the same placements), for any affine placement with finite placed vertices: no condition number, no margin.
+ * Among candidates with dist2 < max_dist2 the smallest dist2 wins; among equal dist2 THE LOWEST INSTANCE NUMBER, then the
+ * lowest primitive id: unlike the world's rays, a tie across instances is decided, and the result depends on neither tree
+ * nor on the order of the walk. A dead instance is never answered. Liveness of a query and the miss record are
+ * rtk_dev_closest_points's: a non-finite coordinate or a max_dist2 that is NaN, zero or negative is a miss; RTK_INF means no
+ * limit; a miss is dist2 = max_dist2 as given, u = v = 0, RTK_PRIM_NONE in prim and in the instance, the point the query's.
+ * With placed vertices that are not finite nothing is promised about results; the call terminates and writes only its outputs.
+ * The record is a rtk_closest_record: rtk_dev_select_rays and rtk_dev_expand_hits (on the instance's scene) take it.
+ * `list` as for the listed traces (a slot that is not listed is not written; an id >= n is skipped; an id may repeat).
+ * rtk_world_filter as for rays; d_ignore_instance is read at the query's slot (the body a point belongs to).
+ * Asynchronous on `stream`, nothing is read back; the scratch set and the launch-error word are the top tree's for that stream
+ * (rtk_dev_world_trace_status). A scene that changed must be followed by rtk_dev_world_update first, as for rays.
+ * _counted: with visit counts (nodes and leaves of both levels together, triangles = proxies and triangle records, hits,
+ * stack_spills); on the null stream, synchronises. Refusals before any HIP call are those of rtk_dev_world_trace_rays;
+ * num_queries == 0 is RTK_AMD_OK with nothing launched. */
+int rtk_dev_world_closest_points(const rtk_dev_world *w, const rtk_point_query *d_queries, size_t num_queries,
+	const rtk_ray_list *list, const rtk_world_filter *filter,
+	rtk_closest_record *d_records, uint32_t *d_instances /* may be NULL */, float *d_points /* may be NULL */, void *stream);
+int rtk_dev_world_closest_points_counted(const rtk_dev_world *w, const rtk_point_query *d_queries, size_t num_queries,
+	const rtk_world_filter *filter, rtk_closest_record *d_records, uint32_t *d_instances, float *d_points, rtk_trace_counters *out);
+/* (8-byte stack entries per lane the walk keeps on chip before it uses the spill area, for tests) */
+uint32_t rtk_amd_world_closest_stack_entries(void);
 
 /* Waits for `stream` and reports whether a launch of this scene on it overflowed a traversal stack
  * (RTK_AMD_ERR_BAD_SCENE; impossible for a validated tree -- the push is dropped, never written out of bounds). */

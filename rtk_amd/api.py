@@ -234,6 +234,7 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_dev_world_create", "rtk_dev_world_update", "rtk_dev_world_rebuild", "rtk_dev_world_get_info", "rtk_dev_world_free",
                      "rtk_dev_world_top_scene", "rtk_dev_world_trace_status", "rtk_dev_world_trace_rays", "rtk_dev_world_trace_rays_any",
                      "rtk_dev_world_trace_rays_counted", "rtk_amd_world_stack_entries",
+                     "rtk_dev_world_closest_points", "rtk_dev_world_closest_points_counted", "rtk_amd_world_closest_stack_entries",
                      "rtk_dev_trace_rays_count", "rtk_dev_trace_rays_all", "rtk_amd_allhits_stack_entries",
                      "rtk_dev_triangles_within_count", "rtk_dev_triangles_within_all", "rtk_dev_triangles_within_counted",
                      "rtk_amd_within_stack_entries",
@@ -366,6 +367,12 @@ def lib():
     L.rtk_dev_world_trace_rays_counted.restype = C.c_int
     L.rtk_amd_world_stack_entries.argtypes = []
     L.rtk_amd_world_stack_entries.restype = C.c_uint32
+    L.rtk_dev_world_closest_points.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(WorldFilter), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtk_dev_world_closest_points.restype = C.c_int
+    L.rtk_dev_world_closest_points_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(WorldFilter), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
+    L.rtk_dev_world_closest_points_counted.restype = C.c_int
+    L.rtk_amd_world_closest_stack_entries.argtypes = []
+    L.rtk_amd_world_closest_stack_entries.restype = C.c_uint32
     for fam in SWEEPS.values():
         fn, fn_any, fn_counted, entries = (getattr(L, name) for name in (fam.stem, fam.stem + "_any", fam.stem + "_counted", fam.stack_entries))
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter), C.c_void_p]
@@ -2154,7 +2161,7 @@ class DeviceScene:
 
 class DeviceWorld:
     """An instanced world (rtk_dev_world*; include/rtk_amd.h, "Instanced worlds"): placed copies of device scenes under a small
-    top tree, for rays. The object keeps its scenes alive; a scene that was refitted, split or rebuilt must be followed by
+    top tree, for rays and closest points. The object keeps its scenes alive; a scene that was refitted, split or rebuilt must be followed by
     update() before the next trace."""
 
     def __init__(self, handle, scenes):
@@ -2315,6 +2322,72 @@ class DeviceWorld:
         d = self.trace_any_device(to_device(rays), n, instance_mask=instance_mask, ignore_instance=ignore_instance)
         self.status()
         return d.cpu().numpy().astype(bool)
+
+
+    # -- closest points on the world (rtk_dev_world_closest_points): asynchronous on the current stream --
+
+    def closest_points_device(self, d_queries, n, d_records=None, d_instances=None, d_points=None, count=None, ids=None, instance_mask=None,
+                              ignore_instance=None, want_points=True):
+        """The nearest triangle over all instances to each of n queries (POINT_QUERY_DTYPE bytes on the device): returns
+        (d_records, d_instances, d_points): a uint8 cuda tensor of CLOSEST_RECORD_DTYPE records (prim: the primitive id in the
+        instance's scene), an int32 cuda tensor of instance numbers (-1 = RTK_PRIM_NONE on a miss) and a uint8 cuda tensor of 3
+        floats per query, world coordinates (want_points=False: NULL is passed and None returned). count / ids: cuda int64 tensors
+        naming the queries to answer; slots that are not listed are not written. ignore_instance is read at the query's slot."""
+        torch = _torch()
+        if d_records is None:
+            d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        if d_instances is None:
+            d_instances = torch.empty(n, dtype=torch.int32, device="cuda")
+        if not want_points:
+            d_points = None
+        elif d_points is None:
+            d_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        if ids is not None and count is None:
+            raise RtkError("DeviceWorld.closest_points_device: ids without count (a list's length lives on the device)")
+        l = make_ray_list(count, ids) if count is not None else None
+        f, _keep = self._filter(instance_mask, ignore_instance)
+        _check(lib().rtk_dev_world_closest_points(self.handle, C.c_void_p(d_queries.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                  C.byref(f) if f is not None else None, C.c_void_p(d_records.data_ptr()),
+                                                  C.c_void_p(d_instances.data_ptr()), C.c_void_p(d_points.data_ptr()) if d_points is not None else None,
+                                                  _stream_ptr()), "rtk_dev_world_closest_points")
+        self._keep = _keep
+        return d_records, d_instances, d_points
+
+    def closest_points_counted(self, d_queries, n, instance_mask=None, ignore_instance=None):
+        """closest_points_device of all n queries on the null stream, synchronous, with the visit counts of
+        rtk_dev_world_closest_points_counted: returns (d_records, d_instances, d_points, counts dict)."""
+        torch = _torch()
+        d_records = torch.empty(n * 16, dtype=torch.uint8, device="cuda")
+        d_instances = torch.empty(n, dtype=torch.int32, device="cuda")
+        d_points = torch.empty(n * 12, dtype=torch.uint8, device="cuda")
+        ctr = TraceCounters()
+        f, _keep = self._filter(instance_mask, ignore_instance)
+        torch.cuda.synchronize()
+        _check(lib().rtk_dev_world_closest_points_counted(self.handle, C.c_void_p(d_queries.data_ptr()), n, C.byref(f) if f is not None else None,
+                                                          C.c_void_p(d_records.data_ptr()), C.c_void_p(d_instances.data_ptr()),
+                                                          C.c_void_p(d_points.data_ptr()), C.byref(ctr)), "rtk_dev_world_closest_points_counted")
+        return d_records, d_instances, d_points, ctr.as_dict()
+
+    def closest_points(self, points, max_dist=None, instance_mask=None, ignore_instance=None):
+        """points: array-like (n, 3) float32. max_dist: a distance (scalar or one per point) beyond which a triangle does not
+        count, squared in float32; None = no limit (RTK_INF). Returns (records CLOSEST_RECORD_DTYPE, instances uint32, points
+        (n, 3) float32): prim == instance == 0xFFFFFFFF is a miss, whose point is the query itself. Waits for the stream."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        q = np.zeros(n, POINT_QUERY_DTYPE)
+        q["point"] = pts
+        if max_dist is None:
+            q["max_dist2"] = RTK_INF
+        else:
+            d = np.broadcast_to(np.asarray(max_dist, np.float32), (n,))
+            with np.errstate(over="ignore", invalid="ignore"):
+                q["max_dist2"] = d * d
+        if n == 0:
+            return np.zeros(0, CLOSEST_RECORD_DTYPE), np.zeros(0, np.uint32), np.zeros((0, 3), np.float32)
+        d_rec, d_inst, d_pts = self.closest_points_device(to_device(q), n, instance_mask=instance_mask, ignore_instance=ignore_instance)
+        self.status()
+        return (d_rec.cpu().numpy().view(CLOSEST_RECORD_DTYPE), d_inst.cpu().numpy().view(np.uint32),
+                d_pts.cpu().numpy().view(np.float32).reshape(n, 3))
 
 
 # -- the reference's own entry points, host pointers (reference rtk.h:126-130) --

@@ -185,6 +185,20 @@ extern "C" int rtk_dev_world_trace_rays_counted(const rtk_dev_world *w, const rt
 	return rtk_launch_world(w, d_rays, n, nullptr, filter, d_records, d_instances, nullptr, false, nullptr, out);
 }
 
+// Closest points on a world (rtk_world_closest.hip): the two doors of one launch
+extern "C" int rtk_dev_world_closest_points(const rtk_dev_world *w, const rtk_point_query *d_queries, size_t num_queries,
+	const rtk_ray_list *list, const rtk_world_filter *filter, rtk_closest_record *d_records, uint32_t *d_instances, float *d_points, void *stream)
+{
+	return rtk_launch_world_closest(w, d_queries, num_queries, list, filter, d_records, d_instances, d_points, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_world_closest_points_counted(const rtk_dev_world *w, const rtk_point_query *d_queries, size_t num_queries,
+	const rtk_world_filter *filter, rtk_closest_record *d_records, uint32_t *d_instances, float *d_points, rtk_trace_counters *out)
+{
+	if (!out) { rtk_set_error("rtk_dev_world_closest_points_counted: NULL counters"); return RTK_AMD_ERR_BAD_ARG; }
+	return rtk_launch_world_closest(w, d_queries, num_queries, nullptr, filter, d_records, d_instances, d_points, nullptr, out);
+}
+
 // Listed batches (rtk_ray_list): everything about the list that the host can see is refused here, before anything is launched
 static int listed_trace(const char *who, const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t num_rays, const rtk_ray_list *list,
 	rtk_hit_record *d_hits, uint8_t *d_occluded, bool any_hit, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream)

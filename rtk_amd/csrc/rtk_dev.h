@@ -441,6 +441,11 @@ int rtk_launch_obbsweep(const rtk_dev_scene *ds, const rtk_obb_sweep *d_sweeps, 
 // form of the closest one (synchronises the stream)
 int rtk_launch_world(const rtk_dev_world *w, const rtk_ray *d_rays, size_t n, const rtk_ray_list *list, const rtk_world_filter *filter,
 	rtk_hit_record *d_records, uint32_t *d_instances, uint8_t *d_blocked, bool any_hit, hipStream_t stream, rtk_trace_counters *counted = nullptr);
+// -- rtk_dev_world_closest_points / _counted (rtk_world_closest.hip) --
+// d_instances, d_points: each or NULL; a non-null `counted` makes it the counting form (synchronises the stream)
+int rtk_launch_world_closest(const rtk_dev_world *w, const rtk_point_query *d_queries, size_t n, const rtk_ray_list *list,
+	const rtk_world_filter *filter, rtk_closest_record *d_records, uint32_t *d_instances, float *d_points, hipStream_t stream,
+	rtk_trace_counters *counted = nullptr);
 // -- the look for an image nobody announced (rtk_detect.hip) --
 int rtk_detect_image(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, hipStream_t stream, uint32_t *w_out, uint32_t *h_out);
 // -- hit records to full hits, and rtk_trace_ray's one-ray launch (rtk_expand.hip) --

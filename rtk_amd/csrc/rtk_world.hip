@@ -33,48 +33,15 @@
 //
 // FLOATING POINT: compiled with -ffp-contract=off like every traversal; the operation order of the triangle test is normative.
 // Compiler's resource report (gfx950, -O3, kernel-resource-usage): WD_RESOURCES below.
-#include "rtk_dev.h"
+#include "rtk_world_internal.h"    // struct rtk_dev_world, DevWorldScene, the WD_ constants, WD_PUSH, rtk_world_launch
 #include "rtk_trace_shared.h"      // sse_min, sse_max
 #include "rtk_world_rule.h"
 
 #include <atomic>
-#include <mutex>
-#include <vector>
 
 // WD_RESOURCES (closest / any / closest FILT / any FILT / counting): VGPRs 95 / 89 / 97 / 90 / 102, scratch 0 and no VGPR spills in
 // every form (48 to 70 SGPRs spill into VGPR lanes), LDS 32 768 B per workgroup: LDS places five workgroups of four waves on a CU,
 // 5 waves per SIMD, and the registers allow 5 (up to 96 VGPRs) or 4. k_world_instances: 60 VGPRs, no LDS, no scratch.
-
-#define WD_THREADS 256u
-#define WD_WAVES (WD_THREADS / 64u)
-#define WD_LDS_STACK 16u           // entries per lane held in LDS: 32 KB per workgroup
-#define WD_REF_TOP 0xfffffffeu     // the sentinel: back to the top tree (never a leaf reference: a scene holds fewer than 2^30 slots)
-#define WD_DEAD 1u                 // DevWorldInstance.flags
-
-struct DevWorldScene {
-	const DevNode *nodes;
-	const DevTri *tris;
-	uint32_t num_nodes, num_tris;
-};
-static_assert(sizeof(DevWorldScene) == 24, "one scene of a world's table");
-
-struct rtk_dev_world {
-	int device = 0;
-	std::mutex mutex;                              // create, update, rebuild and info; a trace reads what they leave
-	std::vector<rtk_dev_scene *> scenes;           // borrowed
-	std::vector<DevWorldScene> scene_table;        // what d_scenes holds
-	uint32_t deepest = 0;                          // the largest stack_entries among the scenes, as of the last update
-	uint32_t num_instances = 0;
-	rtk_dev_scene *top = nullptr;                  // owned
-	SceneMem mem{ rtk_dev_malloc, rtk_dev_free };  // the four tables and the counter
-	DevWorldInstance *d_inst = nullptr;            // [num_instances]
-	rtk_placement *d_place = nullptr;              // [num_instances] as last given
-	float *d_proxy = nullptr;                      // [9 * num_instances]
-	DevWorldScene *d_scenes = nullptr;             // [num_scenes]
-	unsigned long long *d_dead = nullptr;          // dead instances, counted by k_world_instances
-	uint64_t dead = 0;
-	double build_ms = 0.0, update_ms = 0.0;
-};
 
 namespace {
 
@@ -197,13 +164,6 @@ __device__ __forceinline__ void wd_setup(float ox, float oy, float oz, float dx,
 	// near and far plane by the direction's sign BIT (rtk.c:152-154, 458-463)
 	s.ngx = (__float_as_uint(dx) >> 31) != 0u; s.ngy = (__float_as_uint(dy) >> 31) != 0u; s.ngz = (__float_as_uint(dz) >> 31) != 0u;
 }
-
-#define WD_PUSH(e_)                                                                                                        \
-	do {                                                                                                                   \
-		if (sp < WD_LDS_STACK) { stk[sp][lane] = (e_); sp++; }                                                             \
-		else if (sp - WD_LDS_STACK < p.spill_cap) { p.spill[(size_t)(sp - WD_LDS_STACK) * p.spill_stride + glane] = (e_); sp++; if (COUNT) c_spills++; } \
-		else p.counter[RTK_ERROR_WORD] = 1ull;                                                                             \
-	} while (0)
 
 // ANY: one byte per ray, retired at the first candidate. COUNT: the visit counts of rtk_dev_world_trace_rays_counted. FILT: the
 // instance mask and the per-ray ignored instance
@@ -692,14 +652,8 @@ int rtk_launch_world(const rtk_dev_world *w_c, const rtk_ray *d_rays, size_t n, 
 	rtk_dev_world *w = const_cast<rtk_dev_world *>(w_c);
 	const char *who = any_hit ? "rtk_dev_world_trace_rays_any" : counted ? "rtk_dev_world_trace_rays_counted" : "rtk_dev_world_trace_rays";
 	// everything the host can see is refused here, before any HIP call
-	if (!w || (n && (!d_rays || (any_hit ? !d_blocked : !d_records)))) { rtk_set_error("%s: NULL world, rays or output", who); return RTK_AMD_ERR_BAD_ARG; }
-	if (list && (list->struct_size < sizeof(rtk_ray_list) || list->flags != 0u || !list->d_count)) {
-		rtk_set_error("%s: bad list (struct_size %u, flags %#x, d_count %p)", who, list->struct_size, list->flags, (const void *)list->d_count);
-		return RTK_AMD_ERR_BAD_ARG;
-	}
-	if (filter && (filter->struct_size < sizeof(rtk_world_filter) || filter->flags != 0u)) { rtk_set_error("%s: bad rtk_world_filter (struct_size %u, flags %#x)", who, filter->struct_size, filter->flags); return RTK_AMD_ERR_BAD_ARG; }
-	if (filter && filter->d_instance_mask && filter->instance_mask_bits == 0) { rtk_set_error("%s: instance mask without instance_mask_bits", who); return RTK_AMD_ERR_BAD_ARG; }
-	if (n >= ((size_t)1 << 32)) { rtk_set_error("%s: %zu rays: a batch holds fewer than 2^32", who, n); return RTK_AMD_ERR_BAD_ARG; }
+	const int refused = rtk_world_refuse(who, "rays", w, n, d_rays && (any_hit ? d_blocked != nullptr : d_records != nullptr), list, filter);
+	if (refused != RTK_AMD_OK) return refused;
 	if (counted) *counted = rtk_trace_counters();
 	if (n == 0) return RTK_AMD_OK;
 	if (!rtk_on_scene_device(w->top, who)) return RTK_AMD_ERR_BAD_ARG;
@@ -714,50 +668,7 @@ int rtk_launch_world(const rtk_dev_world *w_c, const rtk_ray *d_rays, size_t n, 
 	p.blocked = d_blocked;
 	const bool filtered = filter && (filter->d_instance_mask || filter->d_ignore_instance);
 	if (filtered) { p.mask = filter->d_instance_mask; p.mask_bits = filter->instance_mask_bits; p.ignore_instance = filter->d_ignore_instance; }
-
-	std::lock_guard<std::mutex> wlock(w->mutex);
-	rtk_dev_scene *top = w->top;
-	p.inst = w->d_inst; p.scenes = w->d_scenes;
-	p.num_instances = w->num_instances; p.num_scenes = (uint32_t)w->scenes.size();
-	const size_t blocks_needed = (n + WD_THREADS - 1u) / WD_THREADS;
-	size_t grid = (size_t)(top->num_cus > 0 ? top->num_cus : 1) * (size_t)world_blocks_per_cu(top->device);
-	if (grid > blocks_needed) grid = blocks_needed;
-
-	// the scratch set of (top tree, stream), held until the launch is enqueued; the top tree's view and tree record are read under
-	// the lock a rebuild replaces them under
-	std::lock_guard<std::mutex> lock(top->scratch_mutex);
-	p.top_nodes = top->view.nodes; p.top_tris = top->view.tris; p.top_num_nodes = top->view.num_nodes; p.top_num_tris = top->view.num_tris;
-	p.bound = top->tree.bound_raw;
-	const size_t entries = (size_t)top->tree.stack_entries() + 1u + w->deepest;
-	const size_t spill_cap = entries > WD_LDS_STACK ? entries - WD_LDS_STACK : 0;
-	LaunchScratch *sc = top->scratch.get(stream);
-	if (!sc) return RTK_AMD_ERR_OOM;
-	if (spill_cap) {
-		const int rc = sc->grow_spill(grid * WD_THREADS, spill_cap, sizeof(uint2));
-		if (rc != RTK_AMD_OK) return rc;
-	}
-	p.spill = sc->spill.as<uint2>();
-	p.spill_stride = (uint32_t)(spill_cap ? sc->spill.capacity : 0);
-	p.spill_cap = (uint32_t)spill_cap;
-	p.counter = sc->d_counter;
-	if (!counted) {
-		hipLaunchKernelGGL(world_form((any_hit ? 1 : 0) | (filtered ? 2 : 0)), dim3((unsigned)grid), dim3(WD_THREADS), 0, stream, p);
-		RTK_HIP_CHECK(hipGetLastError(), RTK_AMD_ERR_HIP);
-		return RTK_AMD_OK;
-	}
-	// the counting form: the visit counters start from zero, are brought home and the stream is waited for
-	unsigned long long c[8], err = 0;
-	RTK_HIP_CHECK(hipMemsetAsync(sc->d_counter, 0, RTK_COUNTER_WORDS * sizeof(unsigned long long), stream), RTK_AMD_ERR_HIP);
-	hipLaunchKernelGGL(world_form(4), dim3((unsigned)grid), dim3(WD_THREADS), 0, stream, p);
-	RTK_HIP_CHECK(hipGetLastError(), RTK_AMD_ERR_HIP);
-	RTK_HIP_CHECK(hipMemcpyAsync(c, sc->d_counter, sizeof(c), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
-	RTK_HIP_CHECK(hipMemcpyAsync(&err, sc->d_counter + RTK_ERROR_WORD, sizeof(err), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
-	RTK_HIP_CHECK(hipStreamSynchronize(stream), RTK_AMD_ERR_HIP);
-	counted->rays = c[1]; counted->nodes = c[2]; counted->leaves = c[3]; counted->triangles = c[4]; counted->hits = c[5]; counted->stack_spills = c[6];
-	if (err) {
-		(void)hipMemsetAsync(sc->d_counter + RTK_ERROR_WORD, 0, sizeof(err), stream);
-		rtk_set_error("rtk_dev_world_trace_rays_counted: traversal stack overflow (corrupted scene)");
-		return RTK_AMD_ERR_BAD_SCENE;
-	}
-	return RTK_AMD_OK;
+	// (the largest |plane| of the top tree: read under the lock a rebuild replaces it under)
+	return rtk_world_launch(w, n, stream, world_blocks_per_cu(w->device), world_form((any_hit ? 1 : 0) | (filtered ? 2 : 0)), world_form(4), p,
+		[](const rtk_dev_scene *top, WorldParams &q) { q.bound = top->tree.bound_raw; }, counted, "rtk_dev_world_trace_rays_counted");
 }
