@@ -262,6 +262,14 @@ SWEEPS = {f.name: f for f in (
     Sweep("capsules", "rtk_dev_sweep_capsules", ("d_points", "d_axis_points"), CAPSULE_SWEEP_DTYPE, "rtk_amd_capsule_stack_entries"),
     Sweep("obbs", "rtk_dev_sweep_obbs", ("d_centres", "d_normals"), OBB_SWEEP_DTYPE, "rtk_amd_obbsweep_stack_entries"))}
 
+# the three overlap queries (one walk, rtk_amd/csrc/rtk_overlap_walk.h): the name in the Python methods (count_<name>_device,
+# <name>_all_device), the C symbol stem, the symbol that tells the on-chip stack entries, whether the calls take a TouchFilter
+Overlap = collections.namedtuple("Overlap", "name stem stack_entries filtered")
+OVERLAPS = {f.name: f for f in (
+    Overlap("in_boxes", "rtk_dev_triangles_in_box", "rtk_amd_box_stack_entries", False),
+    Overlap("in_obbs", "rtk_dev_triangles_in_obb", "rtk_amd_obb_stack_entries", False),
+    Overlap("touching", "rtk_dev_triangles_touching", "rtk_amd_touch_stack_entries", True))}
+
 _lib = None
 
 
@@ -391,30 +399,15 @@ def lib():
     L.rtk_dev_triangles_within_counted.restype = C.c_int
     L.rtk_amd_within_stack_entries.argtypes = []
     L.rtk_amd_within_stack_entries.restype = C.c_uint32
-    L.rtk_dev_triangles_in_box_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p]
-    L.rtk_dev_triangles_in_box_count.restype = C.c_int
-    L.rtk_dev_triangles_in_box_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.rtk_dev_triangles_in_box_all.restype = C.c_int
-    L.rtk_dev_triangles_in_box_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
-    L.rtk_dev_triangles_in_box_counted.restype = C.c_int
-    L.rtk_amd_box_stack_entries.argtypes = []
-    L.rtk_amd_box_stack_entries.restype = C.c_uint32
-    L.rtk_dev_triangles_in_obb_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p]
-    L.rtk_dev_triangles_in_obb_count.restype = C.c_int
-    L.rtk_dev_triangles_in_obb_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.rtk_dev_triangles_in_obb_all.restype = C.c_int
-    L.rtk_dev_triangles_in_obb_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
-    L.rtk_dev_triangles_in_obb_counted.restype = C.c_int
-    L.rtk_amd_obb_stack_entries.argtypes = []
-    L.rtk_amd_obb_stack_entries.restype = C.c_uint32
-    L.rtk_dev_triangles_touching_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(TouchFilter), C.c_void_p, C.c_void_p]
-    L.rtk_dev_triangles_touching_count.restype = C.c_int
-    L.rtk_dev_triangles_touching_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(TouchFilter), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.rtk_dev_triangles_touching_all.restype = C.c_int
-    L.rtk_dev_triangles_touching_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TouchFilter), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
-    L.rtk_dev_triangles_touching_counted.restype = C.c_int
-    L.rtk_amd_touch_stack_entries.argtypes = []
-    L.rtk_amd_touch_stack_entries.restype = C.c_uint32
+    for fam in OVERLAPS.values():
+        fn_count, fn_all, fn_counted, entries = (getattr(L, name) for name in (fam.stem + "_count", fam.stem + "_all", fam.stem + "_counted", fam.stack_entries))
+        filt = [C.POINTER(TouchFilter)] if fam.filtered else []
+        fn_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList)] + filt + [C.c_void_p, C.c_void_p]
+        fn_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList)] + filt + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        fn_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + filt + [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
+        fn_count.restype = fn_all.restype = fn_counted.restype = C.c_int
+        entries.argtypes = []
+        entries.restype = C.c_uint32
     L.rtk_dev_closest_triangles.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(TouchFilter), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rtk_dev_closest_triangles.restype = C.c_int
     L.rtk_dev_closest_triangles_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TouchFilter), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
@@ -1324,50 +1317,102 @@ class DeviceScene:
         _, rec, pts, written = self.triangles_within(points, max_dist, max_per_point=k)
         return rec.reshape(n, k), pts.reshape(n, k, 3), written
 
-    # -- triangles that touch a box (rtk_dev_triangles_in_box_count / _all): asynchronous on the current stream --
+    # -- the three overlap queries (triangles that touch a box, an oriented box, a triangle; a row of OVERLAPS each): asynchronous
+    # on the current stream, nothing here waits for it. first_prim / skip_shared are the touching calls' alone --
+
+    def _overlap_count_device(self, fam, d_q, n, d_counts, count, ids, first_prim=None, skip_shared=False):
+        """count_<fam.name>_device"""
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        if ids is not None and count is None:
+            raise RtkError("count_%s_device: ids without count (a list's length lives on the device)" % fam.name)
+        l = make_ray_list(count, ids) if count is not None else None
+        f = make_touch_filter(first_prim, skip_shared)
+        filt = (C.byref(f) if f is not None else None,) if fam.filtered else ()
+        _check(getattr(lib(), fam.stem + "_count")(self.handle, C.c_void_p(d_q.data_ptr()), n, C.byref(l) if l is not None else None, *filt,
+                                                   C.c_void_p(d_counts.data_ptr()), _stream_ptr()), fam.stem + "_count")
+        return d_counts
+
+    def _overlap_all_device(self, fam, d_q, n, d_offsets, d_prims, d_written, count, ids, first_prim=None, skip_shared=False):
+        """<fam.name>_all_device"""
+        if ids is not None and count is None:
+            raise RtkError("%s_all_device: ids without count (a list's length lives on the device)" % fam.name)
+        l = make_ray_list(count, ids) if count is not None else None
+        f = make_touch_filter(first_prim, skip_shared)
+        filt = (C.byref(f) if f is not None else None,) if fam.filtered else ()
+        _check(getattr(lib(), fam.stem + "_all")(self.handle, C.c_void_p(d_q.data_ptr()), n, C.byref(l) if l is not None else None, *filt,
+                                                 C.c_void_p(d_offsets.data_ptr()), C.c_void_p(d_prims.data_ptr()),
+                                                 C.c_void_p(d_written.data_ptr()) if d_written is not None else None, _stream_ptr()), fam.stem + "_all")
+        return d_written
+
+    def _overlap_counted(self, fam, d_q, n, d_offsets, d_prims, d_counts, first_prim=None, skip_shared=False):
+        """triangles_<fam.name>_counted: on the null stream, synchronous"""
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        ctr = TraceCounters()
+        f = make_touch_filter(first_prim, skip_shared)
+        filt = (C.byref(f) if f is not None else None,) if fam.filtered else ()
+        torch.cuda.synchronize()
+        _check(getattr(lib(), fam.stem + "_counted")(self.handle, C.c_void_p(d_q.data_ptr()), n, *filt,
+                                                     C.c_void_p(d_offsets.data_ptr()) if d_offsets is not None else None,
+                                                     C.c_void_p(d_prims.data_ptr()) if d_prims is not None else None,
+                                                     C.c_void_p(d_counts.data_ptr()), C.byref(ctr)), fam.stem + "_counted")
+        return d_counts, ctr.as_dict()
+
+    def _overlap_lists(self, fam, d_q, n, k, first_prim=None, skip_shared=False):
+        """count, prefix sum and fill (or, with k, offsets i * k and the fill) on the current stream -> (d_offsets int64 [n + 1],
+        d_prims int32 [max(total, 1)], d_written int32 [n], total). Only the size of the buffer is read back."""
+        torch = _torch()
+        if k is None:
+            d_counts = self._overlap_count_device(fam, d_q, n, None, None, None, first_prim, skip_shared)
+            d_offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+            d_offsets[1:] = torch.cumsum(d_counts, 0, dtype=torch.int64)
+            total = int(d_offsets[n].item())                 # (the one read-back: how many ids to allocate)
+        else:
+            d_offsets = torch.arange(n + 1, dtype=torch.int64, device="cuda") * k
+            total = n * k
+        d_prims = torch.zeros(max(total, 1), dtype=torch.int32, device="cuda")
+        d_written = torch.empty(n, dtype=torch.int32, device="cuda")
+        self._overlap_all_device(fam, d_q, n, d_offsets, d_prims, d_written, None, None, first_prim, skip_shared)
+        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
+        return d_offsets, d_prims, d_written, total
+
+    def _overlap_lists_host(self, fam, q, max_per_query, who, first_prim=None, skip_shared=False):
+        """_overlap_lists of host records q (max_per_query: None or k, refused in `who`'s name if negative) as numpy arrays:
+        (offsets int64[n + 1], prims uint32[offsets[n]], written uint32[n])"""
+        n = q.shape[0]
+        if n == 0:
+            return np.zeros(1, np.int64), np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+        k = None
+        if max_per_query is not None:
+            k = int(max_per_query)
+            if k < 0:
+                raise RtkError("%s %r" % (who, max_per_query))
+        d_offsets, d_prims, d_written, total = self._overlap_lists(fam, to_device(q), n, k, first_prim, skip_shared)
+        return d_offsets.cpu().numpy(), d_prims.cpu().numpy().view(np.uint32)[:total], d_written.cpu().numpy().view(np.uint32)
+
+    # -- triangles that touch a box (rtk_dev_triangles_in_box_count / _all) --
 
     def count_in_boxes_device(self, d_boxes, n, d_counts=None, count=None, ids=None):
         """The number of triangles that touch each of n boxes (BOX_QUERY_DTYPE bytes on the device, or a float32 [n, 6] cuda
         tensor of lo, hi; include/rtk_amd.h, "Triangles that touch a box"): a cuda tensor of n uint32 words (d_counts: any
         cuda tensor of at least 4 n bytes; None: a new int32 tensor). count / ids: cuda int64 tensors naming the queries to
         answer, as for closest_points_device; slots that are not listed are not written. Nothing waits for the stream."""
-        torch = _torch()
-        if d_counts is None:
-            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
-        if ids is not None and count is None:
-            raise RtkError("count_in_boxes_device: ids without count (a list's length lives on the device)")
-        l = make_ray_list(count, ids) if count is not None else None
-        _check(lib().rtk_dev_triangles_in_box_count(self.handle, C.c_void_p(d_boxes.data_ptr()), n, C.byref(l) if l is not None else None,
-                                                    C.c_void_p(d_counts.data_ptr()), _stream_ptr()), "rtk_dev_triangles_in_box_count")
-        return d_counts
+        return self._overlap_count_device(OVERLAPS["in_boxes"], d_boxes, n, d_counts, count, ids)
 
     def in_boxes_all_device(self, d_boxes, n, d_offsets, d_prims, d_written=None, count=None, ids=None):
         """Box i's triangles, ascending global primitive ids (uint32), into entries d_offsets[i] .. d_offsets[i + 1] of d_prims:
         as many as the box has or the segment holds, the lowest ids first. d_offsets: a cuda int64 tensor of n + 1 entries.
         d_written: a cuda tensor of 4 n bytes, or None (the call gets NULL). Entries beyond written[i], and outside every
         segment, are not written. count / ids as for count_in_boxes_device. Nothing waits for the stream."""
-        if ids is not None and count is None:
-            raise RtkError("in_boxes_all_device: ids without count (a list's length lives on the device)")
-        l = make_ray_list(count, ids) if count is not None else None
-        _check(lib().rtk_dev_triangles_in_box_all(self.handle, C.c_void_p(d_boxes.data_ptr()), n, C.byref(l) if l is not None else None,
-                                                  C.c_void_p(d_offsets.data_ptr()), C.c_void_p(d_prims.data_ptr()),
-                                                  C.c_void_p(d_written.data_ptr()) if d_written is not None else None,
-                                                  _stream_ptr()), "rtk_dev_triangles_in_box_all")
-        return d_written
+        return self._overlap_all_device(OVERLAPS["in_boxes"], d_boxes, n, d_offsets, d_prims, d_written, count, ids)
 
     def triangles_in_boxes_counted(self, d_boxes, n, d_offsets=None, d_prims=None, d_counts=None):
         """count_in_boxes_device (d_offsets None) or in_boxes_all_device of all n boxes on the null stream, synchronous, with the
         visit counts of rtk_dev_triangles_in_box_counted: returns (d_counts -- the counts, or the written numbers --, counts dict)."""
-        torch = _torch()
-        if d_counts is None:
-            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
-        ctr = TraceCounters()
-        torch.cuda.synchronize()
-        _check(lib().rtk_dev_triangles_in_box_counted(self.handle, C.c_void_p(d_boxes.data_ptr()), n,
-                                                      C.c_void_p(d_offsets.data_ptr()) if d_offsets is not None else None,
-                                                      C.c_void_p(d_prims.data_ptr()) if d_prims is not None else None,
-                                                      C.c_void_p(d_counts.data_ptr()), C.byref(ctr)), "rtk_dev_triangles_in_box_counted")
-        return d_counts, ctr.as_dict()
+        return self._overlap_counted(OVERLAPS["in_boxes"], d_boxes, n, d_offsets, d_prims, d_counts)
 
     def triangles_in_boxes(self, boxes, max_per_box=None):
         """Every triangle that touches each box, or with max_per_box=k the k lowest ids of them. boxes: array-like (n, 6) float32
@@ -1376,29 +1421,9 @@ class DeviceScene:
         the device and the fill, enqueued without a host wait in between (only the size of the buffer is read back, to allocate
         it), and written[i] == offsets[i + 1] - offsets[i]. With it: offsets[i] = i * k, no count, and the entries of a segment
         beyond written[i] are zero."""
-        torch = _torch()
         boxes = np.asarray(boxes)
         q = np.ascontiguousarray(boxes if boxes.dtype == BOX_QUERY_DTYPE else np.asarray(boxes, np.float32).reshape(-1, 6))
-        n = q.shape[0]
-        if n == 0:
-            return np.zeros(1, np.int64), np.zeros(0, np.uint32), np.zeros(0, np.uint32)
-        d_q = to_device(q)
-        if max_per_box is None:
-            d_counts = self.count_in_boxes_device(d_q, n)
-            d_offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
-            d_offsets[1:] = torch.cumsum(d_counts, 0, dtype=torch.int64)
-            total = int(d_offsets[n].item())                 # (the one read-back: how many ids to allocate)
-        else:
-            k = int(max_per_box)
-            if k < 0:
-                raise RtkError("triangles_in_boxes: max_per_box %r" % (max_per_box,))
-            d_offsets = torch.arange(n + 1, dtype=torch.int64, device="cuda") * k
-            total = n * k
-        d_prims = torch.zeros(max(total, 1), dtype=torch.int32, device="cuda")
-        d_written = torch.empty(n, dtype=torch.int32, device="cuda")
-        self.in_boxes_all_device(d_q, n, d_offsets, d_prims, d_written)
-        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
-        return d_offsets.cpu().numpy(), d_prims.cpu().numpy().view(np.uint32)[:total], d_written.cpu().numpy().view(np.uint32)
+        return self._overlap_lists_host(OVERLAPS["in_boxes"], q, max_per_box, "triangles_in_boxes: max_per_box")
 
     def occupancy(self, lo, hi, shape):
         """A bool cuda tensor of `shape` (nx, ny, nz): true where at least one triangle touches the voxel. The voxel faces are
@@ -1425,71 +1450,26 @@ class DeviceScene:
         n uint32 words (d_counts: any cuda tensor of at least 4 n bytes; None: a new int32 tensor). count / ids: cuda int64
         tensors naming the queries to answer, as for count_in_boxes_device; slots that are not listed are not written. Nothing
         waits for the stream."""
-        torch = _torch()
-        if d_counts is None:
-            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
-        if ids is not None and count is None:
-            raise RtkError("count_in_obbs_device: ids without count (a list's length lives on the device)")
-        l = make_ray_list(count, ids) if count is not None else None
-        _check(lib().rtk_dev_triangles_in_obb_count(self.handle, C.c_void_p(d_obbs.data_ptr()), n, C.byref(l) if l is not None else None,
-                                                    C.c_void_p(d_counts.data_ptr()), _stream_ptr()), "rtk_dev_triangles_in_obb_count")
-        return d_counts
+        return self._overlap_count_device(OVERLAPS["in_obbs"], d_obbs, n, d_counts, count, ids)
 
     def in_obbs_all_device(self, d_obbs, n, d_offsets, d_prims, d_written=None, count=None, ids=None):
         """Oriented box i's triangles, ascending global primitive ids (uint32), into entries d_offsets[i] .. d_offsets[i + 1] of
         d_prims: as many as the box has or the segment holds, the lowest ids first. d_offsets: a cuda int64 tensor of n + 1
         entries. d_written: a cuda tensor of 4 n bytes, or None (the call gets NULL). Entries beyond written[i], and outside every
         segment, are not written. count / ids as for count_in_obbs_device. Nothing waits for the stream."""
-        if ids is not None and count is None:
-            raise RtkError("in_obbs_all_device: ids without count (a list's length lives on the device)")
-        l = make_ray_list(count, ids) if count is not None else None
-        _check(lib().rtk_dev_triangles_in_obb_all(self.handle, C.c_void_p(d_obbs.data_ptr()), n, C.byref(l) if l is not None else None,
-                                                  C.c_void_p(d_offsets.data_ptr()), C.c_void_p(d_prims.data_ptr()),
-                                                  C.c_void_p(d_written.data_ptr()) if d_written is not None else None,
-                                                  _stream_ptr()), "rtk_dev_triangles_in_obb_all")
-        return d_written
+        return self._overlap_all_device(OVERLAPS["in_obbs"], d_obbs, n, d_offsets, d_prims, d_written, count, ids)
 
     def triangles_in_obbs_counted(self, d_obbs, n, d_offsets=None, d_prims=None, d_counts=None):
         """count_in_obbs_device (d_offsets None) or in_obbs_all_device of all n boxes on the null stream, synchronous, with the
         visit counts of rtk_dev_triangles_in_obb_counted: returns (d_counts -- the counts, or the written numbers --, counts dict)."""
-        torch = _torch()
-        if d_counts is None:
-            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
-        ctr = TraceCounters()
-        torch.cuda.synchronize()
-        _check(lib().rtk_dev_triangles_in_obb_counted(self.handle, C.c_void_p(d_obbs.data_ptr()), n,
-                                                      C.c_void_p(d_offsets.data_ptr()) if d_offsets is not None else None,
-                                                      C.c_void_p(d_prims.data_ptr()) if d_prims is not None else None,
-                                                      C.c_void_p(d_counts.data_ptr()), C.byref(ctr)), "rtk_dev_triangles_in_obb_counted")
-        return d_counts, ctr.as_dict()
+        return self._overlap_counted(OVERLAPS["in_obbs"], d_obbs, n, d_offsets, d_prims, d_counts)
 
     def triangles_in_obbs(self, centres, half, rotation, max_per_box=None):
         """Every triangle that touches each oriented box, or with max_per_box=k the k lowest ids of them. centres: (n, 3); half:
         the half extents along the box's own axes, (n, 3), (3,) or a scalar (a cube); rotation: (n, 3, 3) or (3, 3) matrices whose
         ROWS are the box's axes in scene coordinates, or (n, 4) or (4,) quaternions (x, y, z, w) (see obb_axes). Returns what
         triangles_in_boxes returns: (offsets int64[n + 1], prims uint32[offsets[n]], written uint32[n])."""
-        torch = _torch()
-        q = obb_query_array(centres, half, rotation)
-        n = q.shape[0]
-        if n == 0:
-            return np.zeros(1, np.int64), np.zeros(0, np.uint32), np.zeros(0, np.uint32)
-        d_q = to_device(q)
-        if max_per_box is None:
-            d_counts = self.count_in_obbs_device(d_q, n)
-            d_offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
-            d_offsets[1:] = torch.cumsum(d_counts, 0, dtype=torch.int64)
-            total = int(d_offsets[n].item())                 # (the one read-back: how many ids to allocate)
-        else:
-            k = int(max_per_box)
-            if k < 0:
-                raise RtkError("triangles_in_obbs: max_per_box %r" % (max_per_box,))
-            d_offsets = torch.arange(n + 1, dtype=torch.int64, device="cuda") * k
-            total = n * k
-        d_prims = torch.zeros(max(total, 1), dtype=torch.int32, device="cuda")
-        d_written = torch.empty(n, dtype=torch.int32, device="cuda")
-        self.in_obbs_all_device(d_q, n, d_offsets, d_prims, d_written)
-        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
-        return d_offsets.cpu().numpy(), d_prims.cpu().numpy().view(np.uint32)[:total], d_written.cpu().numpy().view(np.uint32)
+        return self._overlap_lists_host(OVERLAPS["in_obbs"], obb_query_array(centres, half, rotation), max_per_box, "triangles_in_obbs: max_per_box")
 
     def occupancy_oriented(self, centre, half, rotation, shape):
         """A bool cuda tensor of `shape` (nx, ny, nz): true where at least one triangle touches the cell of the nx x ny x nz grid
@@ -1509,65 +1489,24 @@ class DeviceScene:
         tensors naming the queries to answer, as for closest_points_device; slots that are not listed are not written.
         first_prim: a cuda tensor of n 32-bit words, query i keeps ids >= first_prim[i]; skip_shared: records that share a
         vertex position with the query are left out. Nothing waits for the stream."""
-        torch = _torch()
-        if d_counts is None:
-            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
-        if ids is not None and count is None:
-            raise RtkError("count_touching_device: ids without count (a list's length lives on the device)")
-        l = make_ray_list(count, ids) if count is not None else None
-        f = make_touch_filter(first_prim, skip_shared)
-        _check(lib().rtk_dev_triangles_touching_count(self.handle, C.c_void_p(d_tris.data_ptr()), n, C.byref(l) if l is not None else None,
-                                                      C.byref(f) if f is not None else None, C.c_void_p(d_counts.data_ptr()), _stream_ptr()),
-               "rtk_dev_triangles_touching_count")
-        return d_counts
+        return self._overlap_count_device(OVERLAPS["touching"], d_tris, n, d_counts, count, ids, first_prim, skip_shared)
 
     def touching_all_device(self, d_tris, n, d_offsets, d_prims, d_written=None, count=None, ids=None, first_prim=None, skip_shared=False):
         """Query i's triangles, ascending global primitive ids (uint32), into entries d_offsets[i] .. d_offsets[i + 1] of d_prims:
         as many as it meets or the segment holds, the lowest ids first. d_offsets: a cuda int64 tensor of n + 1 entries.
         d_written: a cuda tensor of 4 n bytes, or None (the call gets NULL). Entries beyond written[i], and outside every
         segment, are not written. The other arguments as for count_touching_device. Nothing waits for the stream."""
-        if ids is not None and count is None:
-            raise RtkError("touching_all_device: ids without count (a list's length lives on the device)")
-        l = make_ray_list(count, ids) if count is not None else None
-        f = make_touch_filter(first_prim, skip_shared)
-        _check(lib().rtk_dev_triangles_touching_all(self.handle, C.c_void_p(d_tris.data_ptr()), n, C.byref(l) if l is not None else None,
-                                                    C.byref(f) if f is not None else None, C.c_void_p(d_offsets.data_ptr()),
-                                                    C.c_void_p(d_prims.data_ptr()), C.c_void_p(d_written.data_ptr()) if d_written is not None else None,
-                                                    _stream_ptr()), "rtk_dev_triangles_touching_all")
-        return d_written
+        return self._overlap_all_device(OVERLAPS["touching"], d_tris, n, d_offsets, d_prims, d_written, count, ids, first_prim, skip_shared)
 
     def triangles_touching_counted(self, d_tris, n, d_offsets=None, d_prims=None, d_counts=None, first_prim=None, skip_shared=False):
         """count_touching_device (d_offsets None) or touching_all_device of all n queries on the null stream, synchronous, with the
         visit counts of rtk_dev_triangles_touching_counted: returns (d_counts -- the counts, or the written numbers --, counts dict)."""
-        torch = _torch()
-        if d_counts is None:
-            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
-        ctr = TraceCounters()
-        f = make_touch_filter(first_prim, skip_shared)
-        torch.cuda.synchronize()
-        _check(lib().rtk_dev_triangles_touching_counted(self.handle, C.c_void_p(d_tris.data_ptr()), n, C.byref(f) if f is not None else None,
-                                                        C.c_void_p(d_offsets.data_ptr()) if d_offsets is not None else None,
-                                                        C.c_void_p(d_prims.data_ptr()) if d_prims is not None else None,
-                                                        C.c_void_p(d_counts.data_ptr()), C.byref(ctr)), "rtk_dev_triangles_touching_counted")
-        return d_counts, ctr.as_dict()
+        return self._overlap_counted(OVERLAPS["touching"], d_tris, n, d_offsets, d_prims, d_counts, first_prim, skip_shared)
 
     def _touching_on_device(self, d_q, n, k, d_first, skip_shared):
         """count, prefix sum and fill (or, with k, offsets i * k and the fill) on the current stream -> (d_offsets int64 [n + 1],
         d_prims int32 [max(total, 1)], d_written int32 [n], total). Only the size of the buffer is read back."""
-        torch = _torch()
-        if k is None:
-            d_counts = self.count_touching_device(d_q, n, first_prim=d_first, skip_shared=skip_shared)
-            d_offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
-            d_offsets[1:] = torch.cumsum(d_counts, 0, dtype=torch.int64)
-            total = int(d_offsets[n].item())                 # (the one read-back: how many ids to allocate)
-        else:
-            d_offsets = torch.arange(n + 1, dtype=torch.int64, device="cuda") * k
-            total = n * k
-        d_prims = torch.zeros(max(total, 1), dtype=torch.int32, device="cuda")
-        d_written = torch.empty(n, dtype=torch.int32, device="cuda")
-        self.touching_all_device(d_q, n, d_offsets, d_prims, d_written, first_prim=d_first, skip_shared=skip_shared)
-        _check(lib().rtk_dev_trace_status(self.handle, _stream_ptr()), "rtk_dev_trace_status")
-        return d_offsets, d_prims, d_written, total
+        return self._overlap_lists(OVERLAPS["touching"], d_q, n, k, d_first, skip_shared)
 
     def triangles_touching(self, tris, max_per_tri=None, first_prim=None, skip_shared=False):
         """Every triangle of the scene that each query triangle meets, or with max_per_tri=k the k lowest ids of them. tris:

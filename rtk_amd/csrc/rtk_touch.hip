@@ -3,15 +3,9 @@
 // first `room` --, by the rule of rtk_touch_rule.h. The result is a function of the scene's triangle records and the query alone
 // (DESIGN.md "Triangles that touch a triangle"): the tree and the order of the walk only decide which records are never looked at.
 //
-// k_box's frame (rtk_box.hip): one query per lane of a 64-wide wave, a fixed grid of resident workgroups that steps through the
-// batch, exact 128-byte nodes only, a leaf as its run of DevTri records up to RTK_TRI_LAST, one at a time through
-// rtk_touch_candidate, the stack [entry][lane] in LDS with the deeper part in the spill area of the (scene, stream) scratch set, a
-// push that fits neither dropped WITHOUT advancing and flagged in the stream's launch-error word. A child word beyond the node
-// array and a slot beyond the triangle array are not followed. The skip is rtk_box_skip against the query triangle's own box,
-// comparisons only and static, so a stack entry is a bare 4-byte reference, the order of the walk is irrelevant, and the fill
-// form walks what the count form walks; a candidate's id goes into the segment through rtk_box_insert with the segment's last
-// entry kept in a register. A list that names a query twice: the first lane to claim it (one bit per query in the scratch
-// set, cleared ahead of the launch) answers it.
+// The walk, the stack and the launch are rtk_overlap_walk.h's; this file is the triangle: the skip is rtk_box_skip against the
+// query triangle's own box, a record goes through rtk_touch_candidate, and a launch carries the filter (the slots' first_prim
+// and the flags).
 //
 // WHAT IS HOISTED (rtk_touch_hoist, once per query, 45 floats of which 36 are distinct registers: ea0 is a1 - a0): the query's
 // vertex 0, its box, a1 - a0 and a2 - a0, its three edges, nA and the three nA X ea_i; a1 and a2 themselves stay for the
@@ -22,20 +16,17 @@
 // them in registers or form them again, the bits being the same.
 //
 // FLOATING POINT: the flags of rtk_closest.hip (no contraction); every bit is the rule header's.
-#include "rtk_dev.h"
+#include "rtk_overlap_walk.h"
 #include "rtk_touch_rule.h"
-
-#include <atomic>
-#include <mutex>
 
 // TC_RESOURCES: the compiler's report (gfx950, -O3, -Rpass-analysis=kernel-resource-usage) for each instantiated form
 // <FILL, COUNT>; scratch 0, no VGPR spills and no AGPRs in every one of them; the SGPRs past the 106 it may use go to lanes of a
 // VGPR (counted in the VGPR column), not to memory:
 //                          VGPRs  SGPRs (spilled)  LDS per workgroup   waves per SIMD by registers / workgroups per CU by LDS
-//   count          <0, 0>   191    106 (10)            16 384 B                 2                   /        10
-//   fill           <1, 0>   197    106 (20)            16 384 B                 2                   /        10
+//   count          <0, 0>   191    106 (12)            16 384 B                 2                   /        10
+//   fill           <1, 0>   197    106 (18)            16 384 B                 2                   /        10
 //   count, counted <0, 1>   197    106 (10)            16 384 B                 2                   /        10
-//   fill, counted  <1, 1>   203    106 (24)            16 384 B                 2                   /        10
+//   fill, counted  <1, 1>   203    106 (22)            16 384 B                 2                   /        10
 // A workgroup is four waves, one per SIMD, so "workgroups per CU" and "waves per SIMD" are the same number: the registers
 // (512 / 192 = 2) decide in every form, the 16 KB of the stack never do. Two and a half times the box kernel's registers: 42 of
 // them hold the query (what is hoisted, and a1 and a2), 30 the record, its differences about a0, its edges and nB, and the
@@ -43,265 +34,60 @@
 // compiler spill 156 to 432 bytes per lane to scratch, which this kernel must not have; hoisting less or forming B's edges
 // again per group of axes is the way to the next occupancy step (168 VGPRs for three waves) and has not been tried. Not tuned.
 
-#define TC_THREADS 256u
-#define TC_WAVES (TC_THREADS / 64u)
-#define TC_LDS_STACK 16u           // entries per lane held in LDS, 4 bytes each
-
 static_assert(RTK_TOUCH_RULE_SKIP_SHARED_VERTEX == RTK_TOUCH_SKIP_SHARED_VERTEX, "the rule header's flag is the interface's");
 static_assert(sizeof(rtk_tri_query) == 36, "a float32 [n, 9] tensor is a batch of queries");
 
 namespace {
 
-struct TouchParams {
-	const DevNode *nodes;
-	const DevTri *tris;
-	uint32_t num_nodes;
-	uint32_t num_tris;
-	const rtk_tri_query *queries;
-	const uint32_t *first_prim;        // or NULL: 0 for every query; indexed by query slot
-	const unsigned long long *ids;     // or NULL: 0, 1, 2, ...
-	const unsigned long long *count;   // or NULL: n
-	uint32_t *counts;                  // the count form: one word per query slot; the fill form: d_written or NULL
-	const unsigned long long *offsets; // the fill form: n + 1 entries
-	uint32_t *prims;                   // the fill form
-	uint32_t *claim;                   // the fill form with ids: one bit per query slot, cleared ahead of the launch; else NULL
-	unsigned long long *counter;       // the stream's counter words: [RTK_ERROR_WORD] is set by a dropped push
-	uint32_t *spill;                   // [entry][lane of the launch]
-	uint32_t spill_stride;
-	uint32_t spill_cap;                // entries per lane
-	uint32_t n;
-	uint32_t flags;                    // RTK_TOUCH_SKIP_SHARED_VERTEX
-};
-
-typedef float tc_f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t tc_u32x4 __attribute__((ext_vector_type(4)));
-
-// FILL: the list into the query's segment (else the count); COUNT: the visit counts of rtk_dev_triangles_touching_counted, summed
-// per lane and added to the stream's counter words at the end
-template <bool FILL, bool COUNT>
-__global__ void __launch_bounds__(TC_THREADS) k_touch(TouchParams p)
-{
-	__shared__ uint32_t s_stack[TC_WAVES][TC_LDS_STACK][64];
-
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	uint32_t (*stk)[64] = s_stack[wave];
-	const uint32_t glane = blockIdx.x * TC_THREADS + threadIdx.x;
-	uint32_t m = p.n;
-	if (p.count) { const unsigned long long listed = *p.count; m = listed < p.n ? (uint32_t)listed : p.n; }
-	const unsigned long long step = (unsigned long long)gridDim.x * TC_THREADS;
-	uint32_t c_queries = 0, c_nodes = 0, c_leaves = 0, c_tris = 0, c_hits = 0, c_spills = 0;
-
-	for (unsigned long long i = glane; i < m; i += step) {
-		const uint32_t r = p.ids ? (uint32_t)p.ids[i] : (uint32_t)i;
-		if (r >= p.n) continue;                                   // (the caller's error; nothing is read or written out of range)
-		if (FILL && p.claim) {
-			// a query the list names twice is answered once: two lanes must not sort into one segment
-			const uint32_t bit = 1u << (r & 31u);
-			if (atomicOr(p.claim + (r >> 5), bit) & bit) continue;
-		}
-		// (36 bytes at a stride of 36: a query is only 4-byte aligned)
-		const float *qw = reinterpret_cast<const float *>(p.queries + r);
-		const float a0[3] = { qw[0], qw[1], qw[2] }, a1[3] = { qw[3], qw[4], qw[5] }, a2[3] = { qw[6], qw[7], qw[8] };
-		const uint32_t first = p.first_prim ? p.first_prim[r] : 0u;
+struct Touch {
+	typedef rtk_tri_query Query;
+	typedef rtk_touch_filter Filter;
+	struct Extra {
+		const uint32_t *first_prim;    // or NULL: 0 for every query; indexed by query slot
+		uint32_t flags;                // RTK_TOUCH_SKIP_SHARED_VERTEX
+	};
+	struct Prepared {
 		rtk_touch_hoist q;
-		rtk_touch_hoist_query(a0, a1, a2, q);
-		uint32_t kept = 0;                                        // candidates counted, or entries of the segment in use
-		uint32_t room = 0;
-		uint32_t *seg = nullptr;
-		uint32_t worst = 0u;                                      // the segment's last entry once kept == room
-		bool walk = rtk_touch_live(a0, a1, a2) && p.num_nodes != 0u && p.num_tris != 0u;
-		if (FILL) {
-			// (offsets that decrease are the caller's error: such a query has no room, nothing is written for it)
-			const unsigned long long o0 = p.offsets[r], o1 = p.offsets[(size_t)r + 1u];
-			const unsigned long long space = o1 > o0 ? o1 - o0 : 0ull;
-			room = space < 0xffffffffull ? (uint32_t)space : 0xffffffffu;
-			seg = p.prims + o0;
-			walk = walk && room != 0u;                            // nothing can be kept: no walk
+		float a0[3], a1[3], a2[3];
+		uint32_t first, flags;
+	};
+	static constexpr int FLOATS = 9;
+	static constexpr const char *NAME_COUNT = "rtk_dev_triangles_touching_count", *NAME_ALL = "rtk_dev_triangles_touching_all",
+		*NAME_COUNTED = "rtk_dev_triangles_touching_counted", *NOUN = "triangles";
+
+	static bool extras(const Filter *filter, const char *who, Extra &x)
+	{
+		if (filter && (filter->struct_size < sizeof(rtk_touch_filter) || (filter->flags & ~(uint32_t)RTK_TOUCH_SKIP_SHARED_VERTEX) != 0u)) {
+			rtk_set_error("%s: bad filter (struct_size %u, flags %#x)", who, filter->struct_size, filter->flags);
+			return false;
 		}
-		uint32_t top = walk ? 0u : RTK_REF_NONE;
-		uint32_t sp = 0;
-		if (COUNT) c_queries++;
-
-		while (top != RTK_REF_NONE) {
-			if ((int32_t)top < 0) {
-				// ---------------------------------------------------------------- leaf: its records up to RTK_TRI_LAST
-				uint32_t slot = top & 0x7fffffffu;
-				if (COUNT) c_leaves++;
-				while (slot < p.num_tris) {
-					const tc_f32x4 *t = reinterpret_cast<const tc_f32x4 *>(reinterpret_cast<const char *>(p.tris) + (size_t)slot * RTK_TRI_STRIDE);
-					const tc_f32x4 A = t[0], B = t[1], C = t[2];
-					const float b0[3] = { A.x, A.y, A.z }, b1[3] = { B.x, B.y, B.z }, b2[3] = { C.x, C.y, C.z };
-					if (COUNT) c_tris++;
-					if (rtk_touch_candidate(q, a0, a1, a2, b0, b1, b2, __float_as_uint(A.w), first, p.flags)) {
-						if (FILL) kept = rtk_box_insert(seg, room, kept, __float_as_uint(A.w), worst);
-						else kept++;
-					}
-					if (__float_as_uint(B.w) & RTK_TRI_LAST) break;
-					slot++;
-				}
-				top = RTK_REF_NONE;
-			} else if (top < p.num_nodes) {
-				// ---------------------------------------------------------------- node: four boxes
-				const tc_f32x4 *nd = reinterpret_cast<const tc_f32x4 *>(p.nodes + top);
-				const tc_f32x4 xl = nd[0], xh = nd[1], yl = nd[2], yh = nd[3], zl = nd[4], zh = nd[5];
-				const tc_u32x4 ch = *reinterpret_cast<const tc_u32x4 *>(nd + 6);
-				uint32_t ref[4];
-				if (COUNT) c_nodes++;
-#pragma unroll
-				for (int k = 0; k < 4; k++) {
-					const float clo[3] = { xl[k], yl[k], zl[k] }, chi[3] = { xh[k], yh[k], zh[k] };
-					ref[k] = ch[k] != RTK_REF_NONE && !rtk_box_skip(clo, chi, q.lo, q.hi) ? ch[k] : RTK_REF_NONE;
-				}
-				// any order gives the same result: the first admitted slot is entered
-				top = RTK_REF_NONE;
-#pragma unroll
-				for (int k = 0; k < 4; k++) {
-					if (top == RTK_REF_NONE && ref[k] != RTK_REF_NONE) { top = ref[k]; ref[k] = RTK_REF_NONE; }
-				}
-				// the others. A push that does not fit LDS or the spill area is dropped WITHOUT advancing sp and flagged
-#pragma unroll
-				for (int k = 3; k >= 0; k--) {
-					if (ref[k] == RTK_REF_NONE) continue;
-					if (sp < TC_LDS_STACK) { stk[sp][lane] = ref[k]; sp++; }
-					else if (sp - TC_LDS_STACK < p.spill_cap) { p.spill[(size_t)(sp - TC_LDS_STACK) * p.spill_stride + glane] = ref[k]; sp++; if (COUNT) c_spills++; }
-					else p.counter[RTK_ERROR_WORD] = 1ull;
-				}
-			} else top = RTK_REF_NONE;                                // (a child word beyond the array: not a tree; nothing is read)
-			// ---------------------------------------------------------------- pop
-			if (top == RTK_REF_NONE && sp != 0u) {
-				--sp;
-				top = sp < TC_LDS_STACK ? stk[sp][lane] : p.spill[(size_t)(sp - TC_LDS_STACK) * p.spill_stride + glane];
-			}
-		}
-
-		if (COUNT && kept != 0u) c_hits++;
-		if (p.counts) __builtin_nontemporal_store(kept, p.counts + r);
+		x.first_prim = filter ? filter->d_first_prim : nullptr;
+		x.flags = filter ? filter->flags : 0u;
+		return true;
 	}
-	if (COUNT) {
-		// (the words k_closest's counting build uses)
-		atomicAdd(p.counter + 1, (unsigned long long)c_queries);
-		atomicAdd(p.counter + 2, (unsigned long long)c_nodes);
-		atomicAdd(p.counter + 3, (unsigned long long)c_leaves);
-		atomicAdd(p.counter + 4, (unsigned long long)c_tris);
-		atomicAdd(p.counter + 5, (unsigned long long)c_hits);
-		atomicAdd(p.counter + 6, (unsigned long long)c_spills);
+	static __device__ __forceinline__ bool prepare(const float *w, const Extra &x, uint32_t r, Prepared &Q)
+	{
+		for (int a = 0; a < 3; a++) { Q.a0[a] = w[a]; Q.a1[a] = w[3 + a]; Q.a2[a] = w[6 + a]; }
+		Q.first = x.first_prim ? x.first_prim[r] : 0u;
+		Q.flags = x.flags;
+		rtk_touch_hoist_query(Q.a0, Q.a1, Q.a2, Q.q);
+		return rtk_touch_live(Q.a0, Q.a1, Q.a2);
 	}
-}
-
-typedef void (*touch_kernel_fn)(TouchParams);
-
-// form: fill | counted << 1
-touch_kernel_fn touch_form(int form)
-{
-	switch (form & 3) {
-	case 0: return k_touch<false, false>;
-	case 1: return k_touch<true, false>;
-	case 2: return k_touch<false, true>;
-	default: return k_touch<true, true>;
+	static __device__ __forceinline__ bool skip(const Prepared &Q, const float *clo, const float *chi) { return rtk_box_skip(clo, chi, Q.q.lo, Q.q.hi); }
+	static __device__ __forceinline__ bool candidate(const Prepared Q, const float *b0, const float *b1, const float *b2, uint32_t prim)
+	{
+		return rtk_touch_candidate(Q.q, Q.a0, Q.a1, Q.a2, b0, b1, b2, prim, Q.first, Q.flags);
 	}
-}
-
-// workgroups of a form a CU holds, asked once per device
-int touch_blocks_per_cu(int device, int form)
-{
-	static std::atomic<int> known[RTK_MAX_DEVICES][4];
-	if (device < 0 || device >= RTK_MAX_DEVICES) return 4;
-	int b = known[device][form & 3].load(std::memory_order_relaxed);
-	if (b == 0) {
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, touch_form(form), (int)TC_THREADS, 0) != hipSuccess || b < 1) b = 4;
-		known[device][form & 3].store(b, std::memory_order_relaxed);
-	}
-	return b;
-}
+};
 
 } // namespace
 
-extern "C" uint32_t rtk_amd_touch_stack_entries(void) { return TC_LDS_STACK; }
+extern "C" uint32_t rtk_amd_touch_stack_entries(void) { return OVERLAP_LDS_STACK; }
 
 // d_offsets == NULL: the count form (d_counts the counts); else the fill form (d_counts the written numbers, or NULL)
-int rtk_launch_touch(const rtk_dev_scene *ds_c, const rtk_tri_query *d_tris, size_t num_queries, const rtk_ray_list *list,
+int rtk_launch_touch(const rtk_dev_scene *ds, const rtk_tri_query *d_tris, size_t num_queries, const rtk_ray_list *list,
 	const rtk_touch_filter *filter, uint32_t *d_counts, const uint64_t *d_offsets, uint32_t *d_prims, bool fill, hipStream_t stream,
 	rtk_trace_counters *counted)
 {
-	rtk_dev_scene *ds = const_cast<rtk_dev_scene *>(ds_c);
-	const char *const who = counted ? "rtk_dev_triangles_touching_counted" : fill ? "rtk_dev_triangles_touching_all" : "rtk_dev_triangles_touching_count";
-	// everything the host can see is refused here, before any HIP call
-	if (!ds) { rtk_set_error("%s: NULL scene", who); return RTK_AMD_ERR_BAD_ARG; }
-	if (num_queries && (!d_tris || (fill ? (!d_offsets || !d_prims) : !d_counts))) {
-		rtk_set_error("%s: NULL triangles, %s", who, fill ? "offsets or prims" : "counts");
-		return RTK_AMD_ERR_BAD_ARG;
-	}
-	if (list && (list->struct_size < sizeof(rtk_ray_list) || list->flags != 0u || !list->d_count)) {
-		rtk_set_error("%s: bad list (struct_size %u, flags %#x, d_count %p)", who, list->struct_size, list->flags, (const void *)list->d_count);
-		return RTK_AMD_ERR_BAD_ARG;
-	}
-	if (filter && (filter->struct_size < sizeof(rtk_touch_filter) || (filter->flags & ~(uint32_t)RTK_TOUCH_SKIP_SHARED_VERTEX) != 0u)) {
-		rtk_set_error("%s: bad filter (struct_size %u, flags %#x)", who, filter->struct_size, filter->flags);
-		return RTK_AMD_ERR_BAD_ARG;
-	}
-	if (num_queries >= ((size_t)1 << 32)) { rtk_set_error("%s: %zu queries: a batch holds fewer than 2^32", who, num_queries); return RTK_AMD_ERR_BAD_ARG; }
-	if (counted) *counted = rtk_trace_counters();
-	if (num_queries == 0) return RTK_AMD_OK;
-	if (!rtk_on_scene_device(ds, who)) return RTK_AMD_ERR_BAD_ARG;
-
-	TouchParams p = {};
-	p.queries = d_tris;
-	p.first_prim = filter ? filter->d_first_prim : nullptr;
-	p.flags = filter ? filter->flags : 0u;
-	p.ids = list ? reinterpret_cast<const unsigned long long *>(list->d_ids) : nullptr;
-	p.count = list ? reinterpret_cast<const unsigned long long *>(list->d_count) : nullptr;
-	p.counts = d_counts;
-	p.offsets = reinterpret_cast<const unsigned long long *>(d_offsets);
-	p.prims = d_prims;
-	p.n = (uint32_t)num_queries;
-	const int form = (fill ? 1 : 0) | (counted ? 2 : 0);
-	const size_t blocks_needed = (num_queries + TC_THREADS - 1u) / TC_THREADS;
-	size_t grid = (size_t)(ds->num_cus > 0 ? ds->num_cus : 1) * (size_t)touch_blocks_per_cu(ds->device, form);
-	if (grid > blocks_needed) grid = blocks_needed;
-
-	// the scratch set of (scene, stream), held until the launch is enqueued; the view and the tree record are read under the
-	// same lock a rebuild replaces them under (rtk_launch_box does the same)
-	std::lock_guard<std::mutex> lock(ds->scratch_mutex);
-	p.nodes = ds->view.nodes; p.tris = ds->view.tris; p.num_nodes = ds->view.num_nodes; p.num_tris = ds->view.num_tris;
-	const size_t entries = ds->tree.stack_entries();
-	const size_t spill_cap = entries > TC_LDS_STACK ? entries - TC_LDS_STACK : 0;
-	LaunchScratch *sc = ds->scratch.get(stream);
-	if (!sc) return RTK_AMD_ERR_OOM;
-	if (spill_cap) {
-		// (sized in 8-byte entries although these are 4: the area is shared with the other walks of the stream, which hold such entries)
-		const int rc = sc->grow_spill(grid * TC_THREADS, spill_cap, sizeof(uint2));
-		if (rc != RTK_AMD_OK) return rc;
-	}
-	p.spill = sc->spill.as<uint32_t>();
-	p.spill_stride = (uint32_t)(spill_cap ? sc->spill.capacity : 0);
-	p.spill_cap = (uint32_t)spill_cap;
-	p.counter = sc->d_counter;
-	if (fill && p.ids) {
-		// one bit per query slot, in the area rtk_dev_select_rays keeps its masks in: launches of one stream are ordered
-		const size_t claim_bytes = ((num_queries + 31u) / 32u) * sizeof(uint32_t);
-		const int rc = sc->grow(sc->select, claim_bytes, claim_bytes);
-		if (rc != RTK_AMD_OK) return rc;
-		p.claim = sc->select.as<uint32_t>();
-		RTK_HIP_CHECK(hipMemsetAsync(p.claim, 0, claim_bytes, stream), RTK_AMD_ERR_HIP);
-	}
-	if (!counted) {
-		hipLaunchKernelGGL(touch_form(form), dim3((unsigned)grid), dim3(TC_THREADS), 0, stream, p);
-		RTK_HIP_CHECK(hipGetLastError(), RTK_AMD_ERR_HIP);
-		return RTK_AMD_OK;
-	}
-	// the counting form: the visit counters start from zero, are brought home and the stream is waited for
-	unsigned long long c[8], err = 0;
-	RTK_HIP_CHECK(hipMemsetAsync(sc->d_counter, 0, RTK_COUNTER_WORDS * sizeof(unsigned long long), stream), RTK_AMD_ERR_HIP);
-	hipLaunchKernelGGL(touch_form(form), dim3((unsigned)grid), dim3(TC_THREADS), 0, stream, p);
-	RTK_HIP_CHECK(hipGetLastError(), RTK_AMD_ERR_HIP);
-	RTK_HIP_CHECK(hipMemcpyAsync(c, sc->d_counter, sizeof(c), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
-	RTK_HIP_CHECK(hipMemcpyAsync(&err, sc->d_counter + RTK_ERROR_WORD, sizeof(err), hipMemcpyDeviceToHost, stream), RTK_AMD_ERR_HIP);
-	RTK_HIP_CHECK(hipStreamSynchronize(stream), RTK_AMD_ERR_HIP);
-	counted->rays = c[1]; counted->nodes = c[2]; counted->leaves = c[3]; counted->triangles = c[4]; counted->hits = c[5]; counted->stack_spills = c[6];
-	if (err) {
-		(void)hipMemsetAsync(sc->d_counter + RTK_ERROR_WORD, 0, sizeof(err), stream);
-		rtk_set_error("%s: traversal stack overflow (corrupted scene)", who);
-		return RTK_AMD_ERR_BAD_SCENE;
-	}
-	return RTK_AMD_OK;
+	return rtk_launch_overlap_walk<Touch>(ds, d_tris, num_queries, list, filter, d_counts, d_offsets, d_prims, fill, stream, counted);
 }

@@ -343,9 +343,12 @@ def test_rule_header_includes_no_hip_and_states_its_rules():
                  "rtk_dev_trace_status", "rtk_mgpu_scene(m, i)", "CANNOT BE CULLED BY WHAT IT HAS KEPT", "ASCENDING PRIMITIVE ID", "touching counts"):
         assert word in section, word
     mk = open(os.path.join(ROOT, "rtk_amd", "csrc", "Makefile")).read()
-    assert "rtk_box_rule.h" in mk and "rtk_box.hip" in mk
+    assert "rtk_box_rule.h" in mk and "rtk_box.hip" in mk and "rtk_overlap_walk.h" in mk
+    # the shape's own calls in its file, what the three overlap shapes share in the walk
     kernel = open(os.path.join(ROOT, "rtk_amd", "csrc", "rtk_box.hip")).read()
-    assert "rtk_box_insert(" in kernel and "rtk_box_skip(" in kernel and "rtk_box_candidate(" in kernel and "rtk_box_live(" in kernel
+    walk = open(os.path.join(ROOT, "rtk_amd", "csrc", "rtk_overlap_walk.h")).read()
+    assert "rtk_box_insert(" in walk and "rtk_box_skip(" in kernel and "rtk_box_candidate(" in kernel and "rtk_box_live(" in kernel
+    assert "rtk_box_boxes_touch(" in kernel and "rtk_box_separated(" in kernel         # (rtk_box_candidate's one line, spelled out there)
     assert "kernel-resource-usage" in kernel and "scratch 0" in kernel
 
 

@@ -229,6 +229,17 @@ def test_at_most_k(api, base, k):
     assert_fill(run_fill(api, base.ds, base.q, offsets, n * k, with_written=False), expected_fill(cut(base.ref.lists, k), offsets, n * k), "k = %d, no written" % k)
 
 
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 4097])
+def test_sizes(api, base, n):
+    which = (np.arange(n) * 7) % base.n                              # (a stride: every part of the mix at every size)
+    q = base.q[which]
+    got = run_count(api, base.ds, q, n=n)
+    assert got[:n].tobytes() == base.ref.counts[which].tobytes()
+    offsets = np.arange(n + 1, dtype=np.int64) * 3
+    kept = cut([base.ref.lists[i] for i in which], 3)
+    assert_fill(run_fill(api, base.ds, q, offsets, n * 3, n=n), expected_fill(kept, offsets, n * 3), "n = %d" % n)
+
+
 def test_ragged_room(api, base):
     """Room 0 .. 6 per query, and one pair of decreasing offsets: the kept prefix, nothing for the query without room"""
     rng = np.random.RandomState(9)

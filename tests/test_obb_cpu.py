@@ -406,9 +406,11 @@ def test_rule_header_includes_no_hip_and_states_its_rules():
                  "rtk_dev_trace_status", "rtk_mgpu_scene(m, i)", "CANNOT BE CULLED BY WHAT IT HAS KEPT", "ASCENDING PRIMITIVE ID", "touching counts", "2^-10"):
         assert word in section, word
     mk = open(os.path.join(ROOT, "rtk_amd", "csrc", "Makefile")).read()
-    assert "rtk_obb_rule.h" in mk and "rtk_obb.hip" in mk
+    assert "rtk_obb_rule.h" in mk and "rtk_obb.hip" in mk and "rtk_overlap_walk.h" in mk
+    # the shape's own calls in its file, what the three overlap shapes share in the walk
     kernel = open(os.path.join(ROOT, "rtk_amd", "csrc", "rtk_obb.hip")).read()
-    assert "rtk_box_insert(" in kernel and "rtk_obb_skip(" in kernel and "rtk_obb_candidate(" in kernel and "rtk_obb_prepare(" in kernel
+    walk = open(os.path.join(ROOT, "rtk_amd", "csrc", "rtk_overlap_walk.h")).read()
+    assert "rtk_box_insert(" in walk and "rtk_obb_skip(" in kernel and "rtk_obb_candidate(" in kernel and "rtk_obb_prepare(" in kernel
     assert "kernel-resource-usage" in kernel and "scratch 0" in kernel and "OB_RESOURCES" in kernel
     layout = open(os.path.join(ROOT, "rtk_amd", "csrc", "rtk_layout_check.h")).read()
     assert "static_assert(sizeof(rtk_obb_query) == 60" in layout

@@ -474,10 +474,12 @@ def test_rule_header_includes_no_hip_and_states_its_rules():
                  "SEVENTEEN AXES", "indexed by query slot", "RTK_TOUCH_SKIP_SHARED_VERTEX", "unknown bit"):
         assert word in section, word
     mk = open(os.path.join(ROOT, "rtk_amd", "csrc", "Makefile")).read()
-    assert "rtk_touch_rule.h" in mk and "rtk_touch.hip" in mk
+    assert "rtk_touch_rule.h" in mk and "rtk_touch.hip" in mk and "rtk_overlap_walk.h" in mk
+    # the shape's own calls in its file, what the three overlap shapes share in the walk
     kernel = open(os.path.join(ROOT, "rtk_amd", "csrc", "rtk_touch.hip")).read()
-    assert "rtk_box_insert(" in kernel and "rtk_box_skip(" in kernel and "rtk_touch_candidate(" in kernel and "rtk_touch_live(" in kernel
-    assert "kernel-resource-usage" in kernel and "scratch 0" in kernel and "LaunchScratch" in kernel
+    walk = open(os.path.join(ROOT, "rtk_amd", "csrc", "rtk_overlap_walk.h")).read()
+    assert "rtk_box_insert(" in walk and "rtk_box_skip(" in kernel and "rtk_touch_candidate(" in kernel and "rtk_touch_live(" in kernel
+    assert "kernel-resource-usage" in kernel and "scratch 0" in kernel and "LaunchScratch" in walk
 
 
 def test_header_symbols_and_argtypes(api):
