@@ -1330,8 +1330,9 @@ uint32_t rtk_amd_allhits_stack_entries(void);
  * placed meshes into such a set, so memory and build time grow with instances x triangles and moving one body refits that
  * body's triangles. A rtk_dev_world is the second level: a small TOP TREE over the world boxes of INSTANCES, each a
  * (scene, rtk_placement) pair; a scene is held once however often it is placed, and moving an instance costs a 64-byte
- * record and a refit of the top tree. A world answers rays (closest hit and any hit) and closest points
- * (rtk_dev_world_closest_points, below); signed distance, within, overlaps, pairs and sweeps still take one rtk_dev_scene.
+ * record and a refit of the top tree. A world answers rays (closest hit and any hit), closest points
+ * (rtk_dev_world_closest_points, below) and the three overlap queries (rtk_dev_world_triangles_in_box_* / _in_obb_* /
+ * _touching_*, below); signed distance, winding, within, pairs and sweeps still take one rtk_dev_scene.
  *
  * THE OBJECT. rtk_dev_world_create(scenes, num_scenes, instance_scene, placements, num_instances): instance i places scene
  * scenes[instance_scene[i]] by placements[i] (host memory, both arrays; the rule of rtk_dev_scene_build_placed maps the
@@ -1431,6 +1432,60 @@ int rtk_dev_world_closest_points_counted(const rtk_dev_world *w, const rtk_point
 	const rtk_world_filter *filter, rtk_closest_record *d_records, uint32_t *d_instances, float *d_points, rtk_trace_counters *out);
 /* (8-byte stack entries per lane the walk keeps on chip before it uses the spill area, for tests) */
 uint32_t rtk_amd_world_closest_stack_entries(void);
+
+/* OVERLAPS ON A WORLD: which triangles of which instances touch this box, this oriented box, this triangle -- the broad and
+ * narrow phase of collision without flattening the world. rtk_dev_world_triangles_in_box_*, _in_obb_* and _touching_* are
+ * rtk_dev_triangles_in_box_*, _in_obb_* and _touching_* asked of a world, with the world's filter in place of the scene's.
+ * The rule (rtk_amd/csrc/rtk_world_overlap_rule.h): a record's vertices are placed by the instance's FORWARD placement with the
+ * rule of rtk_dev_scene_build_placed, then the shape's own candidate rule (rtk_box_rule.h, rtk_obb_rule.h, rtk_touch_rule.h)
+ * answers on the placed vertices, unchanged. THE CANDIDATES ARE THOSE THE SCENE CALL GIVES ON THE FLAT PLACED TWIN
+ * (rtk_dev_scene_build_placed of the same meshes under the same placements), for any affine placement with finite placed
+ * vertices: no condition number, no margin -- a scene's node box is placed exactly and all three skips are comparisons
+ * (DESIGN.md 3.23.2). A query's liveness is the shape's own; a dead instance is never answered. The result depends on
+ * neither tree nor on the order of the walk.
+ * AN ENTRY is one uint64_t: ((uint64_t)instance << 32) | prim, prim the GLOBAL PRIMITIVE ID IN THE INSTANCE'S SCENE as for
+ * rtk_dev_world_trace_rays. A query's list is its candidates in ASCENDING ENTRY, that is by instance, then by primitive id;
+ * a torch int64 tensor is an entry buffer as it stands (instance = e >> 32, prim = e & 0xffffffff).
+ * _count: d_counts[i] = the number of candidates of query i over all live instances the filter lets through, written for
+ * EVERY answered query (0 for a query that is not live). _all: query i owns d_entries[d_offsets[i] .. d_offsets[i + 1]);
+ * d_offsets has num_queries + 1 entries and is indexed by query slot; the segment receives the first
+ * min(count, d_offsets[i + 1] - d_offsets[i]) entries of the list, d_written[i] (d_written may be NULL) that number; ENTRIES
+ * BEYOND IT AND OUTSIDE EVERY SEGMENT ARE NOT WRITTEN. Offsets that decrease mean no room: nothing is written into such a
+ * segment and d_written[i] = 0. d_offsets[i] = i * k with no count pass gives the k lowest entries of every query. `list` as
+ * for the scene calls: A SLOT THAT IS NOT LISTED IS NOT WRITTEN, an id >= num_queries is skipped, an id that repeats is
+ * answered once. rtk_world_filter as for rays and closest points; d_ignore_instance is read at the query's slot (the body a
+ * query shape belongs to: there is no d_first_prim on a world). touch_flags: RTK_TOUCH_SKIP_SHARED_VERTEX or 0 -- a record
+ * whose PLACED vertices share a position with the query's is left out, which is what the flat twin compares; any other bit is
+ * refused.
+ * Asynchronous on `stream`, nothing is read back; the scratch set and the launch-error word are the top tree's for that stream
+ * (rtk_dev_world_trace_status). A scene that changed must be followed by rtk_dev_world_update first, as for rays.
+ * _counted: the count form (d_offsets == NULL) or the fill form with visit counts (nodes and leaves of both levels together,
+ * triangles = proxies and triangle records, hits = queries with a candidate, stack_spills); on the null stream, synchronises.
+ * Refusals before any HIP call (RTK_AMD_ERR_BAD_ARG, the function's name in the text) are those of rtk_dev_world_trace_rays --
+ * a NULL world, NULL queries or outputs with num_queries != 0, a bad list, a bad filter, num_queries >= 2^32 -- and an unknown
+ * bit of touch_flags; num_queries == 0 is RTK_AMD_OK with nothing launched. */
+int rtk_dev_world_triangles_in_box_count(const rtk_dev_world *w, const rtk_box_query *d_boxes, size_t num_queries,
+	const rtk_ray_list *list, const rtk_world_filter *filter, uint32_t *d_counts, void *stream);
+int rtk_dev_world_triangles_in_box_all(const rtk_dev_world *w, const rtk_box_query *d_boxes, size_t num_queries,
+	const rtk_ray_list *list, const rtk_world_filter *filter, const uint64_t *d_offsets, uint64_t *d_entries, uint32_t *d_written /* may be NULL */, void *stream);
+int rtk_dev_world_triangles_in_box_counted(const rtk_dev_world *w, const rtk_box_query *d_boxes, size_t num_queries,
+	const rtk_world_filter *filter, const uint64_t *d_offsets, uint64_t *d_entries, uint32_t *d_counts_or_written, rtk_trace_counters *out);
+int rtk_dev_world_triangles_in_obb_count(const rtk_dev_world *w, const rtk_obb_query *d_obbs, size_t num_queries,
+	const rtk_ray_list *list, const rtk_world_filter *filter, uint32_t *d_counts, void *stream);
+int rtk_dev_world_triangles_in_obb_all(const rtk_dev_world *w, const rtk_obb_query *d_obbs, size_t num_queries,
+	const rtk_ray_list *list, const rtk_world_filter *filter, const uint64_t *d_offsets, uint64_t *d_entries, uint32_t *d_written /* may be NULL */, void *stream);
+int rtk_dev_world_triangles_in_obb_counted(const rtk_dev_world *w, const rtk_obb_query *d_obbs, size_t num_queries,
+	const rtk_world_filter *filter, const uint64_t *d_offsets, uint64_t *d_entries, uint32_t *d_counts_or_written, rtk_trace_counters *out);
+int rtk_dev_world_triangles_touching_count(const rtk_dev_world *w, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_ray_list *list, const rtk_world_filter *filter, uint32_t touch_flags, uint32_t *d_counts, void *stream);
+int rtk_dev_world_triangles_touching_all(const rtk_dev_world *w, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_ray_list *list, const rtk_world_filter *filter, uint32_t touch_flags, const uint64_t *d_offsets, uint64_t *d_entries,
+	uint32_t *d_written /* may be NULL */, void *stream);
+int rtk_dev_world_triangles_touching_counted(const rtk_dev_world *w, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_world_filter *filter, uint32_t touch_flags, const uint64_t *d_offsets, uint64_t *d_entries, uint32_t *d_counts_or_written,
+	rtk_trace_counters *out);
+/* (8-byte stack entries per lane the walk keeps on chip before it uses the spill area, for tests) */
+uint32_t rtk_amd_world_overlap_stack_entries(void);
 
 /* Waits for `stream` and reports whether a launch of this scene on it overflowed a traversal stack
  * (RTK_AMD_ERR_BAD_SCENE; impossible for a validated tree -- the push is dropped, never written out of bounds). */

@@ -13,7 +13,7 @@ import os
 
 import numpy as np
 
-from .types import (BOX_QUERY_DTYPE, BOX_SWEEP_DTYPE, CAPSULE_SWEEP_DTYPE, CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, OBB_QUERY_DTYPE, OBB_SWEEP_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, SPHERE_SWEEP_DTYPE, TRI_QUERY_DTYPE, MeshSet, Placement, SceneDesc, SceneHeader,
+from .types import (BOX_QUERY_DTYPE, BOX_SWEEP_DTYPE, CAPSULE_SWEEP_DTYPE, CLOSEST_RECORD_DTYPE, HIT_DTYPE, HIT_RECORD_DTYPE, OBB_QUERY_DTYPE, OBB_SWEEP_DTYPE, POINT_QUERY_DTYPE, RAY_DTYPE, RTK_INF, SPHERE_SWEEP_DTYPE, TRI_QUERY_DTYPE, WORLD_ENTRY_DTYPE, MeshSet, Placement, SceneDesc, SceneHeader,
                     placement_array)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -235,6 +235,10 @@ RTK_AMD_H_SYMBOLS = ["rtk_amd_last_error", "rtk_amd_device_count", "rtk_amd_set_
                      "rtk_dev_world_top_scene", "rtk_dev_world_trace_status", "rtk_dev_world_trace_rays", "rtk_dev_world_trace_rays_any",
                      "rtk_dev_world_trace_rays_counted", "rtk_amd_world_stack_entries",
                      "rtk_dev_world_closest_points", "rtk_dev_world_closest_points_counted", "rtk_amd_world_closest_stack_entries",
+                     "rtk_dev_world_triangles_in_box_count", "rtk_dev_world_triangles_in_box_all", "rtk_dev_world_triangles_in_box_counted",
+                     "rtk_dev_world_triangles_in_obb_count", "rtk_dev_world_triangles_in_obb_all", "rtk_dev_world_triangles_in_obb_counted",
+                     "rtk_dev_world_triangles_touching_count", "rtk_dev_world_triangles_touching_all",
+                     "rtk_dev_world_triangles_touching_counted", "rtk_amd_world_overlap_stack_entries",
                      "rtk_dev_trace_rays_count", "rtk_dev_trace_rays_all", "rtk_amd_allhits_stack_entries",
                      "rtk_dev_triangles_within_count", "rtk_dev_triangles_within_all", "rtk_dev_triangles_within_counted",
                      "rtk_amd_within_stack_entries",
@@ -269,6 +273,14 @@ OVERLAPS = {f.name: f for f in (
     Overlap("in_boxes", "rtk_dev_triangles_in_box", "rtk_amd_box_stack_entries", False),
     Overlap("in_obbs", "rtk_dev_triangles_in_obb", "rtk_amd_obb_stack_entries", False),
     Overlap("touching", "rtk_dev_triangles_touching", "rtk_amd_touch_stack_entries", True))}
+
+# ... and on a world (rtk_amd/csrc/rtk_world_overlap.hip): the name in DeviceWorld's methods (triangles_<name>_count_device, ...),
+# the C symbol stem, the width of a query in floats, whether the calls take touch_flags after the world's filter
+WorldOverlap = collections.namedtuple("WorldOverlap", "name stem floats flagged")
+WORLD_OVERLAPS = {f.name: f for f in (
+    WorldOverlap("in_box", "rtk_dev_world_triangles_in_box", 6, False),
+    WorldOverlap("in_obb", "rtk_dev_world_triangles_in_obb", 15, False),
+    WorldOverlap("touching", "rtk_dev_world_triangles_touching", 9, True))}
 
 _lib = None
 
@@ -381,6 +393,15 @@ def lib():
     L.rtk_dev_world_closest_points_counted.restype = C.c_int
     L.rtk_amd_world_closest_stack_entries.argtypes = []
     L.rtk_amd_world_closest_stack_entries.restype = C.c_uint32
+    for fam in WORLD_OVERLAPS.values():
+        fn_count, fn_all, fn_counted = (getattr(L, fam.stem + tail) for tail in ("_count", "_all", "_counted"))
+        flags = [C.c_uint32] if fam.flagged else []
+        fn_count.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(WorldFilter)] + flags + [C.c_void_p, C.c_void_p]
+        fn_all.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.POINTER(WorldFilter)] + flags + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        fn_counted.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(WorldFilter)] + flags + [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TraceCounters)]
+        fn_count.restype = fn_all.restype = fn_counted.restype = C.c_int
+    L.rtk_amd_world_overlap_stack_entries.argtypes = []
+    L.rtk_amd_world_overlap_stack_entries.restype = C.c_uint32
     for fam in SWEEPS.values():
         fn, fn_any, fn_counted, entries = (getattr(L, name) for name in (fam.stem, fam.stem + "_any", fam.stem + "_counted", fam.stack_entries))
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RayList), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DevFilter), C.c_void_p]
@@ -2100,7 +2121,7 @@ class DeviceScene:
 
 class DeviceWorld:
     """An instanced world (rtk_dev_world*; include/rtk_amd.h, "Instanced worlds"): placed copies of device scenes under a small
-    top tree, for rays and closest points. The object keeps its scenes alive; a scene that was refitted, split or rebuilt must be followed by
+    top tree, for rays, closest points and the three overlap queries. The object keeps its scenes alive; a scene that was refitted, split or rebuilt must be followed by
     update() before the next trace."""
 
     def __init__(self, handle, scenes):
@@ -2327,6 +2348,144 @@ class DeviceWorld:
         self.status()
         return (d_rec.cpu().numpy().view(CLOSEST_RECORD_DTYPE), d_inst.cpu().numpy().view(np.uint32),
                 d_pts.cpu().numpy().view(np.float32).reshape(n, 3))
+
+
+    # -- the three overlap queries on the world (rtk_dev_world_triangles_in_box_* / _in_obb_* / _touching_*; a row of
+    # WORLD_OVERLAPS each): asynchronous on the current stream. An entry is instance << 32 | prim: an int64 tensor holds them --
+
+    def _overlap_count_device(self, fam, d_q, n, d_counts, count, ids, instance_mask, ignore_instance, skip_shared=False):
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        if ids is not None and count is None:
+            raise RtkError("DeviceWorld.triangles_%s_count_device: ids without count (a list's length lives on the device)" % fam.name)
+        l = make_ray_list(count, ids) if count is not None else None
+        f, _keep = self._filter(instance_mask, ignore_instance)
+        flags = (TOUCH_SKIP_SHARED_VERTEX if skip_shared else 0,) if fam.flagged else ()
+        _check(getattr(lib(), fam.stem + "_count")(self.handle, C.c_void_p(d_q.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                   C.byref(f) if f is not None else None, *flags, C.c_void_p(d_counts.data_ptr()), _stream_ptr()),
+               fam.stem + "_count")
+        self._keep = _keep
+        return d_counts
+
+    def _overlap_all_device(self, fam, d_q, n, d_offsets, d_entries, d_written, count, ids, instance_mask, ignore_instance, skip_shared=False):
+        if ids is not None and count is None:
+            raise RtkError("DeviceWorld.triangles_%s_all_device: ids without count (a list's length lives on the device)" % fam.name)
+        l = make_ray_list(count, ids) if count is not None else None
+        f, _keep = self._filter(instance_mask, ignore_instance)
+        flags = (TOUCH_SKIP_SHARED_VERTEX if skip_shared else 0,) if fam.flagged else ()
+        _check(getattr(lib(), fam.stem + "_all")(self.handle, C.c_void_p(d_q.data_ptr()), n, C.byref(l) if l is not None else None,
+                                                 C.byref(f) if f is not None else None, *flags, C.c_void_p(d_offsets.data_ptr()),
+                                                 C.c_void_p(d_entries.data_ptr()), C.c_void_p(d_written.data_ptr()) if d_written is not None else None,
+                                                 _stream_ptr()), fam.stem + "_all")
+        self._keep = _keep
+        return d_written
+
+    def _overlap_counted(self, fam, d_q, n, d_offsets, d_entries, d_counts, instance_mask, ignore_instance, skip_shared=False):
+        torch = _torch()
+        if d_counts is None:
+            d_counts = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+        ctr = TraceCounters()
+        f, _keep = self._filter(instance_mask, ignore_instance)
+        flags = (TOUCH_SKIP_SHARED_VERTEX if skip_shared else 0,) if fam.flagged else ()
+        torch.cuda.synchronize()
+        _check(getattr(lib(), fam.stem + "_counted")(self.handle, C.c_void_p(d_q.data_ptr()), n, C.byref(f) if f is not None else None, *flags,
+                                                     C.c_void_p(d_offsets.data_ptr()) if d_offsets is not None else None,
+                                                     C.c_void_p(d_entries.data_ptr()) if d_entries is not None else None,
+                                                     C.c_void_p(d_counts.data_ptr()), C.byref(ctr)), fam.stem + "_counted")
+        return d_counts, ctr.as_dict()
+
+    def _overlap_host(self, fam, q, instance_mask, ignore_instance, skip_shared=False):
+        """count, prefix sum and fill of host records q [n, fam.floats] float32 -> (counts uint32 [n], instances uint32 [total],
+        prims uint32 [total]): query i's candidates are the entries sum(counts[:i]) .. + counts[i], by instance, then by primitive id"""
+        torch = _torch()
+        n = q.shape[0]
+        if n == 0:
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+        d_q = to_device(q)
+        if ignore_instance is not None and not hasattr(ignore_instance, "data_ptr"):
+            ignore_instance = torch.from_numpy(np.ascontiguousarray(ignore_instance, np.uint32).view(np.int32)).cuda()
+        d_counts = self._overlap_count_device(fam, d_q, n, None, None, None, instance_mask, ignore_instance, skip_shared)
+        d_offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+        d_offsets[1:] = torch.cumsum(d_counts, 0, dtype=torch.int64)
+        total = int(d_offsets[n].item())                     # (the one read-back: how many entries to allocate)
+        d_entries = torch.zeros(max(total, 1), dtype=torch.int64, device="cuda")
+        self._overlap_all_device(fam, d_q, n, d_offsets, d_entries, None, None, None, instance_mask, ignore_instance, skip_shared)
+        self.status()
+        e = d_entries.cpu().numpy()[:total].view(WORLD_ENTRY_DTYPE)
+        return d_counts.cpu().numpy().view(np.uint32), e["instance"].copy(), e["prim"].copy()
+
+    def triangles_in_box_count_device(self, d_boxes, n, d_counts=None, count=None, ids=None, instance_mask=None, ignore_instance=None):
+        """The number of triangles over all instances that touch each of n boxes (BOX_QUERY_DTYPE bytes on the device, or a float32
+        [n, 6] cuda tensor of lo, hi; include/rtk_amd.h, "OVERLAPS ON A WORLD"): a cuda tensor of n uint32 words (d_counts: any cuda
+        tensor of at least 4 n bytes; None: a new int32 tensor). count / ids: cuda int64 tensors naming the queries to answer;
+        slots that are not listed are not written. instance_mask / ignore_instance as for closest_points_device; ignore_instance
+        is read at the query's slot. Nothing waits for the stream."""
+        return self._overlap_count_device(WORLD_OVERLAPS["in_box"], d_boxes, n, d_counts, count, ids, instance_mask, ignore_instance)
+
+    def triangles_in_box_all_device(self, d_boxes, n, d_offsets, d_entries, d_written=None, count=None, ids=None, instance_mask=None,
+                                    ignore_instance=None):
+        """Box i's candidates as entries instance << 32 | prim (prim: the primitive id in the instance's scene), ascending, into
+        d_entries[d_offsets[i] .. d_offsets[i + 1]): as many as the box has or the segment holds, the lowest first. d_offsets,
+        d_entries: cuda int64 tensors (n + 1 offsets). d_written: a cuda tensor of 4 n bytes, or None (the call gets NULL).
+        Entries beyond written[i], and outside every segment, are not written. The rest as for triangles_in_box_count_device."""
+        return self._overlap_all_device(WORLD_OVERLAPS["in_box"], d_boxes, n, d_offsets, d_entries, d_written, count, ids, instance_mask, ignore_instance)
+
+    def triangles_in_box_counted(self, d_boxes, n, d_offsets=None, d_entries=None, d_counts=None, instance_mask=None, ignore_instance=None):
+        """The count form (d_offsets None) or the fill form of all n boxes on the null stream, synchronous, with the visit counts of
+        rtk_dev_world_triangles_in_box_counted: returns (d_counts -- the counts, or the written numbers --, counts dict)."""
+        return self._overlap_counted(WORLD_OVERLAPS["in_box"], d_boxes, n, d_offsets, d_entries, d_counts, instance_mask, ignore_instance)
+
+    def triangles_in_box(self, boxes, instance_mask=None, ignore_instance=None):
+        """boxes: array-like (n, 6) float32 of lo, hi, or BOX_QUERY_DTYPE records. A count, its prefix sum on the device and the
+        fill; returns (counts uint32 [n], instances uint32 [total], prims uint32 [total]): box i's candidates are the entries
+        sum(counts[:i]) .. + counts[i], by instance, then by primitive id. Waits for the stream."""
+        boxes = np.asarray(boxes)
+        q = np.ascontiguousarray(boxes.view(np.float32) if boxes.dtype == BOX_QUERY_DTYPE else np.asarray(boxes, np.float32)).reshape(-1, 6)
+        return self._overlap_host(WORLD_OVERLAPS["in_box"], q, instance_mask, ignore_instance)
+
+    def triangles_in_obb_count_device(self, d_obbs, n, d_counts=None, count=None, ids=None, instance_mask=None, ignore_instance=None):
+        """triangles_in_box_count_device for n oriented boxes (OBB_QUERY_DTYPE bytes on the device, or a float32 [n, 15] cuda tensor
+        of centre, half, axes)."""
+        return self._overlap_count_device(WORLD_OVERLAPS["in_obb"], d_obbs, n, d_counts, count, ids, instance_mask, ignore_instance)
+
+    def triangles_in_obb_all_device(self, d_obbs, n, d_offsets, d_entries, d_written=None, count=None, ids=None, instance_mask=None,
+                                    ignore_instance=None):
+        """triangles_in_box_all_device for n oriented boxes."""
+        return self._overlap_all_device(WORLD_OVERLAPS["in_obb"], d_obbs, n, d_offsets, d_entries, d_written, count, ids, instance_mask, ignore_instance)
+
+    def triangles_in_obb_counted(self, d_obbs, n, d_offsets=None, d_entries=None, d_counts=None, instance_mask=None, ignore_instance=None):
+        """triangles_in_box_counted for n oriented boxes (rtk_dev_world_triangles_in_obb_counted)."""
+        return self._overlap_counted(WORLD_OVERLAPS["in_obb"], d_obbs, n, d_offsets, d_entries, d_counts, instance_mask, ignore_instance)
+
+    def triangles_in_obb(self, centres, half, rotation, instance_mask=None, ignore_instance=None):
+        """centres, half, rotation as for DeviceScene.triangles_in_obbs; returns what triangles_in_box returns."""
+        q = np.ascontiguousarray(obb_query_array(centres, half, rotation)).view(np.float32).reshape(-1, 15)
+        return self._overlap_host(WORLD_OVERLAPS["in_obb"], q, instance_mask, ignore_instance)
+
+    def triangles_touching_count_device(self, d_tris, n, d_counts=None, count=None, ids=None, instance_mask=None, ignore_instance=None,
+                                        skip_shared=False):
+        """triangles_in_box_count_device for n query triangles (TRI_QUERY_DTYPE bytes on the device, or a float32 [n, 9] cuda
+        tensor). skip_shared: records whose placed vertices share a position with the query's are left out
+        (RTK_TOUCH_SKIP_SHARED_VERTEX). There is no first_prim on a world: ignore_instance leaves a body's own triangles out."""
+        return self._overlap_count_device(WORLD_OVERLAPS["touching"], d_tris, n, d_counts, count, ids, instance_mask, ignore_instance, skip_shared)
+
+    def triangles_touching_all_device(self, d_tris, n, d_offsets, d_entries, d_written=None, count=None, ids=None, instance_mask=None,
+                                      ignore_instance=None, skip_shared=False):
+        """triangles_in_box_all_device for n query triangles; skip_shared as for triangles_touching_count_device."""
+        return self._overlap_all_device(WORLD_OVERLAPS["touching"], d_tris, n, d_offsets, d_entries, d_written, count, ids, instance_mask,
+                                        ignore_instance, skip_shared)
+
+    def triangles_touching_counted(self, d_tris, n, d_offsets=None, d_entries=None, d_counts=None, instance_mask=None, ignore_instance=None,
+                                   skip_shared=False):
+        """triangles_in_box_counted for n query triangles (rtk_dev_world_triangles_touching_counted)."""
+        return self._overlap_counted(WORLD_OVERLAPS["touching"], d_tris, n, d_offsets, d_entries, d_counts, instance_mask, ignore_instance, skip_shared)
+
+    def triangles_touching(self, tris, instance_mask=None, ignore_instance=None, skip_shared=False):
+        """tris: array-like (n, 9) or (n, 3, 3) float32, or TRI_QUERY_DTYPE records; returns what triangles_in_box returns."""
+        tris = np.asarray(tris)
+        q = np.ascontiguousarray(tris.view(np.float32) if tris.dtype == TRI_QUERY_DTYPE else np.asarray(tris, np.float32)).reshape(-1, 9)
+        return self._overlap_host(WORLD_OVERLAPS["touching"], q, instance_mask, ignore_instance, skip_shared)
 
 
 # -- the reference's own entry points, host pointers (reference rtk.h:126-130) --

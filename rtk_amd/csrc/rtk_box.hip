@@ -9,6 +9,7 @@
 //
 // FLOATING POINT: the flags of rtk_closest.hip (no contraction); every bit is the rule header's.
 #include "rtk_overlap_walk.h"
+#include "rtk_box_shape.h"
 
 // BX_RESOURCES: the compiler's report (gfx950, -O3, -Rpass-analysis=kernel-resource-usage) for each instantiated form
 // <FILL, COUNT>; scratch 0, no SGPR or VGPR spills and no AGPRs in every one of them:
@@ -20,36 +21,9 @@
 // A workgroup is four waves, one per SIMD, so "workgroups per CU" and "waves per SIMD" are the same number: the registers
 // (512 / 80 = 6) decide in every form, the 16 KB of the stack never do.
 
-namespace {
-
-struct Box {
-	typedef rtk_box_query Query;
-	typedef void Filter;
-	struct Extra {};
-	struct Prepared { float lo[3], hi[3], c[3], h[3]; };
-	static constexpr int FLOATS = 6;
-	static constexpr const char *NAME_COUNT = "rtk_dev_triangles_in_box_count", *NAME_ALL = "rtk_dev_triangles_in_box_all",
-		*NAME_COUNTED = "rtk_dev_triangles_in_box_counted", *NOUN = "boxes";
-
-	static bool extras(const Filter *, const char *, Extra &) { return true; }
-	static __device__ __forceinline__ bool prepare(const float *w, const Extra &, uint32_t, Prepared &Q)
-	{
-		for (int a = 0; a < 3; a++) { Q.lo[a] = w[a]; Q.hi[a] = w[3 + a]; }
-		rtk_box_centre(Q.lo, Q.hi, Q.c, Q.h);
-		return rtk_box_live(Q.lo, Q.hi);
-	}
-	static __device__ __forceinline__ bool skip(const Prepared &Q, const float *clo, const float *chi) { return rtk_box_skip(clo, chi, Q.lo, Q.hi); }
-	// rtk_box_candidate(v0, v1, v2, Q.lo, Q.hi, Q.c, Q.h), its one line spelled out: with the rule's call one level further down
-	// the compiler pairs the packed multiplies of the ten axes differently, and the kernels either need 4 VGPRs more (84 in the
-	// fill form: a wave per SIMD) or, with Q by value, the fill is 1 % slower on the device. This form compiles to the
-	// instructions rtk_box.hip had with a kernel of its own (profiles/overlap_walk_refactor.log)
-	static __device__ __forceinline__ bool candidate(const Prepared &Q, const float *v0, const float *v1, const float *v2, uint32_t)
-	{
-		return rtk_box_boxes_touch(v0, v1, v2, Q.lo, Q.hi) && !rtk_box_separated(v0, v1, v2, Q.c, Q.h);
-	}
-};
-
-} // namespace
+// THE SHAPE is rtk_box_shape.h's Box, which the walk of a world (rtk_world_overlap.hip) takes too: prepare is rtk_box_centre(..)
+// and rtk_box_live(..), skip is rtk_box_skip(..), candidate is rtk_box_candidate(..) spelled out as rtk_box_boxes_touch(..) &&
+// !rtk_box_separated(..) (that header says why). The table above is of the struct as it stands there.
 
 extern "C" uint32_t rtk_amd_box_stack_entries(void) { return OVERLAP_LDS_STACK; }
 

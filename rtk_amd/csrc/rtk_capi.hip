@@ -199,6 +199,67 @@ extern "C" int rtk_dev_world_closest_points_counted(const rtk_dev_world *w, cons
 	return rtk_launch_world_closest(w, d_queries, num_queries, nullptr, filter, d_records, d_instances, d_points, nullptr, out);
 }
 
+// Overlaps on a world (rtk_world_overlap.hip): per shape the three doors of one launch
+extern "C" int rtk_dev_world_triangles_in_box_count(const rtk_dev_world *w, const rtk_box_query *d_boxes, size_t num_queries,
+	const rtk_ray_list *list, const rtk_world_filter *filter, uint32_t *d_counts, void *stream)
+{
+	return rtk_launch_world_box(w, d_boxes, num_queries, list, filter, d_counts, nullptr, nullptr, false, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_world_triangles_in_box_all(const rtk_dev_world *w, const rtk_box_query *d_boxes, size_t num_queries,
+	const rtk_ray_list *list, const rtk_world_filter *filter, const uint64_t *d_offsets, uint64_t *d_entries, uint32_t *d_written, void *stream)
+{
+	return rtk_launch_world_box(w, d_boxes, num_queries, list, filter, d_written, d_offsets, d_entries, true, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_world_triangles_in_box_counted(const rtk_dev_world *w, const rtk_box_query *d_boxes, size_t num_queries,
+	const rtk_world_filter *filter, const uint64_t *d_offsets, uint64_t *d_entries, uint32_t *d_counts_or_written, rtk_trace_counters *out)
+{
+	if (!out) { rtk_set_error("rtk_dev_world_triangles_in_box_counted: NULL counters"); return RTK_AMD_ERR_BAD_ARG; }
+	return rtk_launch_world_box(w, d_boxes, num_queries, nullptr, filter, d_counts_or_written, d_offsets, d_entries, d_offsets != nullptr, nullptr, out);
+}
+
+extern "C" int rtk_dev_world_triangles_in_obb_count(const rtk_dev_world *w, const rtk_obb_query *d_obbs, size_t num_queries,
+	const rtk_ray_list *list, const rtk_world_filter *filter, uint32_t *d_counts, void *stream)
+{
+	return rtk_launch_world_obb(w, d_obbs, num_queries, list, filter, d_counts, nullptr, nullptr, false, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_world_triangles_in_obb_all(const rtk_dev_world *w, const rtk_obb_query *d_obbs, size_t num_queries,
+	const rtk_ray_list *list, const rtk_world_filter *filter, const uint64_t *d_offsets, uint64_t *d_entries, uint32_t *d_written, void *stream)
+{
+	return rtk_launch_world_obb(w, d_obbs, num_queries, list, filter, d_written, d_offsets, d_entries, true, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_world_triangles_in_obb_counted(const rtk_dev_world *w, const rtk_obb_query *d_obbs, size_t num_queries,
+	const rtk_world_filter *filter, const uint64_t *d_offsets, uint64_t *d_entries, uint32_t *d_counts_or_written, rtk_trace_counters *out)
+{
+	if (!out) { rtk_set_error("rtk_dev_world_triangles_in_obb_counted: NULL counters"); return RTK_AMD_ERR_BAD_ARG; }
+	return rtk_launch_world_obb(w, d_obbs, num_queries, nullptr, filter, d_counts_or_written, d_offsets, d_entries, d_offsets != nullptr, nullptr, out);
+}
+
+extern "C" int rtk_dev_world_triangles_touching_count(const rtk_dev_world *w, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_ray_list *list, const rtk_world_filter *filter, uint32_t touch_flags, uint32_t *d_counts, void *stream)
+{
+	return rtk_launch_world_touch(w, d_tris, num_queries, list, filter, touch_flags, d_counts, nullptr, nullptr, false, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_world_triangles_touching_all(const rtk_dev_world *w, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_ray_list *list, const rtk_world_filter *filter, uint32_t touch_flags, const uint64_t *d_offsets, uint64_t *d_entries, uint32_t *d_written,
+	void *stream)
+{
+	return rtk_launch_world_touch(w, d_tris, num_queries, list, filter, touch_flags, d_written, d_offsets, d_entries, true, (hipStream_t)stream);
+}
+
+extern "C" int rtk_dev_world_triangles_touching_counted(const rtk_dev_world *w, const rtk_tri_query *d_tris, size_t num_queries,
+	const rtk_world_filter *filter, uint32_t touch_flags, const uint64_t *d_offsets, uint64_t *d_entries, uint32_t *d_counts_or_written,
+	rtk_trace_counters *out)
+{
+	if (!out) { rtk_set_error("rtk_dev_world_triangles_touching_counted: NULL counters"); return RTK_AMD_ERR_BAD_ARG; }
+	return rtk_launch_world_touch(w, d_tris, num_queries, nullptr, filter, touch_flags, d_counts_or_written, d_offsets, d_entries, d_offsets != nullptr,
+		nullptr, out);
+}
+
 // Listed batches (rtk_ray_list): everything about the list that the host can see is refused here, before anything is launched
 static int listed_trace(const char *who, const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t num_rays, const rtk_ray_list *list,
 	rtk_hit_record *d_hits, uint8_t *d_occluded, bool any_hit, const rtk_dev_filter *filter, const rtk_trace_opts *opts, void *stream)

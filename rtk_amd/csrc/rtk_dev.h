@@ -446,6 +446,15 @@ int rtk_launch_world(const rtk_dev_world *w, const rtk_ray *d_rays, size_t n, co
 int rtk_launch_world_closest(const rtk_dev_world *w, const rtk_point_query *d_queries, size_t n, const rtk_ray_list *list,
 	const rtk_world_filter *filter, rtk_closest_record *d_records, uint32_t *d_instances, float *d_points, hipStream_t stream,
 	rtk_trace_counters *counted = nullptr);
+// -- rtk_dev_world_triangles_in_box_* / _in_obb_* / _touching_* (rtk_world_overlap.hip) --
+// fill: offsets, 64-bit entries, d_counts the written numbers or NULL; else d_counts the counts. counted: synchronises the stream
+int rtk_launch_world_box(const rtk_dev_world *w, const rtk_box_query *d_boxes, size_t n, const rtk_ray_list *list, const rtk_world_filter *filter,
+	uint32_t *d_counts, const uint64_t *d_offsets, uint64_t *d_entries, bool fill, hipStream_t stream, rtk_trace_counters *counted = nullptr);
+int rtk_launch_world_obb(const rtk_dev_world *w, const rtk_obb_query *d_obbs, size_t n, const rtk_ray_list *list, const rtk_world_filter *filter,
+	uint32_t *d_counts, const uint64_t *d_offsets, uint64_t *d_entries, bool fill, hipStream_t stream, rtk_trace_counters *counted = nullptr);
+int rtk_launch_world_touch(const rtk_dev_world *w, const rtk_tri_query *d_tris, size_t n, const rtk_ray_list *list, const rtk_world_filter *filter,
+	uint32_t touch_flags, uint32_t *d_counts, const uint64_t *d_offsets, uint64_t *d_entries, bool fill, hipStream_t stream,
+	rtk_trace_counters *counted = nullptr);
 // -- the look for an image nobody announced (rtk_detect.hip) --
 int rtk_detect_image(const rtk_dev_scene *ds, const rtk_ray *d_rays, size_t n, hipStream_t stream, uint32_t *w_out, uint32_t *h_out);
 // -- hit records to full hits, and rtk_trace_ray's one-ray launch (rtk_expand.hip) --

@@ -12,7 +12,7 @@
 //
 // FLOATING POINT: the flags of rtk_closest.hip (no contraction); every bit is the rule header's.
 #include "rtk_overlap_walk.h"
-#include "rtk_obb_rule.h"
+#include "rtk_obb_shape.h"
 
 // OB_RESOURCES: the compiler's report (gfx950, -O3, -Rpass-analysis=kernel-resource-usage) for each instantiated form
 // <FILL, COUNT>; scratch 0, no VGPR spills and no AGPRs in every one of them, so the node loop and the record loop touch no
@@ -26,28 +26,8 @@
 // A workgroup is four waves, one per SIMD, so "workgroups per CU" and "waves per SIMD" are the same number: the registers
 // decide in every form (the 27 floats of a query against the axis-aligned walk's 12), the 16 KB of the stack never do.
 
-namespace {
-
-struct Obb {
-	typedef rtk_obb_query Query;
-	typedef void Filter;
-	struct Extra {};
-	typedef rtk_obb_prepared Prepared;
-	static constexpr int FLOATS = 15;
-	static constexpr const char *NAME_COUNT = "rtk_dev_triangles_in_obb_count", *NAME_ALL = "rtk_dev_triangles_in_obb_all",
-		*NAME_COUNTED = "rtk_dev_triangles_in_obb_counted", *NOUN = "obbs";
-
-	static bool extras(const Filter *, const char *, Extra &) { return true; }
-	static __device__ __forceinline__ bool prepare(const float *w, const Extra &, uint32_t, Prepared &Q) { return rtk_obb_prepare(w, Q); }
-	static __device__ __forceinline__ bool skip(const Prepared &Q, const float *clo, const float *chi) { return rtk_obb_skip(Q, clo, chi); }
-	// (the walk only runs for a live query)
-	static __device__ __forceinline__ bool candidate(const Prepared Q, const float *v0, const float *v1, const float *v2, uint32_t)
-	{
-		return rtk_obb_candidate(Q, true, v0, v1, v2);
-	}
-};
-
-} // namespace
+// THE SHAPE is rtk_obb_shape.h's Obb, which the walk of a world (rtk_world_overlap.hip) takes too: prepare is rtk_obb_prepare(..),
+// skip is rtk_obb_skip(..), candidate is rtk_obb_candidate(..). The table above is of the struct as it stands there.
 
 extern "C" uint32_t rtk_amd_obb_stack_entries(void) { return OVERLAP_LDS_STACK; }
 

@@ -1,5 +1,5 @@
 // rtk_world_internal.h -- internal: the world object and what every walk of a world shares (rtk_world.hip: rays;
-// rtk_world_closest.hip: closest points): the stack frame's constants, the refusals the host can see, and the launch on the
+// rtk_world_closest.hip: closest points; rtk_world_overlap.hip: the three overlap queries): the stack frame's constants, the refusals the host can see, and the launch on the
 // (top tree, stream) scratch set.
 #pragma once
 
@@ -68,9 +68,13 @@ static inline int rtk_world_refuse(const char *who, const char *what, const rtk_
 // the scratch set of (top tree, stream) -- top_nodes .. top_num_tris, inst, scenes, num_instances, num_scenes, counter, spill,
 // spill_stride, spill_cap -- lets `extra(top, p)` add what only that walk reads under the top tree's lock, and enqueues `kernel`
 // on a resident grid, or, with `counted`, `counting` between a clear and a read of the visit counters (synchronises the stream).
-template <class Params, class Extra>
+// `from_scratch(sc, stream, p)` is the hook of a walk that needs more of the scratch set than the spill area and the counter (the
+// overlap walk's claim bits): it runs once the set is fetched and the spill area is sized, under both locks, ahead of the launch
+// on the same stream, and a result other than RTK_AMD_OK ends the call with it. The form without it is the one rays and closest
+// points call.
+template <class Params, class Extra, class FromScratch>
 int rtk_world_launch(rtk_dev_world *w, size_t n, hipStream_t stream, int blocks_per_cu, void (*kernel)(Params), void (*counting)(Params), Params &p,
-	Extra extra, rtk_trace_counters *counted, const char *who)
+	Extra extra, FromScratch from_scratch, rtk_trace_counters *counted, const char *who)
 {
 	std::lock_guard<std::mutex> wlock(w->mutex);
 	rtk_dev_scene *top = w->top;
@@ -97,6 +101,10 @@ int rtk_world_launch(rtk_dev_world *w, size_t n, hipStream_t stream, int blocks_
 	p.spill_stride = (uint32_t)(spill_cap ? sc->spill.capacity : 0);
 	p.spill_cap = (uint32_t)spill_cap;
 	p.counter = sc->d_counter;
+	{
+		const int rc = from_scratch(sc, stream, p);
+		if (rc != RTK_AMD_OK) return rc;
+	}
 	if (!counted) {
 		hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(WD_THREADS), 0, stream, p);
 		RTK_HIP_CHECK(hipGetLastError(), RTK_AMD_ERR_HIP);
@@ -117,4 +125,12 @@ int rtk_world_launch(rtk_dev_world *w, size_t n, hipStream_t stream, int blocks_
 		return RTK_AMD_ERR_BAD_SCENE;
 	}
 	return RTK_AMD_OK;
+}
+
+// ... without a hook: the spill area and the counter are all the walk takes from the scratch set
+template <class Params, class Extra>
+int rtk_world_launch(rtk_dev_world *w, size_t n, hipStream_t stream, int blocks_per_cu, void (*kernel)(Params), void (*counting)(Params), Params &p,
+	Extra extra, rtk_trace_counters *counted, const char *who)
+{
+	return rtk_world_launch(w, n, stream, blocks_per_cu, kernel, counting, p, extra, [](LaunchScratch *, hipStream_t, Params &) { return (int)RTK_AMD_OK; }, counted, who);
 }

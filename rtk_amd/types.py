@@ -26,6 +26,10 @@ CLOSEST_RECORD_DTYPE = np.dtype([("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), (
 BOX_QUERY_DTYPE = np.dtype([("lo", "<f4", (3,)), ("hi", "<f4", (3,))])
 # rtk_tri_query of include/rtk_amd.h (rtk_dev_triangles_touching_count / _all): a float32 [n, 9] array is one
 TRI_QUERY_DTYPE = np.dtype([("v0", "<f4", (3,)), ("v1", "<f4", (3,)), ("v2", "<f4", (3,))])
+# an entry of the overlap queries on a world (rtk_dev_world_triangles_in_box_all and its kin): one little-endian uint64,
+# instance << 32 | prim. An int64 / uint64 array viewed with this dtype is decoded; entries sort by instance, then by prim
+WORLD_ENTRY_DTYPE = np.dtype([("prim", "<u4"), ("instance", "<u4")])
+assert WORLD_ENTRY_DTYPE.itemsize == 8
 # rtk_sphere_sweep of include/rtk_amd.h (rtk_dev_sweep_spheres): a float32 [n, 9] array is one; its record is HIT_RECORD_DTYPE
 SPHERE_SWEEP_DTYPE = np.dtype([("origin", "<f4", (3,)), ("direction", "<f4", (3,)), ("min_t", "<f4"), ("max_t", "<f4"), ("radius", "<f4")])
 
